@@ -8,16 +8,23 @@ direct-LU path.  `value` = candidate steps executed / wall time of the timed loo
 A and the population already resident in HBM when the timed region starts.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full      # plus everything else it measures (see below)
     python bench.py --gpus 8 ...        # starts 8 ranks itself (torch.distributed.run), or is started by
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line: the metric, `per_step` (wall ms, active candidates and the K>=256 zgemm time of
-every timed loop body), `roofline` for the dominant kernel -- the MFMA zgemm of the LU trailing updates, every
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K loop bodies and prints the metric with
+`ms_per_step` and `per_step` (wall ms and active candidates of every timed loop body); nothing else runs.  With
+`--full` the line also carries `roofline` for the dominant kernel -- the MFMA zgemm of the LU trailing updates, every
 K>=256 launch bracketed by HIP events on the stream it runs on inside the timed region and rated over the union
 of those intervals, plus an untimed single-stream pass where every kernel is timed alone -- and, at N=1,
-`small_batch_rates` (the per-rank shares of 8/4/2-way sharding on one GPU) and a `cpu_baseline` object: the
-NumPy/SciPy oracle timed on this host's cores on a bounded sample.
+`small_batch_rates` (the per-rank shares of 8/4/2-way sharding on one GPU), a `cpu_baseline` object (the
+NumPy/SciPy oracle timed on this host's cores on a bounded sample) and `side_configs` (short runs of the other
+BASELINE.json configurations).
+
+`--dump-outputs DIR` writes, after the timed loop bodies, what they left in the population (the arrays a caller of
+MAUS_Solver reads back) as float64 .npy files under DIR; the inputs are seeded, so two builds can be compared file
+for file.
 """
 import argparse
 import json
@@ -39,6 +46,56 @@ HBM_PEAK_GBS = 8000.0
 PMC_ZGEMM = "r04_zgemm_pmc_traffic.json"
 PMC_KERNELS = "r04_pmc_traffic_per_kernel.json"
 PMC_MFMA = "r04_pmc_mfma_lds_per_kernel.json"
+DUMP_BUDGET_BYTES = 60_000_000      # arrays of one dump, npy headers aside: below 64 MB in either unit
+
+
+def dump_outputs(solver, out_dir):
+    """What the timed loop bodies left in the population, as a caller of MAUS_Solver reads it back after the last one:
+    per candidate in list order its id, state, eigenvalue / singular value (real, imag), residual and, for the vectors,
+    one row per candidate with real and imaginary parts side by side.  Only candidates the loop bodies have evaluated
+    are written: one spawned by the last body's population management still has residual_k = inf and the random start
+    the reference gives it (AMS:127), nothing computed yet.  Rows of every candidate while they fit the budget (below 64 MB),
+    otherwise of a fixed seeded sample of them (`vector_rows.npy` holds their positions in the written list)."""
+    from adaptive_matrix_solver_amd.solver import ProblemType
+    os.makedirs(out_dir, exist_ok=True)
+    pt = solver.problem_type
+    if pt == ProblemType.EIGENVALUE:
+        value = lambda c: complex(c.lambda_k)
+        vec_names = ("v",)
+    elif pt == ProblemType.SVD:
+        value = lambda c: complex(float(c.sigma_k))
+        vec_names = ("u", "right_v")
+    else:
+        value = lambda c: 0j
+        vec_names = ("x",)
+    cands = [c for c in solver.candidates if np.isfinite(float(c.residual_k)) and np.isfinite(value(c))]
+    arrays = {"candidate_id": np.array([c.id for c in cands], dtype=np.float64),
+              "state": np.array([c.state.value for c in cands], dtype=np.float64),
+              "residual": np.array([float(c.residual_k) for c in cands], dtype=np.float64)}
+    val = np.array([value(c) for c in cands], dtype=np.complex128)
+    if pt == ProblemType.EIGENVALUE:
+        arrays["lambda"] = np.stack([val.real, val.imag], axis=-1)
+    elif pt == ProblemType.SVD:
+        arrays["sigma"] = val.real.copy()
+    getters = {"v": lambda c: c.v_k, "x": lambda c: c.x_k, "u": lambda c: c.u_k, "right_v": lambda c: c.right_v_k}
+    rows_m, cols_m = solver.M.shape
+    width = {"v": cols_m, "x": cols_m, "u": rows_m, "right_v": cols_m}
+    row_bytes = 16 * sum(width[name] for name in vec_names)
+    room = DUMP_BUDGET_BYTES - sum(a.nbytes for a in arrays.values()) - 8 * len(cands)
+    max_rows = max(0, room // max(1, row_bytes))
+    rows = np.arange(len(cands))
+    if len(cands) > max_rows:
+        rows = np.sort(np.random.default_rng(0).choice(len(cands), size=max_rows, replace=False))
+    vecs = {name: np.array([getters[name](cands[k]) for k in rows.tolist()], dtype=np.complex128).reshape(len(rows), width[name])
+            for name in vec_names}
+    finite = np.ones(len(rows), dtype=bool)
+    for Z in vecs.values():
+        finite &= np.isfinite(Z).all(axis=1)
+    arrays["vector_rows"] = rows[finite].astype(np.float64)
+    for name, Z in vecs.items():
+        arrays[name] = np.stack([Z[finite].real, Z[finite].imag], axis=-1)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def cpu_baseline(A, n, budget_s=25.0):
@@ -181,11 +238,11 @@ def run_other_config(args):
     n = cfg["n"] if args.n is None else args.n
     P = cfg["pop"] if args.pop is None else args.pop
     kind = cfg["kind"]
-    steps_k = args.steps if "--steps" in sys.argv else cfg["steps"]
+    steps_k = args.steps if args.steps is not None else cfg["steps"]
     # Hermitian shortcut: every candidate converges in its first step, so a warm-up body on a scratch solver warms nothing
     # that the timed solver meets again -- and a second solver on the same engine would put a host comparison of two copies of
     # the matrix (is the resident decomposition still this matrix's?  ~100 ms at n = 8192) into the first timed loop body
-    warm_k = args.warmup if "--warmup" in sys.argv else (0 if kind == "herm" else 1)
+    warm_k = args.warmup if args.warmup is not None else (0 if kind == "herm" else 1)
     b = None
     if kind == "eig":
         A, PT = scenarios.ginibre(n, n), ProblemType.EIGENVALUE
@@ -245,6 +302,8 @@ def run_other_config(args):
         steps_done += act
     ctx.sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(solver, args.dump_outputs)
     # one more population from iteration 1 with every launch bracketed by HIP events: per-class kernel times (untimed)
     prof_solver = build(engine=eng, diag=diag)
     ctx.profile_enable(1)
@@ -376,11 +435,123 @@ def run_side_configs(args):
     return res
 
 
+def full_figures(args, prof, iso, iso_active, small, n, P, world):
+    """`--full`, c1: the fields of the bench line that come from the HIP events of the timed region, the isolated pass,
+    the committed PMC passes and the small-population runs."""
+    # Dominant kernel: the zgemm launches of the LU trailing updates proper (profile class "zgemm": K >= 256,
+    # ~70 % of the step).  The small-K launches of the panel recursion (classes zgemm_k128..k16, bandwidth-bound)
+    # are the same kernel template; they are timed in the isolated pass, where nothing overlaps them.
+    gk = [k for k in prof if k.startswith("zgemm")]
+    g = dict(prof["zgemm"])
+    tot_ms = sum(v["ms"] for v in prof.values())
+    exec_ratio = 0.75       # real flops executed on the matrix pipe / algorithmic 8MNK (3M complex products)
+    # rate = flops of the bracketed K>=256 launches / time during which at least one of them was executing (the
+    # union of their intervals over both sub-batch streams).  Two trailing updates running side by side share the
+    # machine: the plain sum of their event-to-event durations would count that time twice, and a sample's duration
+    # would depend on what the other stream happened to run beside it.
+    busy_ms = g.get("union_ms", 0.0) or g["ms"]
+    alg = (g["flops"] / (busy_ms * 1e-3) / 1e12) if busy_ms > 0 else 0.0
+    alg_sum = (g["flops"] / (g["ms"] * 1e-3) / 1e12) if g["ms"] > 0 else 0.0
+    per_launch_ms = g["ms"] / max(1, g["launches"])
+    # HBM bytes per K>=256 zgemm launch from the committed PMC passes (rocprofv3 --pmc cannot be combined with
+    # the timed run; profiles/<PMC_ZGEMM> holds the recipe).  Those passes ran the step as ONE chunk on one
+    # stream; the timed loop bodies run other batch sizes, so the measured bytes are scaled by the ratio of
+    # algorithmic bytes per launch (the traffic / algorithmic ratio is what carries over).
+    traffic = None
+    traffic_note = None
+    for name in (PMC_ZGEMM, "r02_zgemm_pmc_traffic.json"):
+        try:
+            with open(os.path.join(ROOT, "profiles", name)) as f:
+                pm = json.load(f)
+            if n == 4096 and P == 256 and world == 1 and g["launches"] > 0:
+                ratio = pm["hbm_bytes_per_launch"] / pm["algorithmic_bytes_per_launch"]
+                traffic = ratio * g["bytes"] / g["launches"]
+                traffic_note = {"pmc_hbm_bytes_per_launch": pm["hbm_bytes_per_launch"],
+                                "pmc_algorithmic_bytes_per_launch": pm["algorithmic_bytes_per_launch"],
+                                "hbm_over_algorithmic": ratio, "source": "profiles/" + name}
+            break
+        except Exception:
+            continue
+    # HBM-bound kernels: PMC bytes per sweep (a sweep of `matrices` solves, recorded in the file) scaled to the
+    # number of solves of the isolated pass, over their time in that pass
+    hbm_kernels = None
+    try:
+        if iso is not None and n == 4096 and iso_active > 0:
+            with open(os.path.join(ROOT, "profiles", PMC_KERNELS)) as f:
+                pk = json.load(f)
+            scale = iso_active / float(pk["matrices"])
+            hbm_kernels = {"matrices_in_isolated_pass": iso_active, "pmc_matrices": pk["matrices"],
+                           "source": "profiles/" + PMC_KERNELS}
+            for name in ("laswp", "trsm", "build_h", "lu_panel", "backsolve"):
+                if name in pk["classes"] and iso.get(name, {}).get("ms", 0) > 0:
+                    by = pk["classes"][name]["hbm_bytes"] * scale
+                    gbs = by / (iso[name]["ms"] * 1e-3) / 1e9
+                    hbm_kernels[name] = {"ms_per_sweep": round(iso[name]["ms"], 3), "hbm_bytes_per_sweep": by,
+                                         "achieved_GBs": round(gbs, 1), "frac_of_hbm_peak": round(gbs / HBM_PEAK_GBS, 3)}
+    except Exception:
+        hbm_kernels = None
+    pmc_mfma = None
+    try:
+        with open(os.path.join(ROOT, "profiles", PMC_MFMA)) as f:
+            pj = json.load(f)
+            pm = pj[[k for k in pj if k.startswith("zgemm3m_dma_kernel<2, 3, 2, 2, true")][0]]
+        pmc_mfma = {"kernel": "zgemm3m_dma_kernel<2, 3, 2, 2, true> (64x64 tiles: the K = 512 outer updates with M, N >= 1536)",
+                    "MfmaUtil": round(pm["mfma_util"], 4), "effective_clock_GHz": round(pm["effective_clock_GHz"], 3),
+                    "mfma_tflops_executed": round(pm["mfma_tflops_executed"], 2),
+                    "mfma_peak_tflops_at_effective_clock": round(pm["mfma_peak_tflops_at_effective_clock"], 2),
+                    "lds_bank_conflict_per_idx_active": pm.get("lds_bank_conflict_per_idx_active"),
+                    "wave_wait_any_share": round(pm["wait_any_share"], 3), "wave_wait_inst_share": round(pm["wait_inst_any_share"], 3),
+                    "source": "profiles/" + PMC_MFMA + " (SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE/8 x 1024 SIMDs); 256 solves, profiled run)"}
+    except Exception:
+        pmc_mfma = None
+    return {
+        "roofline": {"bound": "mfma", "kernel": "zgemm3m_dma_kernel (LDS-DMA staged 3M zgemm, 64x64 / 64x32 tiles), K>=256 launches (LU trailing updates, v_mfma_f64_16x16x4_f64)",
+                     # achieved / frac: real flops EXECUTED on the matrix pipe (3M: 6*M*N*K per complex GEMM) over the
+                     # union of the launches' intervals; the algorithmic (8*M*N*K) rate is a side field
+                     "achieved": alg * exec_ratio, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                     "frac": alg * exec_ratio / FP64_MFMA_PEAK_TFLOPS,
+                     "achieved_algorithmic_8mnk": alg, "frac_algorithmic_8mnk": alg / FP64_MFMA_PEAK_TFLOPS,
+                     "traffic": traffic, "traffic_detail": traffic_note,
+                     "algorithmic_bytes_per_launch": g["bytes"] / max(1, g["launches"]),
+                     "launches": g["launches"], "avg_launch_ms": per_launch_ms, "event_sampling": args.kernel_events,
+                     "busy_ms_union_over_streams": busy_ms, "sum_of_launch_ms": g["ms"],
+                     "achieved_algorithmic_by_sum_of_launch_durations": alg_sum,
+                     "flops_per_launch_algorithmic": g["flops"] / max(1, g["launches"]),
+                     "kernel_time_share": ((g["ms"] / tot_ms) if tot_ms > 0 else None) if args.kernel_events == "all" else None,
+                     "measured_mfma_f64_issue_rate_tflops": 77.9,
+                     # hardware counters of the K = 512 outer updates (separate rocprofv3 --pmc passes, committed)
+                     "pmc_counters": pmc_mfma,
+                     "lu_streams": os.environ.get("MAUS_LU_STREAMS", "1"),
+                     "isolated_single_stream_pass": None if iso is None else {
+                         "matrices": iso_active,
+                         "achieved_algorithmic_8mnk": iso["zgemm"]["flops"] / max(1e-9, iso["zgemm"]["ms"] * 1e-3) / 1e12,
+                         "avg_launch_ms": iso["zgemm"]["ms"] / max(1, iso["zgemm"]["launches"]),
+                         "launches": iso["zgemm"]["launches"],
+                         "achieved_algorithmic_all_zgemm_launches": sum(iso[k]["flops"] for k in gk) / max(1e-9, sum(iso[k]["ms"] for k in gk) * 1e-3) / 1e12,
+                         "all_zgemm_launches": sum(iso[k]["launches"] for k in gk),
+                         "kernel_ms": {k: round(v["ms"], 3) for k, v in iso.items()},
+                         "note": "one extra untimed step, MAUS_LU_STREAMS=1, every launch bracketed by HIP events"},
+                     "flop_convention": ("achieved = real flops executed on the matrix pipe: the kernel forms each complex product "
+                                         "from 3 real MFMA products (3M), 6*M*N*K per complex GEMM; *_algorithmic_8mnk counts the "
+                                         "8*M*N*K of the textbook complex product")},
+        ("kernel_ms" if args.kernel_events == "all" else "kernel_ms_estimated_from_sampled_launches"): {k: round(v["ms"], 3) for k, v in prof.items()},
+        "hbm_bound_kernels": hbm_kernels,
+        "small_batch_rates": small,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=None, help="timed loop bodies (default: 20 for c1, the configuration's for c2..c5)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed loop bodies before them (default: 5 for c1, the configuration's for c2..c5)")
+    ap.add_argument("--full", action="store_true",
+                    help="c1: besides the timed loop bodies, measure everything else -- roofline from HIP events around the K>=256 "
+                         "zgemm launches, the isolated single-stream pass, small_batch_rates, cpu_baseline and side_configs.  "
+                         "Without it a run times the loop bodies and prints the metric, nothing more")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed loop bodies, write what they left in the population (ids, states, eigen/singular "
+                         "values, residuals, vectors) as float64 .npy files under DIR, at most 64 MB")
     ap.add_argument("--size", dest="n", type=int, default=None, help="matrix order (default: the configuration's; the metric's 4096 for c1)")
     ap.add_argument("--pop", type=int, default=None, help="initial_num_candidates (default: the configuration's; the metric's 256 for c1)")
     ap.add_argument("--config", choices=["c1", "c2", "c3", "c4", "c5"], default="c1",
@@ -394,9 +565,9 @@ def main():
                          "AMS:303; the default here does too, into the device-backed store)")
     ap.add_argument("--no-isolated", action="store_true", help="skip the untimed single-stream kernel-timing pass")
     ap.add_argument("--no-small-batch", action="store_true", help="skip the pop = 32/64/128 side runs (N=1 only)")
-    ap.add_argument("--kernel-events", choices=["sampled", "all", "off"], default="sampled",
-                    help="HIP-event bracketing of kernel launches in the timed region: every K>=256 zgemm launch (default), "
-                         "every launch of every kernel (costs 3-5 %% of throughput), or none")
+    ap.add_argument("--kernel-events", choices=["sampled", "all", "off"], default=None,
+                    help="HIP-event bracketing of kernel launches in the timed region: every K>=256 zgemm launch (default "
+                         "with --full), every launch of every kernel (costs 3-5 %% of throughput), or none (default without --full)")
     ap.add_argument("--cpu-budget", type=float, default=40.0)
     ap.add_argument("--no-side", action="store_true",
                     help="default config only: skip the short runs of the other BASELINE.json configurations (c2, c3, c5, c4) that "
@@ -412,6 +583,8 @@ def main():
                          "(with MAUS_DIST_BACKEND=gloo without touching a GPU: tests/test_dist_gloo.py checks the --gpus N "
                          "self-launch with it)")
     args = ap.parse_args()
+    if args.kernel_events is None:
+        args.kernel_events = "sampled" if args.full else "off"
 
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
@@ -452,6 +625,8 @@ def main():
             sys.exit("bench.py: --config c2..c5 are single-GPU side benches (the driver's scaling run is the default config)")
         run_other_config(args)
         return
+    args.steps = 20 if args.steps is None else args.steps
+    args.warmup = 5 if args.warmup is None else args.warmup
     args.n = 4096 if args.n is None else args.n
     args.pop = 256 if args.pop is None else args.pop
     n, P = args.n, args.pop
@@ -544,6 +719,8 @@ def main():
                      "loop_body_ms": [round(float(x), 2) for x in allr[r, 4:4 + K]],
                      "lu_call_ms": [round(float(x), 2) for x in allr[r, 4 + K:4 + 2 * K]],
                      "collective_ms": [round(float(x), 3) for x in allr[r, 4 + 2 * K:4 + 3 * K]]} for r in range(world)]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(solver, args.dump_outputs)
     prof = ctx.profile_read()
     ctx.profile_enable(False)
     ws_allocs = ctx.lu_workspace_allocations()
@@ -551,7 +728,7 @@ def main():
     # that each kernel has the GPU to itself -- in the timed region two sub-batch streams overlap and a kernel's
     # event-to-event time includes whatever the other stream ran beside it.
     iso, iso_active = None, 0
-    if world == 1 and args.kernel_events != "off" and not args.no_isolated:
+    if args.full and world == 1 and args.kernel_events != "off" and not args.no_isolated:
         saved = os.environ.get("MAUS_LU_STREAMS")
         os.environ["MAUS_LU_STREAMS"] = "1"
         ctx.profile_enable(1)
@@ -568,7 +745,7 @@ def main():
     # Small per-rank populations on this one GPU (what each rank of an 8 / 4 / 2-way sharded run executes per step):
     # the ceiling of strong scaling before any communication.  Same matrix, same engine (workspace already sized).
     small = None
-    if world == 1 and not args.no_small_batch and n == 4096 and P == 256:
+    if args.full and world == 1 and not args.no_small_batch and n == 4096 and P == 256:
         small = {}
         for sp in (32, 64, 128):
             s2 = build(sp, engine=solver.engine, diag=solver.diag_info)
@@ -581,72 +758,6 @@ def main():
             del s2
 
     if rank == 0:
-        # Dominant kernel: the zgemm launches of the LU trailing updates proper (profile class "zgemm": K >= 256,
-        # ~70 % of the step).  The small-K launches of the panel recursion (classes zgemm_k128..k16, bandwidth-bound)
-        # are the same kernel template; they are timed in the isolated pass, where nothing overlaps them.
-        gk = [k for k in prof if k.startswith("zgemm")]
-        g = dict(prof["zgemm"])
-        tot_ms = sum(v["ms"] for v in prof.values())
-        exec_ratio = 0.75       # real flops executed on the matrix pipe / algorithmic 8MNK (3M complex products)
-        # rate = flops of the bracketed K>=256 launches / time during which at least one of them was executing (the
-        # union of their intervals over both sub-batch streams).  Two trailing updates running side by side share the
-        # machine: the plain sum of their event-to-event durations would count that time twice, and a sample's duration
-        # would depend on what the other stream happened to run beside it.
-        busy_ms = g.get("union_ms", 0.0) or g["ms"]
-        alg = (g["flops"] / (busy_ms * 1e-3) / 1e12) if busy_ms > 0 else 0.0
-        alg_sum = (g["flops"] / (g["ms"] * 1e-3) / 1e12) if g["ms"] > 0 else 0.0
-        per_launch_ms = g["ms"] / max(1, g["launches"])
-        # HBM bytes per K>=256 zgemm launch from the committed PMC passes (rocprofv3 --pmc cannot be combined with
-        # the timed run; profiles/<PMC_ZGEMM> holds the recipe).  Those passes ran the step as ONE chunk on one
-        # stream; the timed loop bodies run other batch sizes, so the measured bytes are scaled by the ratio of
-        # algorithmic bytes per launch (the traffic / algorithmic ratio is what carries over).
-        traffic = None
-        traffic_note = None
-        for name in (PMC_ZGEMM, "r02_zgemm_pmc_traffic.json"):
-            try:
-                with open(os.path.join(ROOT, "profiles", name)) as f:
-                    pm = json.load(f)
-                if n == 4096 and P == 256 and world == 1 and g["launches"] > 0:
-                    ratio = pm["hbm_bytes_per_launch"] / pm["algorithmic_bytes_per_launch"]
-                    traffic = ratio * g["bytes"] / g["launches"]
-                    traffic_note = {"pmc_hbm_bytes_per_launch": pm["hbm_bytes_per_launch"],
-                                    "pmc_algorithmic_bytes_per_launch": pm["algorithmic_bytes_per_launch"],
-                                    "hbm_over_algorithmic": ratio, "source": "profiles/" + name}
-                break
-            except Exception:
-                continue
-        # HBM-bound kernels: PMC bytes per sweep (a sweep of `matrices` solves, recorded in the file) scaled to the
-        # number of solves of the isolated pass, over their time in that pass
-        hbm_kernels = None
-        try:
-            if iso is not None and n == 4096 and iso_active > 0:
-                with open(os.path.join(ROOT, "profiles", PMC_KERNELS)) as f:
-                    pk = json.load(f)
-                scale = iso_active / float(pk["matrices"])
-                hbm_kernels = {"matrices_in_isolated_pass": iso_active, "pmc_matrices": pk["matrices"],
-                               "source": "profiles/" + PMC_KERNELS}
-                for name in ("laswp", "trsm", "build_h", "lu_panel", "backsolve"):
-                    if name in pk["classes"] and iso.get(name, {}).get("ms", 0) > 0:
-                        by = pk["classes"][name]["hbm_bytes"] * scale
-                        gbs = by / (iso[name]["ms"] * 1e-3) / 1e9
-                        hbm_kernels[name] = {"ms_per_sweep": round(iso[name]["ms"], 3), "hbm_bytes_per_sweep": by,
-                                             "achieved_GBs": round(gbs, 1), "frac_of_hbm_peak": round(gbs / HBM_PEAK_GBS, 3)}
-        except Exception:
-            hbm_kernels = None
-        pmc_mfma = None
-        try:
-            with open(os.path.join(ROOT, "profiles", PMC_MFMA)) as f:
-                pj = json.load(f)
-                pm = pj[[k for k in pj if k.startswith("zgemm3m_dma_kernel<2, 3, 2, 2, true")][0]]
-            pmc_mfma = {"kernel": "zgemm3m_dma_kernel<2, 3, 2, 2, true> (64x64 tiles: the K = 512 outer updates with M, N >= 1536)",
-                        "MfmaUtil": round(pm["mfma_util"], 4), "effective_clock_GHz": round(pm["effective_clock_GHz"], 3),
-                        "mfma_tflops_executed": round(pm["mfma_tflops_executed"], 2),
-                        "mfma_peak_tflops_at_effective_clock": round(pm["mfma_peak_tflops_at_effective_clock"], 2),
-                        "lds_bank_conflict_per_idx_active": pm.get("lds_bank_conflict_per_idx_active"),
-                        "wave_wait_any_share": round(pm["wait_any_share"], 3), "wave_wait_inst_share": round(pm["wait_inst_any_share"], 3),
-                        "source": "profiles/" + PMC_MFMA + " (SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE/8 x 1024 SIMDs); 256 solves, profiled run)"}
-        except Exception:
-            pmc_mfma = None
         ms_norm = [r["ms"] / max(1, r["active"]) for r in per_step]
         out = {
             "metric": "candidate-steps/sec, n=4096 dense eig pop=256, 1/2/4/8 GPUs vs CPU ref",
@@ -667,48 +778,18 @@ def main():
             "per_step_summary": {"ms_per_candidate_step_median": round(float(np.median(ms_norm)), 4),
                                  "ms_per_candidate_step_max": round(float(np.max(ms_norm)), 4),
                                  "lu_workspace_allocations_total": ws_allocs},
-            "roofline": {"bound": "mfma", "kernel": "zgemm3m_dma_kernel (LDS-DMA staged 3M zgemm, 64x64 / 64x32 tiles), K>=256 launches (LU trailing updates, v_mfma_f64_16x16x4_f64)",
-                         # achieved / frac: real flops EXECUTED on the matrix pipe (3M: 6*M*N*K per complex GEMM) over the
-                         # union of the launches' intervals; the algorithmic (8*M*N*K) rate is a side field
-                         "achieved": alg * exec_ratio, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": alg * exec_ratio / FP64_MFMA_PEAK_TFLOPS,
-                         "achieved_algorithmic_8mnk": alg, "frac_algorithmic_8mnk": alg / FP64_MFMA_PEAK_TFLOPS,
-                         "traffic": traffic, "traffic_detail": traffic_note,
-                         "algorithmic_bytes_per_launch": g["bytes"] / max(1, g["launches"]),
-                         "launches": g["launches"], "avg_launch_ms": per_launch_ms, "event_sampling": args.kernel_events,
-                         "busy_ms_union_over_streams": busy_ms, "sum_of_launch_ms": g["ms"],
-                         "achieved_algorithmic_by_sum_of_launch_durations": alg_sum,
-                         "flops_per_launch_algorithmic": g["flops"] / max(1, g["launches"]),
-                         "kernel_time_share": ((g["ms"] / tot_ms) if tot_ms > 0 else None) if args.kernel_events == "all" else None,
-                         "measured_mfma_f64_issue_rate_tflops": 77.9,
-                         # hardware counters of the K = 512 outer updates (separate rocprofv3 --pmc passes, committed)
-                         "pmc_counters": pmc_mfma,
-                         "lu_streams": os.environ.get("MAUS_LU_STREAMS", "1"),
-                         "isolated_single_stream_pass": None if iso is None else {
-                             "matrices": iso_active,
-                             "achieved_algorithmic_8mnk": iso["zgemm"]["flops"] / max(1e-9, iso["zgemm"]["ms"] * 1e-3) / 1e12,
-                             "avg_launch_ms": iso["zgemm"]["ms"] / max(1, iso["zgemm"]["launches"]),
-                             "launches": iso["zgemm"]["launches"],
-                             "achieved_algorithmic_all_zgemm_launches": sum(iso[k]["flops"] for k in gk) / max(1e-9, sum(iso[k]["ms"] for k in gk) * 1e-3) / 1e12,
-                             "all_zgemm_launches": sum(iso[k]["launches"] for k in gk),
-                             "kernel_ms": {k: round(v["ms"], 3) for k, v in iso.items()},
-                             "note": "one extra untimed step, MAUS_LU_STREAMS=1, every launch bracketed by HIP events"},
-                         "flop_convention": ("achieved = real flops executed on the matrix pipe: the kernel forms each complex product "
-                                             "from 3 real MFMA products (3M), 6*M*N*K per complex GEMM; *_algorithmic_8mnk counts the "
-                                             "8*M*N*K of the textbook complex product")},
-            ("kernel_ms" if args.kernel_events == "all" else "kernel_ms_estimated_from_sampled_launches"): {k: round(v["ms"], 3) for k, v in prof.items()},
-            "hbm_bound_kernels": hbm_kernels,
             "step_tflops": (8.0 / 3.0 * n ** 3 + 24.0 * n * n) * steps_done / elapsed / 1e12,
             "step_frac_of_mfma_peak": (8.0 / 3.0 * n ** 3 + 24.0 * n * n) * steps_done / elapsed / 1e12 / FP64_MFMA_PEAK_TFLOPS,
             # the same in the convention of roofline.frac: flops EXECUTED on the matrix pipe (the LU's 8/3 n^3 run as 3M
             # products, 0.75 of them; the 24 n^2 of the population products as 4M)
             "step_frac_of_mfma_peak_executed": (0.75 * 8.0 / 3.0 * n ** 3 + 24.0 * n * n)
                                                * steps_done / elapsed / 1e12 / FP64_MFMA_PEAK_TFLOPS,
-            "small_batch_rates": small,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out.update(full_figures(args, prof, iso, iso_active, small, n, P, world))
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(A, n, args.cpu_budget)
-        if world == 1 and not args.no_side and n == 4096 and P == 256:
+        if args.full and world == 1 and not args.no_side and n == 4096 and P == 256:
             # the headline context goes first: its LU workspace holds most of the device memory
             del solver
             ctx.close()

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/prof_r02
 rm -rf $O && mkdir -p $O
 cd $R
-B="bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-isolated --no-small-batch --skip-diagnosis"
+B="bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-isolated --no-small-batch --skip-diagnosis"
 # (1) kernel-trace + stats, default (three sub-batch streams)
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/default -- python3 $B > $O/default.json 2> $O/default.err
 # (2) the same on one stream, with the library's launch log (splits the zgemm dispatches by K)

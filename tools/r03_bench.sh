@@ -1,7 +1,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r03
 mkdir -p $O
-timeout -k 10 400 python bench.py > $O/bench_c1.json 2> $O/bench_c1.err && python tools/bench_summary.py $O/bench_c1.json
+timeout -k 10 400 python bench.py --full > $O/bench_c1.json 2> $O/bench_c1.err && python tools/bench_summary.py $O/bench_c1.json
 for c in c2 c3 c5; do
   timeout -k 10 300 python bench.py --config $c > $O/bench_$c.json 2> $O/bench_$c.err || tail -5 $O/bench_$c.err
   python - $O/bench_$c.json <<'PY'

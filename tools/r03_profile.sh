@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/prof_r03
 rm -rf $O && mkdir -p $O
 cd $R
-B="bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-isolated --no-small-batch --skip-diagnosis"
+B="bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-isolated --no-small-batch --skip-diagnosis"
 # (1) kernel-trace + stats of the bench (one stream: the default), with the library's launch log (splits the zgemm dispatches by K)
 MAUS_LU_TRACE=$O/lu_trace.txt rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $B > $O/stats.json 2> $O/stats.err
 python3 tools/k256_durations.py $O/lu_trace.txt $O/stats > $O/zgemm_durations_by_k.txt

@@ -3,7 +3,7 @@ set -e
 O=gpurun_out/r03
 mkdir -p $O
 for s in 1 2; do
-  MAUS_LU_STREAMS=$s timeout -k 10 300 python bench.py --no-cpu-baseline --no-small-batch --no-isolated > $O/streams_$s.json 2> $O/streams_$s.err
+  MAUS_LU_STREAMS=$s timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-small-batch --no-isolated > $O/streams_$s.json 2> $O/streams_$s.err
   python - $O/streams_$s.json $s <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

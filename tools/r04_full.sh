@@ -8,7 +8,7 @@ echo "pytest rc=$?" >> $O/${T}_tests.txt
 tail -22 $O/${T}_tests.txt
 grep -q "rc=0" $O/${T}_tests.txt || { echo TESTS FAILED; exit 1; }
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-( time timeout -k 10 600 python bench.py > $O/${T}_c1.json 2> $O/${T}_c1.err ) 2>&1 | grep real
+( time timeout -k 10 600 python bench.py --full > $O/${T}_c1.json 2> $O/${T}_c1.err ) 2>&1 | grep real
 python tools/bench_summary.py $O/${T}_c1.json
 python - $O/${T}_c1.json <<'PY'
 import json,sys
