@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libmaus_hip.so")
 
 # every symbol include/maus_hip.h declares (tests/test_cabi_symbols.py checks the list against the header)
 SYMBOLS = [
-    "maus_ctx_create", "maus_ctx_destroy", "maus_last_error", "maus_device_info", "maus_abi_version",
+    "maus_ctx_create", "maus_ctx_destroy", "maus_last_error", "maus_device_info", "maus_abi_version", "maus_lu_max_n",
     "maus_set_matrix", "maus_set_rhs", "maus_pop_reserve", "maus_pop_capacity", "maus_pop_put", "maus_pop_get", "maus_pop_copy", "maus_pop_device_ptr", "maus_hist_append", "maus_hist_get", "maus_hist_clear", "maus_hist_generation",
     "maus_matvec_rayleigh", "maus_shifted_lu_solve", "maus_lu_reserve", "maus_lu_workspace_allocs", "maus_set_shared_device", "maus_lu_mw_aborts", "maus_relax_normalise", "maus_residual",
     "maus_svd_power_step", "maus_svd_power_propose", "maus_svd_commit", "maus_set_eigvecs", "maus_herm_match", "maus_herm_tridiag", "maus_herm_release", "maus_herm_tridiag_eig", "maus_herm_tridiag_eigvals", "maus_herm_backtransform", "maus_get_eigvecs", "maus_gmres", "maus_gmres_pert", "maus_jacobi_check",
@@ -66,6 +66,7 @@ def load_library():
         "maus_last_error": ([vp], C.c_char_p),
         "maus_device_info": ([vp, C.c_char_p, C.c_int, ip, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)], C.c_int),
         "maus_abi_version": ([], C.c_int),
+        "maus_lu_max_n": ([], C.c_int),
         "maus_set_matrix": ([vp, vp, C.c_int, C.c_int], C.c_int),
         "maus_set_rhs": ([vp, vp, C.c_int], C.c_int),
         "maus_pop_reserve": ([vp, C.c_int], C.c_int),
@@ -221,6 +222,10 @@ class Context:
         """Tell the library that other processes use this GPU too (ranks of a gloo rehearsal on one device): kernels that
         need every one of their workgroups resident at once (the multi-workgroup LU panel) are then never used."""
         self._ck(self.lib.maus_set_shared_device(self.h, 1 if shared else 0), "maus_set_shared_device")
+
+    def lu_max_n(self) -> int:
+        """Largest n the direct LU path and both GMRES modes accept in this build of the library."""
+        return int(self.lib.maus_lu_max_n())
 
     def lu_mw_aborts(self) -> int:
         """Batches that were repeated with one panel workgroup per matrix after a rendezvous time-out."""

@@ -239,6 +239,7 @@ static void prof_resolve(maus_ctx* c) {
 extern "C" {
 
 int maus_abi_version(void) { return 1; }
+int maus_lu_max_n(void) { return 16384; }
 
 int maus_ctx_create(int device, maus_ctx** out) {
     if (!out) return -1;
@@ -635,9 +636,12 @@ int maus_matvec_rayleigh(maus_ctx* c, const int* slots, int count, double* num, 
 // ~100 GB costs seconds, so a workspace that follows the batch size step by step (the eig population grows by up to 15
 // candidates per iteration, AMS:533-534) would re-allocate inside somebody's timed region.  Callers that know their
 // population announce it with maus_lu_reserve(); batches beyond the workspace run in chunks.
+// Above npad = 8192 one solve's H + U is 2.6 GB (n = 9000) to 8.6 GB (n = 16384): the workspace is sized to the solves asked
+// for instead of a multiple of 32 (which would claim 0.8 of the device for the condition estimator's single solve).
 static int ensure_lu_ws(maus_ctx* c, int n, int want) {
     int npad = round_up(n, 32);
-    if (npad > maus_lu_max_npad()) FAIL(c, "direct LU path supports n <= 8192 in this build");
+    if (n > maus_lu_max_n() || npad > maus_lu_max_npad()) FAIL(c, "direct LU path supports n <= 16384 in this build");
+    const int gran = (npad > 8192) ? 1 : 32;                                  // allocation granule (solves)
     size_t per = 2 * sizeof(c128) * (size_t)npad * lu_ntiles(npad) * LU_TW;    // H and the logical-order U array (implicit pivoting), tile-major (luws.h)
     if (c->H && c->Hnpad == npad && (c->Hg >= want || c->ws_at_limit)) return 0;     // at the limit: callers chunk
     const bool second = c->H && c->Hnpad == npad;
@@ -647,7 +651,7 @@ static int ensure_lu_ws(maus_ctx* c, int n, int want) {
     int gmax = (int)std::max<size_t>(1, (size_t)(fr * 0.80) / per);
     const char* env = getenv("MAUS_LU_BATCH");
     int cap = env ? std::max(1, atoi(env)) : 512;
-    int G = round_up(want, 32);
+    int G = round_up(want, gran);
     if (c->H && c->Hnpad == npad) G = std::max(G, cap);               // a second allocation goes straight to the limit: never a third
     G = std::min(std::min(G, cap), gmax);
     if (c->H && c->Hnpad == npad && c->Hg >= G) { c->ws_at_limit = true; return 0; }   // nothing more to be had
@@ -667,11 +671,11 @@ static int ensure_lu_ws(maus_ctx* c, int n, int want) {
     // than fail the step.  (Round 2 also slept and retried here, on the theory that memory of a process that has just exited
     // comes back late; that was never shown and is gone.)
     {
-        const int floor_g = std::min(G, std::max(32, round_up(std::min(want, 64), 32)));
+        const int floor_g = std::min(G, std::max(gran, round_up(std::min(want, 64), gran)));
         while (hipMalloc((void**)&c->H, per * G) != hipSuccess) {
             (void)hipGetLastError();
             c->H = nullptr;
-            if (G > floor_g) G = std::max(floor_g, std::min(G - 32, (G * 3 / 4) / 32 * 32));
+            if (G > floor_g) G = std::max(floor_g, std::min(G - gran, (G * 3 / 4) / gran * gran));
             else FAIL(c, "LU workspace: hipMalloc failed even for the smallest batch (out of device memory)");
         }
     }

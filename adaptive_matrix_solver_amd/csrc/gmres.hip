@@ -45,6 +45,7 @@ struct GState {
     c128 h[MAXR][MAXR + 1];
 };
 
+template <int NT = GT>
 __device__ __forceinline__ double blk_sum(double v, double* sbuf) {
     v = wave_sum(v);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -53,7 +54,7 @@ __device__ __forceinline__ double blk_sum(double v, double* sbuf) {
     __syncthreads();
     double t = 0.0;
 #pragma unroll
-    for (int w = 0; w < GT / 64; ++w) t += sbuf[w];
+    for (int w = 0; w < NT / 64; ++w) t += sbuf[w];
     return t;
 }
 
@@ -261,10 +262,12 @@ gmres_compact_kernel(const GState* __restrict__ st, int count, int rows_per, int
     if (threadIdx.x == 0) *nact = sbase;
 }
 
-template <int EPT>
-__global__ void __launch_bounds__(GT)
+// EPT entries of the candidate's vectors per thread of an NT-thread workgroup: 256 threads up to n = 8192, 512 threads (EPT 32,
+// the same 128 VGPRs of w) for 8192 < n <= 16384
+template <int EPT, int NT = GT>
+__global__ void __launch_bounds__(NT)
 gmres_post_kernel(GArgs a, const int* __restrict__ act) {
-    __shared__ double sbuf[GT / 64];
+    __shared__ double sbuf[NT / 64];
     __shared__ c128 s_h[MAXR + 2];
     __shared__ c128 s_y[MAXR + 1];
     __shared__ int s_flag[2];                 // [0]: x update requested, [1]: candidate finished this tick
@@ -286,7 +289,7 @@ gmres_post_kernel(GArgs a, const int* __restrict__ act) {
         double ss = 0.0;
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
-            const int i = tid + e * GT;
+            const int i = tid + e * NT;
             if (i < n) {
                 c128 hx = y[i]; cfma(hx, sh, x[i]);
                 const c128 r = cmake(b[i].x - hx.x, b[i].y - hx.y);
@@ -294,7 +297,7 @@ gmres_post_kernel(GArgs a, const int* __restrict__ act) {
                 ss = fma(r.x, r.x, ss); ss = fma(r.y, r.y, ss);
             }
         }
-        const double rnorm = sqrt(blk_sum(ss, sbuf));
+        const double rnorm = sqrt(blk_sum<NT>(ss, sbuf));
         bool done = false; int info = 0;
         double pmf = s.pmf, ptol = s.ptol; int cycle = s.cycle;
         if (!(rnorm == rnorm)) { done = true; info = a.maxiter; }              // NaN: can never pass a test
@@ -318,14 +321,14 @@ gmres_post_kernel(GArgs a, const int* __restrict__ act) {
         double sv = 0.0;
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
-            const int i = tid + e * GT;
+            const int i = tid + e * NT;
             if (i < n) { w[e] = psolve1(a, k, i, w[e]); sv = fma(w[e].x, w[e].x, sv); sv = fma(w[e].y, w[e].y, sv); }
         }
-        const double tmp = sqrt(blk_sum(sv, sbuf));
+        const double tmp = sqrt(blk_sum<NT>(sv, sbuf));
         const double inv = 1.0 / tmp;
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
-            const int i = tid + e * GT;
+            const int i = tid + e * NT;
             if (i < n) Vk[i] = cmake(w[e].x * inv, w[e].y * inv);
         }
         if (tid == 0) {
@@ -342,49 +345,49 @@ gmres_post_kernel(GArgs a, const int* __restrict__ act) {
     double ss = 0.0;
 #pragma unroll
     for (int e = 0; e < EPT; ++e) {
-        const int i = tid + e * GT;
+        const int i = tid + e * NT;
         if (i < n) {
             c128 av = y[i]; cfma(av, sh, z[i]);
             w[e] = psolve1(a, k, i, av);
             ss = fma(w[e].x, w[e].x, ss); ss = fma(w[e].y, w[e].y, ss);
         }
     }
-    const double h0 = sqrt(blk_sum(ss, sbuf));
+    const double h0 = sqrt(blk_sum<NT>(ss, sbuf));
     for (int kk = 0; kk <= col; ++kk) {                        // modified Gram-Schmidt
         const c128* vk = Vk + (long)kk * n;
         double tr = 0.0, ti = 0.0;
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
-            const int i = tid + e * GT;
+            const int i = tid + e * NT;
             if (i < n) {
                 const c128 v = vk[i];
                 tr = fma(v.x, w[e].x, tr); tr = fma(v.y, w[e].y, tr);
                 ti = fma(v.x, w[e].y, ti); ti = fma(-v.y, w[e].x, ti);
             }
         }
-        tr = blk_sum(tr, sbuf); ti = blk_sum(ti, sbuf);
+        tr = blk_sum<NT>(tr, sbuf); ti = blk_sum<NT>(ti, sbuf);
         const c128 t = cmake(tr, ti);
         if (tid == 0) s_h[kk] = t;
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
-            const int i = tid + e * GT;
+            const int i = tid + e * NT;
             if (i < n) cfms(w[e], t, vk[i]);
         }
     }
     ss = 0.0;
 #pragma unroll
     for (int e = 0; e < EPT; ++e) {
-        const int i = tid + e * GT;
+        const int i = tid + e * NT;
         if (i < n) { ss = fma(w[e].x, w[e].x, ss); ss = fma(w[e].y, w[e].y, ss); }
     }
-    const double h1 = sqrt(blk_sum(ss, sbuf));
+    const double h1 = sqrt(blk_sum<NT>(ss, sbuf));
     const bool brk = h1 <= EPS * h0;
     {
         c128* vn = Vk + (long)(col + 1) * n;
         const double inv = brk ? 1.0 : 1.0 / h1;
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
-            const int i = tid + e * GT;
+            const int i = tid + e * NT;
             if (i < n) vn[i] = cmake(w[e].x * inv, w[e].y * inv);
         }
     }
@@ -434,7 +437,7 @@ gmres_post_kernel(GArgs a, const int* __restrict__ act) {
     if (s_flag[0]) {                                           // x += y @ V[:col+1]
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
-            const int i = tid + e * GT;
+            const int i = tid + e * NT;
             if (i < n) {
                 c128 acc = x[i];
                 for (int j = 0; j <= col; ++j) cfma(acc, s_y[j], Vk[(long)j * n + i]);
@@ -491,7 +494,7 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
     if (rhs_mode == 1 && (!c->b || c->bn != c->rows)) FAIL(c, "maus_gmres: rhs b not set");
     if (count <= 0) return 0;
     const int n = c->rows;
-    if (n > 32 * GT) FAIL(c, "maus_gmres: n <= 8192 in this build");
+    if (n > maus_lu_max_n()) FAIL(c, "maus_gmres: n <= 16384 in this build");
     const int R = std::max(1, std::min(std::min(restart, MAXR), n));
     if (maxiter < 1) maxiter = 1;
     if (upload_slots(c, slots, count)) return -1;
@@ -542,7 +545,8 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
         { ProfScope ps(c, KC_VEC, 0, 16.0 * h_nact * (double)n * (R + 4));
           if (n <= 4 * GT) hipLaunchKernelGGL((gmres_post_kernel<4>), dim3(h_nact), dim3(GT), 0, c->st, a, act);
           else if (n <= 16 * GT) hipLaunchKernelGGL((gmres_post_kernel<16>), dim3(h_nact), dim3(GT), 0, c->st, a, act);
-          else hipLaunchKernelGGL((gmres_post_kernel<32>), dim3(h_nact), dim3(GT), 0, c->st, a, act); }
+          else if (n <= 32 * GT) hipLaunchKernelGGL((gmres_post_kernel<32>), dim3(h_nact), dim3(GT), 0, c->st, a, act);
+          else hipLaunchKernelGGL((gmres_post_kernel<32, 2 * GT>), dim3(h_nact), dim3(2 * GT), 0, c->st, a, act); }
     }
     hipLaunchKernelGGL(gmres_finish_kernel, dim3(count), dim3(GT), 0, c->st, a, c->W, c->ldp, outs, outs + count, outs + 2 * count);
     if (maus_d2h(c, info_out, outs, sizeof(int) * count, c->st)) return -1;

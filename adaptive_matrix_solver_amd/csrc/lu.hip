@@ -168,8 +168,10 @@ __device__ unsigned long long g_panel_clk[16];
 //   (c') the row update above, U broadcast from LDS, L read from the row's own finished columns
 //   (d') the pivot steps on the register sub-block: max |re|+|im| over the logical rows >= the diagonal, first index wins
 //        (LAPACK izamax); the two owner threads exchange register rows and the physical rows they stand for
-// PWL = 4 columns with up to 8 rows per thread (m <= 4096), 2 columns with 16 rows per thread (m <= 8192) -- the same 128
-// VGPRs of sub-block either way.
+// PWL = 4 columns with up to 8 rows per thread (m <= 4096), 2 columns with 16 rows per thread (m <= 8192), 1 column with 32
+// rows per thread (m <= 16384, the tall panel of n > 8192) -- the same 128 VGPRs of sub-block in every case.  The tall panel
+// re-reads more finished columns (one-column sub-blocks: 136 column reads per 16-wide panel instead of 72 with two columns) and is chosen only
+// for m > 8192, so every panel of an n <= 8192 factorisation keeps its kernel.
 // Where its time goes (in-kernel clocks, -DMAUS_PANEL_CLOCK + tools/panel_clocks.py, profiles/r02_panel_phase_clocks.txt):
 // per panel ~45 us (32 solves) to ~100 us (181 solves) in the left-looking loads, ~38 us in the 16 column steps (2.4 us
 // each, instruction-bound: ~800 instructions per step and wave at 4 rows per thread), ~20 us store + barrier, ~9 us (b').
@@ -206,8 +208,8 @@ __device__ __forceinline__ void panel_store_diaginv(const c128 (*sL)[17], c128* 
 }
 
 // physical rows of a thread's logical rows (k is a compile-time constant at every use: the loops are unrolled).  LDS_BACKED: the
-// 16-rows-per-thread variant (m > 4096) keeps them in LDS, [k][thread] as 16-bit entries (npad <= 8192) -- in registers they
-// were what the kernel spilled
+// 16- and 32-rows-per-thread variants (m > 4096) keep them in LDS, [k][thread] as 16-bit entries (npad <= 16384: 32 KB at 32
+// rows per thread) -- in registers they were what the kernel spilled
 template <int RPT, bool LDS_BACKED> struct PhysRows;
 template <int RPT> struct PhysRows<RPT, false> {
     int v[RPT];
@@ -882,7 +884,7 @@ trsm_mfma_kernel(const c128* __restrict__ Hg, c128* __restrict__ Ug, long stride
     c128* U = Ug + (long)g * strideH;
     const int* perm = perm_g + (long)g * npad + j;
     const int q = lane >> 4, i16 = lane & 15;
-    // addresses = wave-uniform 64-bit base + 32-bit lane offset (a physical row is at most 8192 * 1 KB into a tile): one VGPR per
+    // addresses = wave-uniform 64-bit base + 32-bit lane offset (a physical row is at most 16384 * 1 KB into a tile): one VGPR per
     // address instead of two keeps the 4 NB tile loads that are in flight together inside the register budget
     const c128* Hs = H + lu_tile_off(npad, col0);                            // this strip's tile column, physical row 0
     c128* Us = U + lu_tile_off(npad, col0) + (long)j * LU_TW;                // this strip's tile column, logical row j
@@ -985,6 +987,7 @@ trsm_mfma_kernel(const c128* __restrict__ Hg, c128* __restrict__ Ug, long stride
 // Back substitution U x = y (y = augmented column npad).  One workgroup per matrix,
 // 32-row blocks from the bottom: dot products of the U row tails against x (LDS), then a
 // 32x32 triangle solved by one wave.  Writes x[0..n) to W[slot]; flags bit1 <- non-finite x.
+// LDS holds x[row_lo, row_hi) only: npad entries for the whole matrix, the block's own rows in the blocked form.
 // ---------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(512)
 backsolve_kernel(c128* __restrict__ Hg, long ld, long strideH, int n, int npad,
@@ -995,8 +998,9 @@ backsolve_kernel(c128* __restrict__ Hg, long ld, long strideH, int n, int npad,
     // x then goes back into the augmented column, where the update of the rows above reads it; the whole matrix in one
     // launch is row_lo = 0, row_hi = npad
     const bool whole = (row_lo == 0 && row_hi == npad);
-    extern __shared__ c128 sx[];          // npad entries of x, then a 32x33 diagonal block, then 2 x 32 partial sums
-    c128* sD = sx + npad;
+    extern __shared__ c128 sxm[];         // row_hi - row_lo entries of x, then a 32x33 diagonal block, then 2 x 32 partial sums
+    c128* sD = sxm + (row_hi - row_lo);
+    auto sx = [&](int j) -> c128& { return sxm[j - row_lo]; };
     c128* sP = sD + BSB * (BSB + 1);           // 2 x 32 partial sums of the block's rows
     const int g = blockIdx.x;
     c128* H = Hg + (long)g * strideH;
@@ -1028,7 +1032,7 @@ backsolve_kernel(c128* __restrict__ Hg, long ld, long strideH, int n, int npad,
                 for (int q = 0; q < 4; ++q) {
                     const int tq = t + 2 * q, j = (tq << 6) + lane;
                     const bool ok = tq < t_hi && j >= jt && j < row_hi;
-                    xv[q] = ok ? sx[j] : cmake(0.0, 0.0);
+                    xv[q] = ok ? sx(j) : cmake(0.0, 0.0);
                     const long off = ((long)tq * npad << 6) + lane;
 #pragma unroll
                     for (int r = 0; r < 8; ++r) u[q][r] = ok ? rbase[(long)r * ld + off] : cmake(0.0, 0.0);
@@ -1060,7 +1064,7 @@ backsolve_kernel(c128* __restrict__ Hg, long ld, long strideH, int n, int npad,
                 c128 xj = cmul(rv, dinv);                         // meaningful on lane j only
                 xj.x = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(xj.x), j), __builtin_amdgcn_readlane(__double2loint(xj.x), j));
                 xj.y = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(xj.y), j), __builtin_amdgcn_readlane(__double2loint(xj.y), j));
-                if (lane == j) { sx[i0 + j] = xj; if (!whole) H[(long)(i0 + j) * ld + lu_tile_off(npad, npad)] = xj; }
+                if (lane == j) { sx(i0 + j) = xj; if (!whole) H[(long)(i0 + j) * ld + lu_tile_off(npad, npad)] = xj; }
                 if (lane < j) cfms(rv, sD[lane * (BSB + 1) + j], xj);
             }
         }
@@ -1068,7 +1072,7 @@ backsolve_kernel(c128* __restrict__ Hg, long ld, long strideH, int n, int npad,
     }
     if (!whole) return;
     c128* out = (Wg != nullptr) ? Wg + (long)slots[g] * ldw : xout_dense + (long)g * n;
-    for (int i = tid; i < n; i += blockDim.x) { c128 v = sx[i]; bad |= !cfinite(v); out[i] = v; }
+    for (int i = tid; i < n; i += blockDim.x) { c128 v = sx(i); bad |= !cfinite(v); out[i] = v; }
     if (__any(bad) && lane == 0) atomicOr(&flags[g], 2);
 }
 
@@ -1146,7 +1150,8 @@ static void lu_panel(const LuWs& w, int j0) {
         prof(w, KC_PANEL, 1, 8.0 * m * NBP * NBP / 2 * w.G, 16.0 * m * NBP * 2 * w.G);
         return;
     }
-    if (w.mw_sync && m > 1024) {
+    // (not for npad > 8192: there a candidate's bits must not depend on how many solves share its call, and this kernel's choice does)
+    if (w.mw_sync && m > 1024 && w.npad <= 8192) {
         static const int ncu = [] { int v = 0; int dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev); return v > 0 ? v : 256; }();
         auto p2floor = [](int x) { int p = 1; while (2 * p <= x) p *= 2; return p; };
         auto p2ceil = [](int x) { int p = 1; while (p < x) p *= 2; return p; };
@@ -1166,7 +1171,8 @@ static void lu_panel(const LuWs& w, int j0) {
     // 8-column register sub-blocks where the rows per thread allow it (m <= 2048): 24 instead of 40 column reads per panel
     // (33.0 vs 34.4 ms per 181-solve sweep, 37.5 vs 39.1 at 256, against 4-column sub-blocks everywhere)
     if (rpt <= 1) PANEL_IP(1, 8); else if (rpt <= 2) PANEL_IP(2, 8); else if (rpt <= 4) PANEL_IP(4, 8);
-    else if (rpt <= 8) PANEL_IP(8, 4); else PANEL_IP(16, 2);
+    else if (rpt <= 8) PANEL_IP(8, 4); else if (rpt <= 16) PANEL_IP(16, 2);
+    else PANEL_IP(32, 1);                         // m > 8192: the tall panel (npad > 8192 only)
 #undef PANEL_IP
     prof(w, KC_PANEL, 1, 8.0 * m * NBP * NBP / 2 * w.G, 16.0 * m * NBP * 8 * w.G);
 }
@@ -1188,8 +1194,9 @@ extern "C" int maus_debug_panel_clocks(unsigned long long* out, int reset) {
     return 0;
 }
 #endif
-// Maximum rows the base panel can own (512 threads x 16 rows per thread in the 2-column sub-block variant)
-int maus_lu_max_npad() { return PT * 16; }
+// Maximum rows the base panel can own (512 threads x 32 rows per thread in the 1-column sub-block variant).  16-bit physical
+// rows in the panel's LDS and 32-bit lane offsets of the triangular solves hold up to here, not beyond.
+int maus_lu_max_npad() { return PT * 32; }
 #if MAUS_NBP == 16
 size_t maus_lu_mw_sync_bytes() { return sizeof(MwSync); }
 #else
@@ -1211,7 +1218,7 @@ void maus_lu_factor(const LuWs& w, int nbo) {
 
 void maus_lu_backsolve(const LuWs& w, c128* Wpop, long ldw, const int* d_slots, c128* xout_dense) {
     prof(w, KC_BACKSOLVE, 0);
-    size_t shm = sizeof(c128) * ((size_t)w.npad + BSB * (BSB + 1) + 2 * BSB);
+    auto shm_for = [](int rows) { return sizeof(c128) * ((size_t)rows + BSB * (BSB + 1) + 2 * BSB); };
     static bool attr_set = false;
     if (!attr_set) {   // ~83 KB of dynamic LDS at npad = 4096, 145 KB at 8192 (160 KB per CU on gfx950)
         (void)hipFuncSetAttribute((const void*)backsolve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
@@ -1221,17 +1228,23 @@ void maus_lu_backsolve(const LuWs& w, c128* Wpop, long ldw, const int* d_slots, 
     // matrix at ~40 GB/s, 3.3 ms whatever the batch.  Then the substitution runs in blocks of 256 columns: the block's own
     // triangle by the kernel above (x back into the augmented column), everything above it as ONE product over the whole
     // batch, y[0 : b0] -= U[0 : b0, block] x_block on the skinny zgemm (N = 1: the chip's bandwidth instead of G CUs').
+    // Above npad = 8192 the blocked form is the only one (x of the whole matrix no longer fits in LDS) and is chosen from the
+    // size alone -- never from the batch -- so that a candidate's bits do not depend on how many solves share its call.  The
+    // blocks are counted from the bottom; when npad is not a multiple of 256 the top block is the short one (npad is a multiple
+    // of 32, and the zgemm takes K-tiles at any 16-column offset).
     constexpr int BB = 256;                                  // (128 .. 1024 measured: 2.2-2.4 ms at 32 solves either way)
-    if (w.G <= 64 && w.npad >= 2048 && (w.npad % BB) == 0 && w.ident != nullptr) {
-        for (int b0 = w.npad - BB; b0 >= 0; b0 -= BB) {
-            hipLaunchKernelGGL(backsolve_kernel, dim3(w.G), dim3(512), shm, w.st, w.U, (long)LU_TW, w.strideH, w.n, w.npad,
-                               Wpop, ldw, d_slots, xout_dense, w.flags, b0, b0 + BB);
-            if (b0 > 0) maus_zgemm_launch_lu(w.st, b0, 1, BB, w.U, w.U, w.U, w.npad, w.strideH, b0, b0, w.npad, w.G, w.ident, 0);
+    const bool blocked = (w.npad > 8192) ? true : (w.G <= 64 && w.npad >= 2048 && (w.npad % BB) == 0);
+    if (blocked && w.ident != nullptr) {
+        for (int b1 = w.npad; b1 > 0; b1 -= BB) {
+            const int b0 = std::max(0, b1 - BB);
+            hipLaunchKernelGGL(backsolve_kernel, dim3(w.G), dim3(512), shm_for(b1 - b0), w.st, w.U, (long)LU_TW, w.strideH, w.n, w.npad,
+                               Wpop, ldw, d_slots, xout_dense, w.flags, b0, b1);
+            if (b0 > 0) maus_zgemm_launch_lu(w.st, b0, 1, b1 - b0, w.U, w.U, w.U, w.npad, w.strideH, b0, b0, w.npad, w.G, w.ident, 0);
         }
         hipLaunchKernelGGL(backsolve_out_kernel, dim3((w.n + 255) / 256, w.G), dim3(256), 0, w.st, w.U, (long)LU_TW, w.strideH, w.n, w.npad,
                            Wpop, ldw, d_slots, xout_dense, w.flags);
     } else
-    hipLaunchKernelGGL(backsolve_kernel, dim3(w.G), dim3(512), shm, w.st, w.U, (long)LU_TW, w.strideH, w.n, w.npad,
+    hipLaunchKernelGGL(backsolve_kernel, dim3(w.G), dim3(512), shm_for(w.npad), w.st, w.U, (long)LU_TW, w.strideH, w.n, w.npad,
                        Wpop, ldw, d_slots, xout_dense, w.flags, 0, w.npad);
     prof(w, KC_BACKSOLVE, 1, 4.0 * w.npad * w.npad * w.G, 8.0 * w.npad * w.npad * w.G);
 }

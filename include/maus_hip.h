@@ -74,6 +74,9 @@ const char* maus_last_error(const maus_ctx* ctx);
 int maus_device_info(maus_ctx* ctx, char* name, int name_len, int* cus, size_t* hbm_total, size_t* hbm_free);
 /* library ABI version (compile-time constant) */
 int maus_abi_version(void);
+/* largest n of the direct LU path (maus_shifted_lu_solve, maus_lu_solve_host, maus_lu_reserve) and of both GMRES modes
+ * (maus_gmres, maus_gmres_pert) in this build: 16384 */
+int maus_lu_max_n(void);
 
 /* ---- problem data (AMS:343, 346: everything is complex128) -------------- */
 /* Upload the rows x cols problem matrix.  Replaces passing `current_matrix_A`
