@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libmaus_hip.so")
 # every symbol include/maus_hip.h declares (tests/test_cabi_symbols.py checks the list against the header)
 SYMBOLS = [
     "maus_ctx_create", "maus_ctx_destroy", "maus_last_error", "maus_device_info", "maus_abi_version", "maus_lu_max_n",
-    "maus_set_matrix", "maus_set_rhs", "maus_pop_reserve", "maus_pop_capacity", "maus_pop_put", "maus_pop_get", "maus_pop_copy", "maus_pop_device_ptr", "maus_hist_append", "maus_hist_get", "maus_hist_clear", "maus_hist_generation",
+    "maus_set_matrix", "maus_set_matrix_csr", "maus_matrix_is_sparse", "maus_set_rhs", "maus_pop_reserve", "maus_pop_capacity", "maus_pop_put", "maus_pop_get", "maus_pop_copy", "maus_pop_device_ptr", "maus_hist_append", "maus_hist_get", "maus_hist_clear", "maus_hist_generation",
     "maus_matvec_rayleigh", "maus_shifted_lu_solve", "maus_lu_reserve", "maus_lu_workspace_allocs", "maus_set_shared_device", "maus_lu_mw_aborts", "maus_relax_normalise", "maus_residual",
     "maus_svd_power_step", "maus_svd_power_propose", "maus_svd_commit", "maus_set_eigvecs", "maus_herm_match", "maus_herm_tridiag", "maus_herm_release", "maus_herm_tridiag_eig", "maus_herm_tridiag_eigvals", "maus_herm_backtransform", "maus_get_eigvecs", "maus_gmres", "maus_gmres_pert", "maus_jacobi_check",
     "maus_profile_union_ms", "maus_gram", "maus_zgemm_host", "maus_lu_solve_host", "maus_timer_start", "maus_timer_stop",
@@ -31,7 +31,8 @@ POP_X, POP_U, POP_W, POP_Y = 0, 1, 2, 3
 KIND_EIG, KIND_LINEAR, KIND_SVD = 1, 2, 3
 PERT_NONE, PERT_UNIFORM, PERT_MT19937 = 0, 1, 2
 KC_NAMES = ["zgemm", "lu_panel", "trsm", "laswp", "build_h", "backsolve", "vector",
-            "zgemm_k128", "zgemm_k64", "zgemm_k32", "zgemm_k16"]
+            "zgemm_k128", "zgemm_k64", "zgemm_k32", "zgemm_k16", "spmm"]
+SPMM_SCHEDULES = {0: None, 1: "rows", 2: "wave"}     # maus_matrix_is_sparse: dense / lane per row / wave per row
 
 
 
@@ -68,6 +69,8 @@ def load_library():
         "maus_abi_version": ([], C.c_int),
         "maus_lu_max_n": ([], C.c_int),
         "maus_set_matrix": ([vp, vp, C.c_int, C.c_int], C.c_int),
+        "maus_set_matrix_csr": ([vp, C.c_int, C.c_int, C.c_int64, vp, vp, vp], C.c_int),
+        "maus_matrix_is_sparse": ([vp], C.c_int),
         "maus_set_rhs": ([vp, vp, C.c_int], C.c_int),
         "maus_pop_reserve": ([vp, C.c_int], C.c_int),
         "maus_pop_capacity": ([vp], C.c_int),
@@ -237,6 +240,31 @@ class Context:
         assert A.ndim == 2
         self.rows, self.cols = A.shape
         self._ck(self.lib.maus_set_matrix(self.h, _ptr(A), A.shape[0], A.shape[1]), "maus_set_matrix")
+
+    def set_matrix_csr(self, A):
+        """Upload a scipy.sparse matrix (any format) as complex CSR with sorted, summed indices (maus_set_matrix_csr);
+        the library keeps no dense copy.  Raw arrays go straight to set_matrix_csr_arrays."""
+        import scipy.sparse as sp
+        M = sp.csr_matrix(A, dtype=np.complex128, copy=True)
+        M.sum_duplicates()
+        M.sort_indices()
+        self.set_matrix_csr_arrays(M.shape[0], M.shape[1], M.indptr, M.indices, M.data)
+
+    def set_matrix_csr_arrays(self, rows, cols, indptr, indices, values):
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        values = _c128(values)
+        nnz = int(values.shape[0])
+        if indptr.shape != (int(rows) + 1,) or indices.shape != (nnz,):
+            raise MausHipError(f"maus_set_matrix_csr: array lengths (indptr {indptr.shape}, indices {indices.shape}, "
+                               f"values {values.shape}) do not fit rows = {rows}, nnz = {nnz}")
+        self._ck(self.lib.maus_set_matrix_csr(self.h, int(rows), int(cols), nnz, _ptr(indptr), _ptr(indices), _ptr(values)),
+                 "maus_set_matrix_csr")
+        self.rows, self.cols = int(rows), int(cols)
+
+    def matrix_is_sparse(self):
+        """None for a dense matrix, else the SpMM schedule chosen at bind time ('rows' or 'wave')."""
+        return SPMM_SCHEDULES[int(self.lib.maus_matrix_is_sparse(self.h))]
 
     def set_rhs(self, b):
         b = _c128(b)

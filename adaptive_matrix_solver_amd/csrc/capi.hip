@@ -207,7 +207,7 @@ void prof_tick(void* ud, int klass, int phase, double flops, double bytes) {
         // stands for `stride` launches (weight).  The short launches are left alone: with two sub-batch streams in
         // flight their event-to-event time is mostly the other stream's kernels (prof_stride_small > 0 samples
         // them anyway, for single-stream runs).
-        const bool is_gemm = (klass == KC_GEMM || klass >= KC_GEMM_K128);
+        const bool is_gemm = (klass == KC_GEMM || (klass >= KC_GEMM_K128 && klass <= KC_GEMM_K16));
         const int stride = (klass == KC_GEMM) ? c->prof_stride_big : c->prof_stride_small;
         c->prof_weight = (c->prof_mode == 2) ? (double)stride : 1.0;
         c->prof_skip = (c->prof_mode == 2) && (!is_gemm || stride <= 0 || (c->prof_cnt[klass]++ % stride) != 0);
@@ -263,6 +263,8 @@ int maus_ctx_destroy(maus_ctx* c) {
     void* ptrs[] = {c->A, c->b, c->V, c->X, c->U, c->W, c->Y, c->d_slots, c->d_i1, c->d_i2, c->d_c1, c->d_c2, c->d_r1, c->d_r2,
                     c->H, c->ipiv, c->perm, c->ident, c->mw_sync, c->info, c->flags, c->Upert, c->scratch, c->hq, c->htau, c->hz, c->S};
     for (void* p : ptrs) if (p) (void)hipFree(p);
+    maus_csr_free(c->Acsr); maus_csr_free(c->AHcsr);
+    if (c->Adiag) (void)hipFree(c->Adiag);
     if (c->pin) (void)hipHostFree(c->pin);
     if (c->pin_small) (void)hipHostFree(c->pin_small);
     for (auto e : c->pin_small_ev) if (e) (void)hipEventDestroy(e);
@@ -309,12 +311,20 @@ static void free_population(maus_ctx* c) {
 
 // room for a rows x cols problem matrix; everything that belonged to the previous one goes (also called by comm.hip for the
 // ranks that receive the matrix device to device)
+// drops the CSR operands of a sparse matrix (spmm.hip)
+static void csr_drop(maus_ctx* c) {
+    maus_csr_free(c->Acsr); maus_csr_free(c->AHcsr);
+    if (c->Adiag) { (void)hipFree(c->Adiag); c->Adiag = nullptr; }
+    c->csr = false; c->csr_sched = 0;
+}
+
 int maus_matrix_reserve(maus_ctx* c, int rows, int cols) {
     av_drop_all(c);
     if (rows <= 0 || cols <= 0) FAIL(c, "maus_set_matrix: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->st));
-    if (rows != c->rows || cols != c->cols) {
+    csr_drop(c);
+    if (rows != c->rows || cols != c->cols || !c->A) {
         if (c->A) { (void)hipFree(c->A); c->A = nullptr; }
         if (std::max(rows, cols) != c->ldp) { free_population(c); hist_free(c); }      // vector length changed
         if (c->V) { (void)hipFree(c->V); c->V = nullptr; c->vn = 0; }
@@ -322,6 +332,23 @@ int maus_matrix_reserve(maus_ctx* c, int rows, int cols) {
         c->rows = rows; c->cols = cols;
     }
     if (c->hq) { (void)hipFree(c->hq); c->hq = nullptr; } if (c->htau) { (void)hipFree(c->htau); c->htau = nullptr; } c->hqn = 0;   // reflectors of the previous matrix
+    if (c->hz) { (void)hipFree(c->hz); c->hz = nullptr; c->hzn = 0; }
+    return 0;
+}
+
+// maus_matrix_reserve for a matrix held in CSR (maus_set_matrix_csr): the same drops, and the dense copy is released
+int maus_matrix_reserve_csr(maus_ctx* c, int rows, int cols) {
+    av_drop_all(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    csr_drop(c);
+    if (c->A) { (void)hipFree(c->A); c->A = nullptr; }
+    if (rows != c->rows || cols != c->cols) {
+        if (std::max(rows, cols) != c->ldp) { free_population(c); hist_free(c); }
+        if (c->V) { (void)hipFree(c->V); c->V = nullptr; c->vn = 0; }
+        c->rows = rows; c->cols = cols;
+    }
+    if (c->hq) { (void)hipFree(c->hq); c->hq = nullptr; } if (c->htau) { (void)hipFree(c->htau); c->htau = nullptr; } c->hqn = 0;
     if (c->hz) { (void)hipFree(c->hz); c->hz = nullptr; c->hzn = 0; }
     return 0;
 }
@@ -593,6 +620,11 @@ int maus_hist_get(maus_ctx* c, const int64_t* indices, int count, int len, doubl
 
 // Y[slot] = A @ X[slot] for all listed slots:  C[count, rows] = Xg[count, cols] * A^T  (A as [n][k])
 static void matvec_into_Y(maus_ctx* c, const c128* src, int count) {
+    if (c->csr) {                                        // sparse matrix: the CSR product, same rows in and out (spmm.hip)
+        ProfScope ps(c, KC_SPMM, 8.0 * count * c->Acsr.nnz, 12.0 * c->Acsr.nnz * ((count + 7) / 8) + 32.0 * count * c->rows);
+        maus_spmm_launch(c->st, c->Acsr, c->csr_sched, src, c->ldp, c->Y, c->ldp, c->d_slots, c->d_slots, count);
+        return;
+    }
     ProfScope ps(c, KC_GEMM, 8.0 * count * c->rows * c->cols, 16.0 * ((double)c->rows * c->cols + 2.0 * count * c->ldp));
     maus_zgemm_launch_idx(c->st, count, c->rows, c->cols, src, c->ldp, 0, c->A, c->cols, 0, c->Y, c->ldp, 0,
                           1.0, 0, 1, /*blay*/1, false, false, c->d_slots, c->d_slots);
@@ -615,7 +647,7 @@ static int matvec_missing_into_Y(maus_ctx* c, const int* slots, int count) {
 }
 
 int maus_matvec_rayleigh(maus_ctx* c, const int* slots, int count, double* num, double* den) {
-    if (!c->A || !c->X) FAIL(c, "maus_matvec_rayleigh: matrix/population missing");
+    if (!maus_has_matrix(c) || !c->X) FAIL(c, "maus_matvec_rayleigh: matrix/population missing");
     if (c->rows != c->cols) FAIL(c, "maus_matvec_rayleigh: square matrix required");
     if (count == 0) return 0;
     if (upload_slots(c, slots, count)) return -1;
@@ -850,7 +882,8 @@ static int mt_prepare_and_build(maus_ctx* c, const LuWs& w, const maus_mt_desc* 
 int maus_shifted_lu_solve(maus_ctx* c, const int* slots, int count, const double* shift, const double* psi,
                           int rhs_mode, int pert_mode, const void* pert_data, int32_t* status) {
     av_drop_all(c);
-    if (!c->A || !c->X) FAIL(c, "maus_shifted_lu_solve: matrix/population missing");
+    if (!maus_has_matrix(c) || !c->X) FAIL(c, "maus_shifted_lu_solve: matrix/population missing");
+    if (c->csr && pert_mode != MAUS_PERT_NONE) FAIL(c, "maus_shifted_lu_solve: a sparse matrix has no random term (pert_mode must be NONE)");
     if (c->rows != c->cols) FAIL(c, "maus_shifted_lu_solve: square matrix required");
     if (rhs_mode == 1 && (!c->b || c->bn != c->rows)) FAIL(c, "maus_shifted_lu_solve: rhs b not set");
     if ((pert_mode == MAUS_PERT_UNIFORM || pert_mode == MAUS_PERT_MT19937) && !pert_data) FAIL(c, "pert_data missing");
@@ -906,7 +939,9 @@ int maus_shifted_lu_solve(maus_ctx* c, const int* slots, int count, const double
             c->prof_st = st;
             if (pert_mode == MAUS_PERT_MT19937) {
                 if (mt_prepare_and_build(c, w, (const maus_mt_desc*)pert_data, off + lo, g, rhs_mode, lo, sb, 1)) return -1;
-            } else
+            } else if (c->csr)
+            maus_build_h_csr(w, c->Acsr, c->d_c1 + lo, c->d_r1 + lo, rhs_mode, c->X, c->ldp, c->d_slots + lo, c->b, 1);
+            else
             maus_build_h(w, c->A, c->d_c1 + lo, c->d_r1 + lo, rhs_mode, c->X, c->ldp, c->d_slots + lo, c->b, pert_mode,
                          dU ? dU + 2 * (size_t)n * n * lo : nullptr, 1);
             wss.push_back(w); los.push_back(lo);
@@ -1013,7 +1048,7 @@ int maus_residual(maus_ctx* c, int kind, const int* slots, int count, const doub
     bool have_ahu = (kind == MAUS_SVD) && av_family(c, count, c->rows);
     for (int k = 0; have_ahu && k < count; ++k) have_ahu = slots[k] >= 0 && ahu_has(c, slots[k]);
     av_drop_all(c);
-    if (!c->A || !c->X) FAIL(c, "maus_residual: matrix/population missing");
+    if (!maus_has_matrix(c) || !c->X) FAIL(c, "maus_residual: matrix/population missing");
     if (count == 0) return 0;
     if (upload_slots(c, slots, count)) return -1;
     if (kind == MAUS_EIG || kind == MAUS_LINEAR) {
@@ -1033,7 +1068,10 @@ int maus_residual(maus_ctx* c, int kind, const int* slots, int count, const doub
         maus_launch_svd_resid(c->st, c->Y, c->U, c->ldp, c->d_slots, count, c->rows, c->d_c1, c->d_r1, 0, c->d_i1);
         // ||A^H u - s v||: W = U * conj(A)  (count x cols), B = conj(A) as [k=rows][n=cols] -- or, when the power step of this
         // loop body has left exactly that product in S (same u, same kernel, same bits), no product at all (round 4)
-        if (!have_ahu) {
+        if (!have_ahu && c->csr) {
+            ProfScope ps(c, KC_SPMM, 8.0 * count * c->AHcsr.nnz, 12.0 * c->AHcsr.nnz * ((count + 7) / 8) + 32.0 * count * c->cols);
+            maus_spmm_launch(c->st, c->AHcsr, c->csr_sched, c->U, c->ldp, c->W, c->ldp, c->d_slots, c->d_slots, count);
+        } else if (!have_ahu) {
             ProfScope ps(c, KC_GEMM, 8.0 * count * c->rows * c->cols, 16.0 * (double)c->rows * c->cols);
             maus_zgemm_launch_idx(c->st, count, c->cols, c->rows, c->U, c->ldp, 0, c->A, c->cols, 0, c->W, c->ldp, 0,
                                   1.0, 0, 1, 0, false, true, c->d_slots, c->d_slots);
@@ -1053,7 +1091,7 @@ int maus_residual(maus_ctx* c, int kind, const int* slots, int count, const doub
 // the engine kept a host copy of every candidate's vectors for that, 400 MB over PCIe per loop body at BASELINE
 // configs[4] (6144 candidates x 2048), 57 % of its wall time.
 int maus_svd_power_propose(maus_ctx* c, const int* slots, int count, double* norms_out) {
-    if (!c->A || !c->X) FAIL(c, "maus_svd_power_propose: matrix/population missing");
+    if (!maus_has_matrix(c) || !c->X) FAIL(c, "maus_svd_power_propose: matrix/population missing");
     if (count == 0) return 0;
     if (upload_slots(c, slots, count)) return -1;
     // ||v_in||
@@ -1073,6 +1111,10 @@ int maus_svd_power_propose(maus_ctx* c, const int* slots, int count, double* nor
         HIPCHK(c, hipMalloc((void**)&c->S, sizeof(c128) * (size_t)c->cap * c->ldp));
         c->Scap = c->cap;
     }
+    if (c->csr) {
+        ProfScope ps(c, KC_SPMM, 8.0 * count * c->AHcsr.nnz, 12.0 * c->AHcsr.nnz * ((count + 7) / 8) + 32.0 * count * c->cols);
+        maus_spmm_launch(c->st, c->AHcsr, c->csr_sched, c->Y, c->ldp, c->S, c->ldp, c->d_slots, c->d_slots, count);
+    } else
     { ProfScope ps(c, KC_GEMM, 8.0 * count * c->rows * c->cols, 16.0 * (double)c->rows * c->cols);
       maus_zgemm_launch_idx(c->st, count, c->cols, c->rows, c->Y, c->ldp, 0, c->A, c->cols, 0, c->S, c->ldp, 0,
                             1.0, 0, 1, 0, false, true, c->d_slots, c->d_slots); }
@@ -1154,7 +1196,7 @@ int maus_gmres_pert(maus_ctx* c, const int* slots, int count, const double* shif
                     const int32_t* want_jacobi, int pert_mode, const void* pert_data, double rtol, int restart, int maxiter,
                     int32_t* info_out, int32_t* inner_out, int32_t* status, int32_t* jacobi_out) {
     av_drop_all(c);
-    if (!c->A || !c->X) FAIL(c, "maus_gmres_pert: matrix/population missing");
+    if (!c->A || !c->X) FAIL(c, c->csr ? "maus_gmres_pert: a sparse matrix has no random term (use maus_gmres)" : "maus_gmres_pert: matrix/population missing");
     if (c->rows != c->cols) FAIL(c, "maus_gmres_pert: square matrix required");
     if (rhs_mode == 1 && (!c->b || c->bn != c->rows)) FAIL(c, "maus_gmres_pert: rhs b not set");
     if ((pert_mode == MAUS_PERT_UNIFORM || pert_mode == MAUS_PERT_MT19937) && !pert_data) FAIL(c, "pert_data missing");

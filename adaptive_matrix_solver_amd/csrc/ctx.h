@@ -40,6 +40,13 @@ void maus_launch_svd_resid(hipStream_t st, const c128* Yv, const c128* Uv, long 
 void maus_launch_norm_scale(hipStream_t st, const c128* S, c128* D, long ld, const int* slots, int count, int n, double* norm_out, int stride_out, int off_out);
 void maus_launch_norm(hipStream_t st, const c128* S, long ld, const int* slots, int count, int n, double* norm_out, int stride_out, int off_out);
 void maus_launch_herm_pick(hipStream_t st, const c128* S, long lds_, c128* X, long ldx, const int* slots, int count, const c128* V, int n, int* idx_out, double* norm_out);
+enum { MAUS_SPMM_ROWS = 1, MAUS_SPMM_WAVE = 2 };     // SpMM schedules: a lane per row / a wave per row
+void maus_spmm_launch(hipStream_t st, const MausCsr& m, int sched, const c128* B, long ldb, c128* C, long ldc,
+                      const int* a_rows, const int* c_rows, int count);
+void maus_csr_diag_launch(hipStream_t st, const MausCsr& m, int n, c128* d);
+void maus_csr_free(MausCsr& m);
+void maus_build_h_csr(const LuWs& w, const MausCsr& A, const c128* d_shift, const double* d_psi, int rhs_mode,
+                      const c128* X, long ldx, const int* d_slots, const c128* bvec, int tiled);
 int maus_gmres_run(maus_ctx* ctx, const int* slots, int count, const double* shift, const double* psi, int rhs_mode,
                    const int32_t* use_jacobi, double rtol, int restart, int maxiter, int32_t* info_out, int32_t* inner_out, int32_t* status,
                    const c128* Hdense, long ldh, long strideH, int32_t* jacobi_out);
@@ -53,6 +60,8 @@ struct maus_ctx {
     hipStream_t st = nullptr;
     std::string err;
     c128* A = nullptr; int rows = 0, cols = 0;      // problem matrix
+    // sparse problem matrix (maus_set_matrix_csr): A and A^H in CSR, the diagonal of A, the SpMM schedule; A stays null
+    bool csr = false; MausCsr Acsr, AHcsr; c128* Adiag = nullptr; int csr_sched = 0;
     c128* b = nullptr; int bn = 0;                  // rhs
     c128* V = nullptr; int vn = 0;                  // eigenvectors (Hermitian shortcut)
     c128* hq = nullptr; c128* htau = nullptr; int hqn = 0;   // Householder reflectors of maus_herm_tridiag, until the back-transformation (herm.hip)
@@ -134,6 +143,8 @@ extern thread_local std::string g_err;
 
 
 int maus_matrix_reserve(maus_ctx* c, int rows, int cols);     // capi.hip: device room for the problem matrix
+int maus_matrix_reserve_csr(maus_ctx* c, int rows, int cols); // capi.hip: the same for a CSR matrix (no dense copy)
+inline bool maus_has_matrix(const maus_ctx* c) { return c->A || c->csr; }
 int ensure_scalars(maus_ctx* c, int count);
 int ensure_scratch(maus_ctx* c, size_t bytes);
 int check_slots(maus_ctx* c, const int* slots, int count);

@@ -471,13 +471,14 @@ gmres_finish_kernel(GArgs a, c128* __restrict__ W, long ldw, int* __restrict__ i
 }  // namespace
 
 int maus_jacobi_check_run(maus_ctx* c, int count, const double* shift, const double* psi, int32_t* ok) {
-    if (!c->A || c->rows != c->cols) FAIL(c, "maus_jacobi_check: square matrix required");
+    if (!maus_has_matrix(c) || c->rows != c->cols) FAIL(c, "maus_jacobi_check: square matrix required");
     if (count <= 0) return 0;
     const int n = c->rows;
     if (ensure_scalars(c, count)) return -1;
     if (ensure_scratch(c, sizeof(c128) * n)) return -1;
     c128* dA = (c128*)c->scratch;
-    hipLaunchKernelGGL(diag_kernel, dim3((n + 255) / 256), dim3(256), 0, c->st, c->A, n, dA);
+    if (c->csr) HIPCHK(c, hipMemcpyAsync(dA, c->Adiag, sizeof(c128) * n, hipMemcpyDeviceToDevice, c->st));
+    else hipLaunchKernelGGL(diag_kernel, dim3((n + 255) / 256), dim3(256), 0, c->st, c->A, n, dA);
     if (maus_h2d(c, c->d_c1, shift, sizeof(c128) * count, c->st)) return -1;
     if (maus_h2d(c, c->d_r1, psi, sizeof(double) * count, c->st)) return -1;
     hipLaunchKernelGGL(jacobi_check_kernel, dim3(count), dim3(GT), 0, c->st, dA, n, c->d_c1, c->d_r1, c->d_i1);
@@ -489,7 +490,8 @@ int maus_jacobi_check_run(maus_ctx* c, int count, const double* shift, const dou
 int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift, const double* psi, int rhs_mode,
                    const int32_t* use_jacobi, double rtol, int restart, int maxiter, int32_t* info_out, int32_t* inner_out,
                    int32_t* status, const c128* Hdense, long ldh, long strideH, int32_t* jacobi_out) {
-    if (!c->A || !c->X) FAIL(c, "maus_gmres: matrix/population missing");
+    if (!maus_has_matrix(c) || !c->X) FAIL(c, "maus_gmres: matrix/population missing");
+    if (c->csr && Hdense) FAIL(c, "maus_gmres: a sparse matrix has no random term (no materialised H)");
     if (c->rows != c->cols) FAIL(c, "maus_gmres: square matrix required");
     if (rhs_mode == 1 && (!c->b || c->bn != c->rows)) FAIL(c, "maus_gmres: rhs b not set");
     if (count <= 0) return 0;
@@ -517,7 +519,8 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
     if (maus_h2d(c, c->d_c1, shift, sizeof(c128) * count, c->st)) return -1;
     if (maus_h2d(c, c->d_r1, psi, sizeof(double) * count, c->st)) return -1;
     if (maus_h2d(c, jac, use_jacobi, sizeof(int) * count, c->st)) return -1;
-    hipLaunchKernelGGL(diag_kernel, dim3((n + 255) / 256), dim3(256), 0, c->st, c->A, n, (c128*)(base + o_d));
+    if (c->csr) HIPCHK(c, hipMemcpyAsync(base + o_d, c->Adiag, sizeof(c128) * n, hipMemcpyDeviceToDevice, c->st));
+    else hipLaunchKernelGGL(diag_kernel, dim3((n + 255) / 256), dim3(256), 0, c->st, c->A, n, (c128*)(base + o_d));
     if (Hdense) hipLaunchKernelGGL(jacobi_gate_dense_kernel, dim3(count), dim3(GT), 0, c->st, a, jac);
     hipLaunchKernelGGL(gmres_init_kernel, dim3(count), dim3(GT), 0, c->st, a);
     const long max_ticks = (long)maxiter * (R + 1) + 2;
@@ -527,6 +530,12 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
         if (maus_d2h(c, &h_nact, nact, sizeof(int), c->st)) return -1;
         HIPCHK(c, hipStreamSynchronize(c->st));
         if (h_nact <= 0) break;
+        if (c->csr) {
+            // sparse matrix: every active candidate's product through the CSR operand (rows do not depend on the batch, so the
+            // shared first product A x0 of rhs_mode 1 needs no special case)
+            ProfScope ps(c, KC_SPMM, 8.0 * h_nact * c->Acsr.nnz, 12.0 * c->Acsr.nnz * ((h_nact + 7) / 8) + 32.0 * h_nact * n);
+            maus_spmm_launch(c->st, c->Acsr, c->csr_sched, a.Vb, n, a.Y, n, zrow, act, h_nact);
+        } else
         if (Hdense) {
             ProfScope ps(c, KC_VEC, 0, 16.0 * h_nact * (double)n * n);
             hipLaunchKernelGGL(gemv_dense_kernel, dim3((n + 15) / 16, h_nact), dim3(GT), 0, c->st, a, act, zrow);

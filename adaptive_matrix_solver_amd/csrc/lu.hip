@@ -109,6 +109,51 @@ build_h_kernel(const c128* __restrict__ A, int n, int npad, long ldh, long strid
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&flags[g], 1);
 }
 
+// H build from a CSR matrix (sparse problems): H_k = A - lam_k I + psi_k I with no random term (AMS:46-47).
+// grid = (npad, G), block = 256: the block of row i first writes the row's zeros (identity rows below n), then, after a
+// barrier, its stored entries; the diagonal is (a - lam) + psi as in build_h_kernel, with a = 0 where A stores none.
+// Same augmented block and flags as build_h_kernel.
+__global__ void __launch_bounds__(256)
+build_h_csr_kernel(const int* __restrict__ Ap, const int* __restrict__ Ai, const c128* __restrict__ Av,
+                   int n, int npad, long ldh, long strideH, c128* __restrict__ Hg,
+                   const c128* __restrict__ shift, const double* __restrict__ psi,
+                   int rhs_mode, const c128* __restrict__ X, long ldx, const int* __restrict__ slots,
+                   const c128* __restrict__ bvec, int* __restrict__ flags, int tiled)
+{
+    const int i = blockIdx.x, g = blockIdx.y;
+    c128* Hmat = Hg + (long)g * strideH;
+    auto at = [&](int j) -> c128& { return Hmat[tiled ? lu_tix(npad, i, j) : (long)i * ldh + j]; };
+    const c128 lam = shift[g];
+    const double ps = psi[g];
+    auto diag = [&](c128 a) { return cmake(__dadd_rn(__dsub_rn(a.x, lam.x), ps), __dadd_rn(__dsub_rn(a.y, lam.y), 0.0)); };
+    bool bad = false;
+    if (i < n) {
+        for (int j = threadIdx.x; j < npad; j += blockDim.x) {
+            const c128 h = (j == i) ? diag(cmake(0.0, 0.0)) : cmake(0.0, 0.0);
+            bad |= !cfinite(h);
+            at(j) = h;
+        }
+        __syncthreads();
+        for (int p = Ap[i] + threadIdx.x; p < Ap[i + 1]; p += blockDim.x) {
+            const int j = Ai[p];
+            const c128 h = (j == i) ? diag(Av[p]) : Av[p];
+            bad |= !cfinite(h);
+            at(j) = h;
+        }
+    } else {
+        for (int j = threadIdx.x; j < npad; j += blockDim.x) at(j) = cmake(j == i ? 1.0 : 0.0, 0.0);
+    }
+    for (int j = threadIdx.x; j < AUG; j += blockDim.x) {
+        c128 v = cmake(0.0, 0.0);
+        if (j == 0 && i < n) {
+            v = (rhs_mode == 0) ? X[(long)slots[g] * ldx + i] : bvec[i];
+            bad |= !cfinite(v);
+        }
+        at(npad + j) = v;
+    }
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&flags[g], 1);
+}
+
 // host-provided dense matrices (maus_lu_solve_host): H <- [A_g | b_g], padded
 __global__ void __launch_bounds__(256)
 load_h_kernel(const c128* __restrict__ Ain /*[G][n][n]*/, const c128* __restrict__ bin /*[G][n]*/, int n, int npad,
@@ -1255,6 +1300,14 @@ void maus_build_h(const LuWs& w, const c128* A, const c128* d_shift, const doubl
     hipLaunchKernelGGL(build_h_kernel, dim3(w.npad, w.G), dim3(256), 0, w.st, A, w.n, w.npad, w.ldh, w.strideH, w.H,
                        d_shift, d_psi, rhs_mode, X, ldx, d_slots, bvec, pert_mode, d_U, w.flags, tiled);
     prof(w, KC_BUILD, 1, 0, 32.0 * w.npad * w.ldh * w.G);
+}
+
+void maus_build_h_csr(const LuWs& w, const MausCsr& A, const c128* d_shift, const double* d_psi, int rhs_mode,
+                      const c128* X, long ldx, const int* d_slots, const c128* bvec, int tiled) {
+    prof(w, KC_BUILD, 0);
+    hipLaunchKernelGGL(build_h_csr_kernel, dim3(w.npad, w.G), dim3(256), 0, w.st, A.ptr, A.idx, A.val, w.n, w.npad, w.ldh, w.strideH, w.H,
+                       d_shift, d_psi, rhs_mode, X, ldx, d_slots, bvec, w.flags, tiled);
+    prof(w, KC_BUILD, 1, 0, 16.0 * w.npad * w.ldh * w.G);
 }
 
 void maus_load_h(const LuWs& w, const c128* d_Ain, const c128* d_bin) {

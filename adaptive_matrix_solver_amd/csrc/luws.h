@@ -36,3 +36,6 @@ struct LuWs {
     hipStream_t st;
     void (*tick)(void* ud, int klass, int phase, double flops, double bytes); void* ud;
 };
+
+// CSR operand of a sparse problem matrix (spmm.hip, maus_build_h_csr): 32-bit row pointers and column indices, complex values
+struct MausCsr { int* ptr = nullptr; int* idx = nullptr; c128* val = nullptr; long nnz = 0; int rows = 0; };

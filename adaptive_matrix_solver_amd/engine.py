@@ -237,19 +237,33 @@ def tridiagonal_eigenvalues(ctx, d, e):
     return np.sort(sla.eigvalsh_tridiagonal(d, e))
 
 
+def _is_sparse_matrix(A) -> bool:
+    try:
+        import scipy.sparse as sp
+        return sp.issparse(A)
+    except Exception:
+        return False
+
+
 class DeviceEngine:
     """One GPU context + slot allocator + the batched step."""
 
     _default = None
 
     def __init__(self, device: int = 0, pert_mode: str = "auto", gmres_compat: str = "rtol",
-                 comm=None, ctx=None, eigh_mode: str = "auto"):
+                 comm=None, ctx=None, eigh_mode: str = "auto", sparse_mode=None):
         self.ctx = ctx if ctx is not None else _cabi.Context(device)
         cap_blas_threads()
         # Hermitian eigendecomposition (AMS:161), once per matrix: 'host' = scipy.linalg.eigh, the reference's call, (lambda, V)
         # bit-identical to its; 'device' = reduction and back-transformation on the GPU, the tridiagonal eigenproblem by LAPACK
         # dstemr on the host (csrc/herm.hip); 'auto' = device from n = EIGH_DEVICE_MIN up.  MAUS_EIGH overrides.
         self.eigh_mode = os.environ.get("MAUS_EIGH", eigh_mode)
+        # scipy.sparse problem matrices (DESIGN §10): 'reject' raises NotImplementedError as before; 'device' keeps the matrix
+        # in CSR on the device (no dense copy) and runs the reference's sparse branch.  MAUS_SPARSE sets the default.
+        self.sparse_mode = sparse_mode if sparse_mode is not None else os.environ.get("MAUS_SPARSE", "reject")
+        if self.sparse_mode not in ("reject", "device"):
+            raise ValueError(f"sparse_mode must be 'reject' or 'device', not {self.sparse_mode!r}")
+        self._sparse = False                    # the bound matrix is sparse (CSR on the device)
         self._owner = {}                        # id(candidate) -> rank that executes it this step
         self.pert_mode = pert_mode              # 'auto' | 'uniform' | 'mt19937' | 'none'
         self.gmres_compat = gmres_compat        # 'rtol' | 'scipy-legacy'  (SURVEY F2)
@@ -288,6 +302,21 @@ class DeviceEngine:
         if A is self._bound and not (collective and solo):
             return
         shape_changed = (self.ctx.rows, self.ctx.cols) != tuple(A.shape)
+        if _is_sparse_matrix(A):
+            if self.sparse_mode != "device":
+                raise NotImplementedError("sparse problem matrices need sparse_mode='device' (or MAUS_SPARSE=device)")
+            if comm is not None and comm.world > 1:
+                raise NotImplementedError("sharded runs (comm.world > 1) with a sparse matrix are not supported")
+            self.ctx.set_matrix_csr(A)
+            self._sparse = True
+            self._bound = A
+            if shape_changed:
+                self._free = []
+                self._next_slot = 0
+                self._bound_b = None
+                self.store = CandidateStore()
+            return
+        self._sparse = False
         if collective:
             self.ctx.comm_set_matrix(A, comm.rank, 0, resident_on_root=(comm.rank == 0 and solo and A is self._bound))
             comm.collectives += 1
@@ -448,6 +477,8 @@ class DeviceEngine:
 
     # ---- perturbation mode ---------------------------------------------------------------
     def _pert(self, n: int) -> int:
+        if self._sparse:                        # AMS:46-47: the sparse branch adds psi*I and draws nothing
+            return PERT_NONE
         if self.pert_mode == "uniform":
             return PERT_UNIFORM
         if self.pert_mode == "none":
@@ -457,6 +488,11 @@ class DeviceEngine:
         # auto: small problems upload the exact host draws; large ones regenerate the same draws on the
         # device from the NumPy state (bit-identical H either way)
         return PERT_UNIFORM if n <= 256 else PERT_MT19937
+
+    def _words(self, n: int) -> int:
+        """MT19937 words one solve attempt draws: 2 x rand(N, N) complex parts (AMS:49) for a dense matrix, none for a sparse
+        one (AMS:46-47)."""
+        return 0 if self._sparse else 4 * n * n
 
     # ======================================================================================
     # device phases, sharded over ranks when a communicator is present (dist.py)
@@ -750,11 +786,42 @@ class DeviceEngine:
         comm.bcast_eigvecs(self.ctx, evecs, n)
         self._eig_cache = (A, ev)
 
+    def _sparse_eigh_k(self, A):
+        """The sparse Hermitian shortcut's decomposition (AMS:186-216), once per matrix: eigsh(A, k=min(6, N-1), which='LM')
+        per candidate becomes the k eigenpairs of largest |lambda| of one dense eigh.  Columns kept in ascending order of
+        lambda, zero-padded to n x n on the device, so that the candidate's pick -- argmax |v^H V[:, j]| -- can only land on
+        one of the k.  Returns (eigenvalues, None) or (None, the TypeError text SciPy raises where ARPACK cannot run:
+        k >= N - 1 for complex input (eigs), k >= N for real input)."""
+        import scipy.linalg as sla
+        n = A.shape[0]
+        k = min(6, n - 1)
+        if k < 1 and n >= 1:
+            k = 1
+        if np.issubdtype(A.dtype, np.complexfloating) and k >= n - 1:
+            return None, ("Cannot use scipy.linalg.eig for sparse A with k >= N - 1. "
+                          "Use scipy.linalg.eig(A.toarray()) or reduce k.")
+        if k >= n:
+            return None, "Cannot use scipy.linalg.eigh for sparse A with k >= N. Use scipy.linalg.eigh(A.toarray()) or reduce k."
+        evals, evecs = sla.eigh(A.toarray())
+        keep = np.sort(np.argsort(np.abs(evals), kind="stable")[-k:])
+        V = np.zeros((n, n), dtype=np.complex128)
+        V[:, :k] = evecs[:, keep]
+        self.ctx.set_eigvecs(V)
+        return np.ascontiguousarray(evals[keep], dtype=np.float64), None
+
     def _hermitian(self, cands, A, slots):
         from .solver import SolutionCandidate
         S = SolutionCandidate.State
-        if self._eig_cache is not None and self._eig_cache[0] is not A and self._eig_cache[0].shape == A.shape \
-                and np.array_equal(self._eig_cache[0], A):
+        if self._sparse:
+            if self._eig_cache is None or self._eig_cache[0] is not A:
+                evals, err = self._sparse_eigh_k(A)
+                self._eig_cache = (A, evals, err)
+            if self._eig_cache[1] is None:
+                for c in cands:
+                    print(f"Candidate {c.id}: Unexpected error during sparse Hermitian solve: {self._eig_cache[2]}. Falling back.")
+                return cands
+        elif self._eig_cache is not None and self._eig_cache[0] is not A and self._eig_cache[0].shape == A.shape \
+                and not _is_sparse_matrix(self._eig_cache[0]) and np.array_equal(self._eig_cache[0], A):
             self._eig_cache = (A, self._eig_cache[1])     # another solver on the same engine with an equal matrix: V is still resident
         if self._eig_cache is None or self._eig_cache[0] is not A:
             evals, err = self._eigh_once(A)
@@ -877,7 +944,7 @@ class DeviceEngine:
         pref = know.get("local_solver_preference", DIRECT)
         base_psi = PSI_EPSILON_BASE * aggr                              # AMS:224
         pert = self._pert(n)
-        words = 4 * n * n                                               # MT19937 words per dense attempt
+        words = self._words(n)                                          # MT19937 words per attempt
         # LU workspace sized once for this rank's share of the population plus the growth of the next ~20 iterations
         # (<= 15 spawns each whatever the population, AMS:533-534): it must not be re-allocated inside somebody's timed
         # step (freeing and mapping ~100 GB takes seconds; HBM is otherwise idle)
@@ -1144,7 +1211,7 @@ class DeviceEngine:
         else:
             if pert == PERT_MT19937:
                 pert_data = (np.random.get_state(), 4 * n * n, 0, np.zeros(1, dtype=np.int32))
-            _advance_numpy_stream(4 * n * n)
+            _advance_numpy_stream(self._words(n))
         sh = np.array([shift], dtype=np.complex128)
         ps = np.array([psi.real if hasattr(psi, "real") else psi], dtype=np.float64)
         if method == DIRECT:

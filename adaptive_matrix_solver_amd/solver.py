@@ -14,7 +14,11 @@ Documented deviations:
   F2  `gmres_compat='rtol'` (default) honours the evident intent of `tol=1e-8`;
       `'scipy-legacy'` reproduces SciPy>=1.14 behaviour (TypeError swallowed -> LU).
   F5  the Hermitian eigendecomposition is computed once per matrix, not once per candidate.
-  Sparse inputs are out of scope (dense BASELINE configs only) and raise NotImplementedError.
+Sparse problems -- scipy.sparse input, or an ndarray under 25 % nonzeros, which the reference converts to CSC (AMS:357-358)
+-- raise NotImplementedError by default (`sparse_mode="reject"`).  `sparse_mode="device"` (or MAUS_SPARSE=device) runs the
+reference's sparse branch with the matrix in CSR on the device: no random perturbation and no NumPy draws in the
+solve (AMS:46-47), every product with A a CSR SpMM, and the sparse Hermitian shortcut's eigsh (AMS:186-216) replaced by the k
+eigenpairs of largest |lambda| of one eigh per matrix.
 """
 from __future__ import annotations
 
@@ -87,6 +91,32 @@ def _is_sparse(M) -> bool:
         return False
 
 
+SPARSE_MODES = ("reject", "device")
+
+
+def _sparse_mode(mode):
+    """The `sparse_mode` keyword: an explicit value, else MAUS_SPARSE, else 'reject'."""
+    import os
+    mode = mode if mode is not None else os.environ.get("MAUS_SPARSE", "reject")
+    if mode not in SPARSE_MODES:
+        raise ValueError(f"sparse_mode must be one of {SPARSE_MODES}, not {mode!r}")
+    return mode
+
+
+def _reject_sparse(what):
+    raise NotImplementedError(f"{what} take the reference's sparse path, which runs only with sparse_mode='device' "
+                              f"(or MAUS_SPARSE=device); the default sparse_mode='reject' refuses it")
+
+
+def _as_spmatrix(M):
+    """A scipy.sparse array (sp.sparray) becomes the spmatrix of the same format (the reference only knows spmatrix,
+    AMS:343 / 380: a documented deviation); an spmatrix is returned as it is."""
+    import scipy.sparse as sp
+    if isinstance(M, sp.spmatrix):
+        return M
+    return getattr(sp, f"{M.format}_matrix")(M)
+
+
 # ==========================================================================================
 # InverseIterateSolver (AMS:30-104)
 # ==========================================================================================
@@ -96,7 +126,7 @@ class InverseIterateSolver:
     _engine = None          # private context: every call uploads its own A_target
 
     def __init__(self, N, base_psi_epsilon, max_attempts, preferred_method="direct_solve", is_sparse=False,
-                 gmres_compat="rtol", pert_mode="uniform"):
+                 gmres_compat="rtol", pert_mode="uniform", sparse_mode=None):
         self.N = N
         self.base_psi_epsilon = base_psi_epsilon
         self.max_attempts = max_attempts
@@ -105,6 +135,7 @@ class InverseIterateSolver:
         self.is_sparse = is_sparse
         self.gmres_compat = gmres_compat
         self.pert_mode = pert_mode
+        self.sparse_mode = _sparse_mode(sparse_mode)
         self.last_trace = []
 
     @classmethod
@@ -114,12 +145,19 @@ class InverseIterateSolver:
         return cls._engine
 
     def solve(self, A_target, b_rhs, candidate_stuck_counter):
-        if self.is_sparse or _is_sparse(A_target):
-            raise NotImplementedError("sparse problems are outside the MI355X hot path (dense only)")
+        sparse = self.is_sparse or _is_sparse(A_target)
+        if sparse and self.sparse_mode != "device":
+            _reject_sparse("sparse matrices")
         ctx = self._ctx()
         n = self.N
-        A_target = np.ascontiguousarray(A_target, dtype=np.complex128)
-        ctx.set_matrix(A_target)
+        if sparse:
+            # AMS:46-47, 55-56: H = A_target + psi*I, no random term; the direct solve densifies H on the device (spsolve's
+            # NaNs on a singular H land in the same ValueError -> retry branch as the LU's info > 0)
+            import scipy.sparse as sp
+            ctx.set_matrix_csr(A_target if _is_sparse(A_target) else sp.csr_matrix(A_target))
+        else:
+            A_target = np.ascontiguousarray(A_target, dtype=np.complex128)
+            ctx.set_matrix(A_target)
         ctx.set_rhs(np.ascontiguousarray(b_rhs, dtype=np.complex128))
         ctx.pop_reserve(1)
         ctx.pop_put(POP_X, [0], np.ascontiguousarray(b_rhs, dtype=np.complex128))     # x0 = b (AMS:61)
@@ -132,7 +170,9 @@ class InverseIterateSolver:
             psi = self.base_psi_epsilon * (10 ** (num_psi_attempts / 2.0)) * (10 ** (candidate_stuck_counter / 3.0))
             pert_data = None
             pmode = _cabi.PERT_UNIFORM if uniform else (_cabi.PERT_MT19937 if self.pert_mode == "mt19937" else _cabi.PERT_NONE)
-            if uniform:
+            if sparse:
+                pmode = _cabi.PERT_NONE                                                # no draws at all
+            elif uniform:
                 pert_data = np.empty((1, 2, n, n))
                 pert_data[0, 0] = np.random.rand(n, n)                                 # AMS:49
                 pert_data[0, 1] = np.random.rand(n, n)
@@ -154,8 +194,8 @@ class InverseIterateSolver:
                 elif method == "iterative_gmres":
                     if self.gmres_compat == "scipy-legacy":
                         raise TypeError("gmres() got an unexpected keyword argument 'tol'")
-                    typ = float(np.linalg.norm(A_target)) / np.sqrt(max(1, A_target.size))
-                    if pmode != _cabi.PERT_NONE and 0.075 * abs(ps[0]) >= 2.0 ** -53 * typ:
+                    if pmode != _cabi.PERT_NONE and 0.075 * abs(ps[0]) >= 2.0 ** -53 * (
+                            float(np.linalg.norm(A_target)) / np.sqrt(max(1, A_target.size))):
                         # escalated psi: the random term of AMS:49-50 is no longer below the rounding of a matvec ->
                         # GMRES against the materialised H_solve (engine.DeviceEngine.pert_matters states the rule)
                         want = np.array([1 if (candidate_stuck_counter > 1 and n > 0) else 0], dtype=np.int32)
@@ -638,7 +678,10 @@ class SolutionCandidate:
     # ---- AMS:145-331 -----------------------------------------------------------------------------
     def update_solution_step(self, current_matrix_A, b_vector=None, strat_params=None, global_knowledge=None):
         if _is_sparse(current_matrix_A) or global_knowledge.get("is_sparse_problem", False):
-            raise NotImplementedError("sparse problems are outside the MI355X hot path (dense only)")
+            if getattr(self._engine, "sparse_mode", "reject") != "device":
+                _reject_sparse("sparse problems")
+            if not _is_sparse(current_matrix_A):
+                raise NotImplementedError("is_sparse_problem with a dense matrix: pass the scipy.sparse matrix (AMS:357-358)")
         self._engine.step([self], current_matrix_A, b_vector, strat_params, global_knowledge)
 
     def get_current_solution_params(self):                      # AMS:333-337
@@ -662,10 +705,14 @@ class MAUS_Solver:
     def __init__(self, problem_matrix, problem_type, b_vector=None, initial_num_candidates=None,
                  global_convergence_tol=1e-8, *, device=0, pert_mode="auto", gmres_compat="rtol",
                  record_history=None, comm=None, quiet=False, engine=None, gram_min=8, cond_exact_max=1024,
-                 diag_info=None, eigh_mode="auto"):
+                 diag_info=None, eigh_mode="auto", sparse_mode=None):
+        sparse_mode = _sparse_mode(sparse_mode)
         if _is_sparse(problem_matrix):
-            raise NotImplementedError("sparse problems are outside the MI355X hot path (dense only)")
-        self.M = problem_matrix.astype(np.complex128)                                   # AMS:343
+            if sparse_mode != "device":
+                _reject_sparse("scipy.sparse matrices")
+            self.M = _as_spmatrix(problem_matrix).copy()                                # AMS:343: dtype kept
+        else:
+            self.M = problem_matrix.astype(np.complex128)                               # AMS:343
         self.N_rows, self.N_cols = self.M.shape
         self.N_diag = self.N_rows
         self.problem_type = problem_type
@@ -678,7 +725,8 @@ class MAUS_Solver:
         # `engine` is a test seam (tests/fake_ctx.py drives the host logic without a GPU); product
         # code never passes it, and DeviceEngine() raises if libmaus_hip / the device is missing
         self.engine = engine if engine is not None else DeviceEngine(device=device, pert_mode=pert_mode,
-                                                                     gmres_compat=gmres_compat, comm=comm, eigh_mode=eigh_mode)
+                                                                     gmres_compat=gmres_compat, comm=comm, eigh_mode=eigh_mode,
+                                                                     sparse_mode=sparse_mode)
         # `diag_info`: start-up diagnostics of the same matrix taken from an earlier solver (bench side runs)
         if diag_info is not None:
             self.diag_info = dict(diag_info)
@@ -712,7 +760,19 @@ class MAUS_Solver:
             "is_complex_symmetric": self.diag_info.get("is_complex_symmetric", False),
         }
         if self.problem_knowledge["is_sparse_problem"]:
-            raise NotImplementedError("matrices < 25% dense take the reference's sparse path, which is out of scope")
+            if sparse_mode != "device":
+                _reject_sparse("matrices < 25% dense")
+            import scipy.sparse as sp
+            if not isinstance(self.M, (sp.csc_matrix, sp.csr_matrix, sp.coo_matrix)):       # AMS:357-358
+                self.M = sp.csc_matrix(self.M)
+                self.problem_knowledge["matrix_type"] = "Sparse"
+            if comm is not None and comm.world > 1:
+                raise NotImplementedError("sharded runs (comm.world > 1) with a sparse matrix are not supported")
+            lu_max = getattr(self.engine.ctx, "lu_max_n", None)
+            if self.problem_type != ProblemType.SVD and lu_max is not None and self.N_rows > lu_max():
+                raise NotImplementedError(f"sparse eigenvalue / linear problems need n <= {lu_max()} (the direct fallback "
+                                          f"densifies H_k): n = {self.N_rows}")
+        self._sparse = _is_sparse(self.M)
         self.strat_params = {
             "overall_psi_aggression_factor": 1.0, "max_psi_retries": GLOBAL_MAX_PSI_ATTEMPTS,
             "min_survival_weight": GLOBAL_MIN_WEIGHT_TO_SURVIVE_PRUNE, "spawn_rate_multiplier": 1.0,
@@ -752,7 +812,7 @@ class MAUS_Solver:
         return SolutionCandidate(self.M, self.problem_type, self.N_diag, engine=self.engine,
                                  record_history=self._record_history, **kw)
 
-    # ---- AMS:374-404 (ndarray branch) ---------------------------------------------------------
+    # ---- AMS:374-404 (ndarray and spmatrix branches) ---------------------------------------------
     def _diagnose_matrix_initial(self, matrix):
         diag_info = {"is_hermitian": False, "is_complex_symmetric": False, "is_sparse_init": False,
                      "condition_number": np.inf, "is_singular": False}
@@ -764,6 +824,21 @@ class MAUS_Solver:
                         diag_info["is_hermitian"] = True
                     if _allclose_to_transpose(matrix, conj=False):             # np.allclose(M, M.T), AMS:383
                         diag_info["is_complex_symmetric"] = True
+            except Exception:
+                pass
+        elif _is_sparse(matrix):                                                # AMS:385-395
+            diag_info["is_sparse_init"] = True
+            try:
+                if matrix.shape[0] == matrix.shape[1]:
+                    if matrix.shape[0] * matrix.shape[1] > 1e7:
+                        print("Warning: Sparse matrix too large for dense conversion in property diagnosis. "
+                              "Assuming False for Hermitian/Symmetric.")
+                    else:
+                        M_dense = matrix.todense()
+                        if np.allclose(M_dense, M_dense.conj().T):
+                            diag_info["is_hermitian"] = True
+                        if np.allclose(M_dense, M_dense.T):
+                            diag_info["is_complex_symmetric"] = True
             except Exception:
                 pass
         cond_num_val = np.inf
@@ -1217,6 +1292,8 @@ class MAUS_Solver:
         systems above n = 512 on the device LU, Hermitian spectra and singular values from n = 1536 up through the device
         tridiagonalisation (SURVEY f-4); general eigenvalues by SciPy on the host (O(n^3))."""
         import scipy.linalg as sla
+        if getattr(self, "_sparse", False):
+            return self._reference_solution_sparse()
         try:
             if self.M.size == 0:
                 raise ValueError("Matrix is empty.")
@@ -1268,6 +1345,41 @@ class MAUS_Solver:
             print(f"NumPy reference calculation failed: {e}.")
             return None
 
+    def _reference_solution_sparse(self):
+        """AMS:554-570 for a sparse matrix, on its dense copy (M.todense(), AMS:555): eigenvalues and the linear solution as
+        for a dense matrix (the solution by the device LU above n = 512); singular values as svds(k = min(shape) - 1) reports
+        them -- the min(shape) - 1 largest, from a dense SVD."""
+        import scipy.linalg as sla
+        try:
+            M = np.asarray(self.M.todense())
+            if M.size == 0:
+                raise ValueError("Matrix is empty.")
+            if self.problem_type == ProblemType.EIGENVALUE:
+                if M.shape[0] != M.shape[1]:
+                    raise ValueError("Non-square matrix for Eigenvalue.")
+                vals = sla.eigvals(M)
+                vals.sort()
+                return vals
+            if self.problem_type == ProblemType.SOLVE_LINEAR_SYSTEM:
+                if self.b is None:
+                    raise ValueError("b_vector is None.")
+                if M.shape[0] != self.b.shape[0]:
+                    raise ValueError("A,b shape mismatch.")
+                if self.N_rows > 512 and hasattr(self.engine.ctx, "lu_solve"):
+                    if not (np.all(np.isfinite(M)) and np.all(np.isfinite(self.b))):
+                        raise ValueError("array must not contain infs or NaNs")
+                    x, st = self.engine.ctx.lu_solve(M.astype(np.complex128), self.b)
+                    if st[0] > 0:
+                        raise np.linalg.LinAlgError("Matrix is singular.")
+                    return x[0]
+                return sla.solve(M, self.b, assume_a="general")
+            k = min(M.shape) - 1 if min(M.shape) > 1 else 1
+            s = sorted(sla.svd(M, compute_uv=False).tolist(), reverse=True)
+            return s[:k]
+        except (np.linalg.LinAlgError, ValueError) as e:
+            print(f"NumPy reference calculation failed: {e}.")
+            return None
+
     def _report_residual(self, t):
         """Residual of one reported solution tuple, recomputed from the problem matrix (AMS:594-596)."""
         M = self.M
@@ -1288,7 +1400,8 @@ class MAUS_Solver:
             reference_check = True
         if reference_check:
             if (self.problem_type == ProblemType.EIGENVALUE and self.N_rows == self.N_cols and self.N_rows > REFERENCE_LAZY_MIN
-                    and not (self.problem_knowledge.get("is_hermitian", False) and self.engine.use_device_eigh(self.N_rows))):
+                    and not (self.problem_knowledge.get("is_hermitian", False) and self.engine.use_device_eigh(self.N_rows)
+                             and not self._sparse)):
                 # General eigenvalues are the one reference answer that still costs O(n^3) on the host (about a minute at
                 # n = 4096): computed when `true_solution` is first read -- by the closing comparison below, which only
                 # happens if something converged, or by the caller -- instead of in front of the first iteration.

@@ -82,6 +82,21 @@ int maus_lu_max_n(void);
 /* Upload the rows x cols problem matrix.  Replaces passing `current_matrix_A`
  * by reference into every step (AMS:576). */
 int maus_set_matrix(maus_ctx* ctx, const double* a_c128, int rows, int cols);
+
+/* ---- sparse problem matrices (AMS:357-358, 380-392: the reference's CSC / spmatrix branch) ---------------------------
+ * Upload a rows x cols matrix in CSR form: indptr[rows + 1] (int64, 0 .. nnz, non-decreasing), indices[nnz] (int32, in
+ * [0, cols), strictly increasing inside a row) and values[nnz] complex128.  Malformed input returns -1 with a message and
+ * leaves the device untouched.  The library keeps A and A^H in CSR (the latter built here) and the diagonal of A; no dense
+ * copy is allocated.  Every product with the problem matrix (Rayleigh quotient AMS:264, residuals AMS:295-298, the SVD
+ * power step AMS:228 / 240, the GMRES products of AMS:85) then runs as a CSR SpMM, and the direct solve builds H_k
+ * = A - lambda_k I + psi_k I (AMS:46-47: no random term) straight from the CSR operand into the LU workspace.  Entry points
+ * that need the dense matrix (maus_herm_tridiag, maus_gmres_pert, maus_comm_set_matrix) return an error.  nnz < 2^31.
+ * maus_set_matrix replaces a CSR matrix again.
+ * maus_matrix_is_sparse: 0 = dense matrix (or none), 1 = CSR with the lane-per-row SpMM schedule, 2 = CSR with the
+ * wave-per-row schedule (nnz / rows > 32). */
+int maus_set_matrix_csr(maus_ctx* ctx, int rows, int cols, int64_t nnz,
+                        const int64_t* indptr, const int32_t* indices, const double* values_c128);
+int maus_matrix_is_sparse(maus_ctx* ctx);
 /* Upload b (AMS:146, 275). */
 int maus_set_rhs(maus_ctx* ctx, const double* b_c128, int n);
 
