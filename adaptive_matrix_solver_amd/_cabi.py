@@ -21,6 +21,7 @@ SYMBOLS = [
     "maus_svd_power_step", "maus_svd_power_propose", "maus_svd_commit", "maus_set_eigvecs", "maus_herm_match", "maus_herm_tridiag", "maus_herm_release", "maus_herm_tridiag_eig", "maus_herm_tridiag_eigvals", "maus_herm_backtransform", "maus_get_eigvecs", "maus_gmres", "maus_gmres_pert", "maus_jacobi_check",
     "maus_profile_union_ms", "maus_gram", "maus_zgemm_host", "maus_lu_solve_host", "maus_timer_start", "maus_timer_stop",
     "maus_profile_enable", "maus_profile_read", "maus_sync", "maus_mt19937_jump",
+    "maus_sparse_max_n", "maus_band_prepare", "maus_band_reserve", "maus_band_solve", "maus_band_lu_host", "maus_band_workspace_allocs",
     "maus_device_count", "maus_comm_unique_id", "maus_comm_init", "maus_comm_destroy", "maus_comm_info",
     "maus_comm_allgather_records", "maus_comm_allgather_rows", "maus_comm_bcast", "maus_comm_bcast_eigvecs", "maus_comm_set_matrix", "maus_comm_stats",
 ]
@@ -31,7 +32,7 @@ POP_X, POP_U, POP_W, POP_Y = 0, 1, 2, 3
 KIND_EIG, KIND_LINEAR, KIND_SVD = 1, 2, 3
 PERT_NONE, PERT_UNIFORM, PERT_MT19937 = 0, 1, 2
 KC_NAMES = ["zgemm", "lu_panel", "trsm", "laswp", "build_h", "backsolve", "vector",
-            "zgemm_k128", "zgemm_k64", "zgemm_k32", "zgemm_k16", "spmm"]
+            "zgemm_k128", "zgemm_k64", "zgemm_k32", "zgemm_k16", "spmm", "band"]
 SPMM_SCHEDULES = {0: None, 1: "rows", 2: "wave"}     # maus_matrix_is_sparse: dense / lane per row / wave per row
 
 
@@ -114,6 +115,12 @@ def load_library():
         "maus_profile_read": ([vp, C.c_int, ip, dp, dp, dp], C.c_int),
         "maus_sync": ([vp], C.c_int),
         "maus_mt19937_jump": ([vp, i32p, C.c_uint64], C.c_int),
+        "maus_sparse_max_n": ([], C.c_int),
+        "maus_band_prepare": ([vp, vp, C.c_int, ip, ip], C.c_int),
+        "maus_band_reserve": ([vp, C.c_int, ip], C.c_int),
+        "maus_band_solve": ([vp, vp, C.c_int, vp, vp, C.c_int, vp], C.c_int),
+        "maus_band_lu_host": ([vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp], C.c_int),
+        "maus_band_workspace_allocs": ([vp], C.c_int),
         "maus_device_count": ([], C.c_int),
         "maus_comm_unique_id": ([C.c_char_p], C.c_int),
         "maus_comm_init": ([vp, C.c_int, C.c_int, C.c_char_p], C.c_int),
@@ -525,6 +532,55 @@ class Context:
         ok = np.zeros(k, dtype=np.int32)
         self._ck(self.lib.maus_jacobi_check(self.h, k, _ptr(sh), _ptr(ps), _ptr(ok)), "maus_jacobi_check")
         return ok.astype(bool)
+
+    # -- band solves of a sparse matrix (csrc/band.hip) ---------------------------------------------------------------
+    def sparse_max_n(self) -> int:
+        """Largest n of the CSR eigenvalue / linear path (band solves, GMRES on a CSR matrix)."""
+        return int(self.lib.maus_sparse_max_n())
+
+    def band_prepare(self, perm):
+        """Bind the ordering `perm` (band.band_order) of the bound sparse matrix; returns (kl, ku) of A[perm][:, perm]."""
+        p = np.ascontiguousarray(perm, dtype=np.int32)
+        kl, ku = C.c_int(), C.c_int()
+        self._ck(self.lib.maus_band_prepare(self.h, _ptr(p), int(p.shape[0]), C.byref(kl), C.byref(ku)), "maus_band_prepare")
+        return int(kl.value), int(ku.value)
+
+    def band_reserve(self, count) -> int:
+        """Size the band workspace once for `count` simultaneous solves; returns its capacity in solves."""
+        cap = C.c_int()
+        self._ck(self.lib.maus_band_reserve(self.h, int(count), C.byref(cap)), "maus_band_reserve")
+        return int(cap.value)
+
+    def band_solve(self, slots, shift, psi, rhs_mode=0):
+        """shifted_lu_solve (pert_mode NONE) through the band LU of the bound ordering: W[slot] = (A - shift I + psi I)^-1 rhs."""
+        s = self._slots(slots)
+        k = s.shape[0]
+        sh = _c128(shift, (k,))
+        ps = np.ascontiguousarray(psi, dtype=np.float64)
+        assert ps.shape == (k,)
+        status = np.zeros(k, dtype=np.int32)
+        self._ck(self.lib.maus_band_solve(self.h, _ptr(s), k, _ptr(sh), _ptr(ps), int(rhs_mode), _ptr(status)), "maus_band_solve")
+        return status
+
+    def band_workspace_allocations(self) -> int:
+        return int(self.lib.maus_band_workspace_allocs(self.h))
+
+    def band_lu(self, ab, b, kl, ku):
+        """zgbtrf + zgbtrs on the device: ab[count, 2kl+ku+1, n] in LAPACK's band layout (SciPy's `ab`), b[count, n] ->
+        (x[count, n], ipiv[count, n] 0-based as SciPy returns it, status[count])."""
+        ab = _c128(ab)
+        b = _c128(b)
+        if ab.ndim == 2:
+            ab, b = ab[None], b[None]
+        cnt, ldab, n = ab.shape
+        assert ldab == 2 * kl + ku + 1 and b.shape == (cnt, n)
+        abt = np.ascontiguousarray(ab.transpose(0, 2, 1))
+        x = np.empty((cnt, n), dtype=np.complex128)
+        ipiv = np.zeros((cnt, n), dtype=np.int32)
+        status = np.zeros(cnt, dtype=np.int32)
+        self._ck(self.lib.maus_band_lu_host(self.h, cnt, n, int(kl), int(ku), _ptr(abt), _ptr(b), _ptr(x), _ptr(ipiv), _ptr(status)),
+                 "maus_band_lu_host")
+        return x, ipiv - 1, status
 
     # -- population sharding: RCCL collectives on this context's stream (csrc/comm.hip) -----------------------------
     def comm_init(self, rank: int, world: int, unique_id: bytes):

@@ -1,0 +1,47 @@
+"""Ordering and band shape of a sparse problem matrix for the band solves of csrc/band.hip.
+
+`band_order(A)` picks, once per matrix, the symmetric permutation the band LU works in: reverse Cuthill-McKee on the pattern
+of |A| + |A|^T + I, or the identity when that is no wider.  Width is the band storage a solve needs, 2 kl + ku + 1 rows
+(zgbtrf's ldab).  The result depends on the matrix alone."""
+from __future__ import annotations
+
+import numpy as np
+
+
+def band_widths(A, perm) -> tuple[int, int]:
+    """(kl, ku): the lower and upper half-bandwidths of A[perm][:, perm] over its stored pattern."""
+    import scipy.sparse as sp
+    C = sp.coo_matrix(A)
+    n = C.shape[0]
+    iperm = np.empty(n, dtype=np.int64)
+    iperm[np.asarray(perm, dtype=np.int64)] = np.arange(n, dtype=np.int64)
+    if C.nnz == 0:
+        return 0, 0
+    d = iperm[C.row] - iperm[C.col]
+    return max(int(d.max()), 0), max(int(-d.min()), 0)
+
+
+def band_order(A) -> tuple[np.ndarray, int, int]:
+    """(perm, kl, ku) for a square scipy.sparse matrix A: perm[i] = the row of A that becomes row i."""
+    import scipy.sparse as sp
+    from scipy.sparse.csgraph import reverse_cuthill_mckee
+    M = sp.csr_matrix(A)
+    n = M.shape[0]
+    if M.shape[0] != M.shape[1]:
+        raise ValueError("band_order: square matrix required")
+    C = M.tocoo()
+    P = sp.csr_matrix((np.ones(C.nnz), (C.row, C.col)), shape=M.shape)
+    P = (P + P.T + sp.identity(n, format="csr")).tocsr()         # the pattern of |A| + |A|^T + I (no cancellation)
+    P.sort_indices()
+    rcm = np.asarray(reverse_cuthill_mckee(P, symmetric_mode=True), dtype=np.int64)
+    ident = np.arange(n, dtype=np.int64)
+    kl_i, ku_i = band_widths(M, ident)
+    kl_r, ku_r = band_widths(M, rcm)
+    if 2 * kl_i + ku_i + 1 <= 2 * kl_r + ku_r + 1:
+        return ident, kl_i, ku_i
+    return rcm, kl_r, ku_r
+
+
+def band_bytes_per_solve(n: int, kl: int, ku: int) -> int:
+    """Device memory of one band solve: the band storage, the right-hand side and the pivots (csrc/band.hip)."""
+    return 16 * ((2 * kl + ku + 1) * n + n) + 4 * n

@@ -1,0 +1,415 @@
+// Batched band LU with partial pivoting for sparse problem matrices above the dense LU's n (gfx950).
+//
+// A sparse matrix is bound once with an ordering perm (band.py: reverse Cuthill-McKee or the identity); B = A[perm][:, perm]
+// has kl subdiagonals and ku superdiagonals.  Every solve of maus_band_solve
+//     builds    H_k = B - lambda_k I + psi_k I  in LAPACK band storage (zgbtrf layout, ldab = 2 kl + ku + 1, column-major:
+//               element (i, j) at row kv + i - j of column j, kv = kl + ku; the first kl rows take the fill of U),
+//               and the permuted right-hand side X[slot][perm] (eigenproblems) or b[perm] (linear systems),
+//     factors   it as zgbtf2 does (pivot = first maximum of |re| + |im| among the kl + 1 candidates of the column, ipiv and info
+//               as LAPACK's), applying L to the right-hand side column by column as zgbtrs would afterwards,
+//     solves    U x = y as ztbsv does and writes x back in the original order into W[slot].
+//
+// Schedule: one workgroup per matrix walks all n columns; the work of a column (pivot search, interchange of two rows over
+// the columns the pivot row reaches, the kl x (kl + ku) rank-1 update) is spread over the workgroup.  Every element of the
+// band is changed by exactly one thread at each column step, by one fused multiply-subtract, and the pivot search is an exact
+// maximum with the lowest index among equals: there is no summation order that the workgroup size or the batch could change.
+// The workgroup size is picked from (kl, ku) alone and only decides who does what.  A candidate's W row is therefore
+// bit-identical alone, in any batch and in any chunking of the workspace (DESIGN §9's rule).
+#include "ctx.h"
+#include <climits>
+
+namespace {
+
+struct BandArgs {
+    c128* ab; c128* x; int* ipiv; int* info; int* flags;
+    int n, kl, ku, ldab;
+};
+
+__device__ __forceinline__ long bix(const BandArgs& a, int g) { return (long)g * a.ldab * a.n; }
+
+// H_k = A[perm][:, perm] - lam_k I + psi_k I into zeroed band storage, one thread per row of the permuted matrix; the
+// diagonal is (a - lam) + psi in NumPy's rounding order, with a = 0 where A stores none (as build_h_csr_kernel).  The permuted
+// right-hand side goes to x.  flags |= 1 on any non-finite value.
+__global__ void __launch_bounds__(256)
+band_build_csr_kernel(BandArgs a, const int* __restrict__ Ap, const int* __restrict__ Ai, const c128* __restrict__ Av,
+                      const int* __restrict__ perm, const int* __restrict__ iperm,
+                      const c128* __restrict__ shift, const double* __restrict__ psi,
+                      int rhs_mode, const c128* __restrict__ X, long ldx, const int* __restrict__ slots, const c128* __restrict__ bvec)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x, g = blockIdx.y;
+    bool bad = false;
+    if (i < a.n) {
+        c128* ab = a.ab + bix(a, g);
+        const int kv = a.kl + a.ku;
+        const c128 lam = shift[g];
+        const double ps = psi[g];
+        auto diag = [&](c128 v) { return cmake(__dadd_rn(__dsub_rn(v.x, lam.x), ps), __dadd_rn(__dsub_rn(v.y, lam.y), 0.0)); };
+        c128 h = diag(cmake(0.0, 0.0));
+        bad |= !cfinite(h);
+        ab[kv + (long)i * a.ldab] = h;
+        const int r = perm[i];
+        for (int p = Ap[r]; p < Ap[r + 1]; ++p) {
+            const int j = iperm[Ai[p]];
+            h = (j == i) ? diag(Av[p]) : Av[p];
+            bad |= !cfinite(h);
+            ab[kv + i - j + (long)j * a.ldab] = h;
+        }
+        const c128 v = (rhs_mode == 0) ? X[(long)slots[g] * ldx + r] : bvec[r];
+        bad |= !cfinite(v);
+        a.x[(long)g * a.n + i] = v;
+    }
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&a.flags[g], 1);
+}
+
+// band matrices and right-hand sides handed in by the caller (maus_band_lu_host): the non-finite scan only
+__global__ void __launch_bounds__(256)
+band_scan_kernel(BandArgs a)
+{
+    const int g = blockIdx.y;
+    const long per = (long)a.ldab * a.n;
+    bool bad = false;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < per; e += (long)gridDim.x * 256) {
+        // element (i, j) of the matrix sits at row r = kv + i - j of column j; the first kl rows are workspace and the corners
+        // outside 0 <= i < n are never read (zgbtrf)
+        const int r = (int)(e % a.ldab);
+        const long j = e / a.ldab, i = r - (a.kl + a.ku) + j;
+        if (r >= a.kl && i >= 0 && i < a.n) bad |= !cfinite(a.ab[bix(a, g) + e]);
+    }
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (long)gridDim.x * 256) bad |= !cfinite(a.x[(long)g * a.n + i]);
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&a.flags[g], 1);
+}
+
+// zgbtf2 on matrix blockIdx.x with the forward half of zgbtrs folded in (see the file comment).  Column j of a step is not
+// written before every thread has read its pivot and its old top entry: the interchange inside column j is carried by the
+// multipliers' source (the row that receives the old top entry) and by one store of the pivot at the end of the step.
+template <int NT>
+__global__ void __launch_bounds__(NT)
+band_factor_kernel(BandArgs a)
+{
+    constexpr int NW = NT / 64;
+    __shared__ double s_best[NW];
+    __shared__ int s_idx[NW];
+    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = a.n, kl = a.kl, ku = a.ku, kv = kl + ku, ldab = a.ldab;
+    c128* ab = a.ab + bix(a, g);
+    c128* x = a.x + (long)g * n;
+    int* ipiv = a.ipiv + (long)g * n;
+    auto at = [&](int r, int j) -> c128& { return ab[r + (long)j * ldab]; };
+    // rows handled together in the update (a power of two from 64 to NT, so that it divides NT) and the column groups that
+    // share them
+    int RW = 64;
+    while (RW < kl && RW < NT) RW *= 2;
+    const int CG = NT / RW;
+    const int pr = tid % RW, cg = tid / RW;
+    // the fill-in rows of columns ku + 1 .. min(kv, n) - 1 start at zero (zgbtf2)
+    for (int j = ku + 1; j < min(kv, n); ++j)
+        for (int r = kv - j + tid; r < kl; r += NT) at(r, j) = cmake(0.0, 0.0);
+    int ju = 0, info = 0;
+    for (int j = 0; j < n; ++j) {
+        if (j + kv < n) for (int r = tid; r < kl; r += NT) at(r, j + kv) = cmake(0.0, 0.0);
+        const int km = min(kl, n - 1 - j);
+        double best = -1.0; int bidx = INT_MAX;
+        for (int p = tid; p <= km; p += NT) {
+            const double v = cabs1(at(kv + p, j));
+            if (v > best) { best = v; bidx = p; }                        // NaN never wins (izamax)
+        }
+        wave_argmax(best, bidx);
+        if (lane == 0) { s_best[wave] = best; s_idx[wave] = bidx; }
+        __syncthreads();
+        double m = s_best[0]; int jp = s_idx[0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) {
+            if (s_best[w] > m) { m = s_best[w]; jp = s_idx[w]; }
+            else if (s_best[w] == m) jp = min(jp, s_idx[w]);
+        }
+        if (jp == INT_MAX) jp = 0;
+        const c128 piv = at(kv + jp, j), top = at(kv, j);
+        if (tid == 0) ipiv[j] = j + jp + 1;                              // LAPACK's 1-based row
+        if (piv.x == 0.0 && piv.y == 0.0) {
+            if (info == 0) info = j + 1;
+            __syncthreads();                                             // s_best / s_idx are written again by the next column
+            continue;
+        }
+        ju = max(ju, min(j + ku + jp, n - 1));
+        if (jp != 0) {
+            for (int c = j + 1 + tid; c <= ju; c += NT) {
+                const c128 t = at(kv + jp + j - c, c);
+                at(kv + jp + j - c, c) = at(kv + j - c, c);
+                at(kv + j - c, c) = t;
+            }
+            if (tid == 0) { const c128 t = x[j + jp]; x[j + jp] = x[j]; x[j] = t; }
+        }
+        __syncthreads();
+        if (km > 0) {
+            const c128 r = crecip(piv);
+            const c128 xj = x[j];
+            if (cg == 0)
+                for (int p = pr; p < km; p += RW) {
+                    const c128 l = cmul(p + 1 == jp ? top : at(kv + 1 + p, j), r);
+                    at(kv + 1 + p, j) = l;
+                    cfms(x[j + 1 + p], l, xj);
+                }
+            __syncthreads();
+            const int ncol = ju - j;
+            for (int p = pr; p < km; p += RW) {
+                const c128 l = at(kv + 1 + p, j);
+                for (int c = 1 + cg; c <= ncol; c += CG) cfms(at(kv + 1 + p - c, j + c), l, at(kv - c, j + c));
+            }
+        }
+        if (tid == 0 && jp != 0) at(kv, j) = piv;
+        __syncthreads();
+    }
+    if (tid == 0) a.info[g] = info;
+}
+
+// U x = y (ztbsv, upper, non-unit, k = kl + ku) on matrix blockIdx.x; x[j] goes to out[perm[j]] (out[j] without perm) once it
+// is final.  Every thread forms x[j] itself (the same division of the same operands), so one barrier per column suffices.
+// flags |= 2 on a non-finite result.
+template <int NT>
+__global__ void __launch_bounds__(NT)
+band_back_kernel(BandArgs a, c128* __restrict__ out, long ldo, const int* __restrict__ slots, const int* __restrict__ perm)
+{
+    const int g = blockIdx.x, tid = threadIdx.x;
+    const int n = a.n, kv = a.kl + a.ku, ldab = a.ldab;
+    const c128* ab = a.ab + bix(a, g);
+    c128* x = a.x + (long)g * n;
+    c128* o = out + (slots ? (long)slots[g] : (long)g) * ldo;
+    bool bad = false;
+    for (int j = n - 1; j >= 0; --j) {
+        c128 xj = x[j];
+        if (xj.x != 0.0 || xj.y != 0.0) {
+            xj = cdiv(xj, ab[kv + (long)j * ldab]);
+            for (int i = max(0, j - kv) + tid; i < j; i += NT) cfms(x[i], xj, ab[kv + i - j + (long)j * ldab]);
+        }
+        if (tid == 0) { o[perm ? perm[j] : j] = xj; bad |= !cfinite(xj); }
+        __syncthreads();
+    }
+    if (tid == 0 && bad) atomicOr(&a.flags[g], 2);
+}
+
+// workgroup size from (kl, ku) alone: one wave for narrow bands, where the barriers of every column dominate
+int band_threads(int kl, int ku) {
+    const long w = (long)kl * (kl + ku);
+    return w <= 512 ? 64 : (w <= 32768 ? 256 : 1024);
+}
+
+void launch_factor(const BandArgs& a, int G, hipStream_t st) {
+    switch (band_threads(a.kl, a.ku)) {
+    case 64: hipLaunchKernelGGL((band_factor_kernel<64>), dim3(G), dim3(64), 0, st, a); break;
+    case 256: hipLaunchKernelGGL((band_factor_kernel<256>), dim3(G), dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL((band_factor_kernel<1024>), dim3(G), dim3(1024), 0, st, a); break;
+    }
+}
+
+void launch_back(const BandArgs& a, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
+    switch (band_threads(a.kl, a.ku)) {
+    case 64: hipLaunchKernelGGL((band_back_kernel<64>), dim3(G), dim3(64), 0, st, a, out, ldo, slots, perm); break;
+    case 256: hipLaunchKernelGGL((band_back_kernel<256>), dim3(G), dim3(256), 0, st, a, out, ldo, slots, perm); break;
+    default: hipLaunchKernelGGL((band_back_kernel<1024>), dim3(G), dim3(1024), 0, st, a, out, ldo, slots, perm); break;
+    }
+}
+
+// algorithmic flops and bytes of G solves: 8 n kl (kl + ku) for the factorisation, 8 n (2 kl + ku) for the
+// solve; the band storage read and written once
+double band_flops(int n, int kl, int ku, int G) { return 8.0 * G * n * ((double)kl * (kl + ku) + 2.0 * kl + ku); }
+double band_bytes(int n, int ldab, int G) { return 32.0 * G * (double)ldab * n; }
+
+size_t band_per_solve(int n, int ldab) { return sizeof(c128) * ((size_t)ldab * n + n) + sizeof(int) * (size_t)n; }
+
+void band_ws_free(maus_ctx* c) {
+    void* ps[] = {c->band_ab, c->band_x, c->band_ipiv, c->band_info, c->band_flags};
+    for (void* p : ps) if (p) (void)hipFree(p);
+    c->band_ab = nullptr; c->band_x = nullptr; c->band_ipiv = nullptr; c->band_info = nullptr; c->band_flags = nullptr;
+    c->band_g = 0; c->band_at_limit = false; c->band_ws_key = 0;
+}
+
+// Band workspace for `want` simultaneous solves of the bound ordering, sized as ensure_lu_ws sizes the dense one: announced
+// once (maus_band_reserve), grown at most once more -- then to the cap (MAUS_BAND_BATCH, default 512, and 80 % of free
+// memory) -- never shrunk; larger batches run in balanced chunks.
+int ensure_band_ws(maus_ctx* c, int want) {
+    const int n = c->band_n, ldab = 2 * c->band_kl + c->band_ku + 1;
+    const size_t per = band_per_solve(n, ldab);
+    const unsigned long long key = ((unsigned long long)n << 32) | (unsigned)ldab;
+    const bool same = c->band_ab && c->band_ws_key == key;
+    if (same && (c->band_g >= want || c->band_at_limit)) return 0;
+    size_t fr = 0, tot = 0;
+    HIPCHK(c, hipMemGetInfo(&fr, &tot));
+    if (same) fr += per * c->band_g;
+    const int gmax = (int)std::max<size_t>(1, (size_t)(fr * 0.80) / per);
+    const char* env = getenv("MAUS_BAND_BATCH");
+    const int cap = env ? std::max(1, atoi(env)) : 512;
+    int G = std::max(1, want);
+    if (same) G = std::max(G, cap);                                     // a second allocation goes straight to the limit
+    G = std::min(std::min(G, cap), gmax);
+    if (same && c->band_g >= G) { c->band_at_limit = true; return 0; }
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    band_ws_free(c);
+    const int G_asked = G;
+    while (hipMalloc((void**)&c->band_ab, sizeof(c128) * (size_t)ldab * n * G) != hipSuccess) {
+        (void)hipGetLastError();
+        c->band_ab = nullptr;
+        if (G > 1) G = std::max(1, G * 3 / 4); else FAIL(c, "band workspace: hipMalloc failed even for one solve (out of device memory)");
+    }
+    HIPCHK(c, hipMalloc((void**)&c->band_x, sizeof(c128) * (size_t)n * G));
+    HIPCHK(c, hipMalloc((void**)&c->band_ipiv, sizeof(int) * (size_t)n * G));
+    HIPCHK(c, hipMalloc((void**)&c->band_info, sizeof(int) * G));
+    HIPCHK(c, hipMalloc((void**)&c->band_flags, sizeof(int) * G));
+    c->band_g = G; c->band_ws_key = key; c->band_allocs++;
+    c->band_at_limit = same || G < G_asked || G >= std::min(cap, gmax);
+    return 0;
+}
+
+BandArgs band_args(maus_ctx* c) {
+    BandArgs a;
+    a.ab = c->band_ab; a.x = c->band_x; a.ipiv = c->band_ipiv; a.info = c->band_info; a.flags = c->band_flags;
+    a.n = c->band_n; a.kl = c->band_kl; a.ku = c->band_ku; a.ldab = 2 * a.kl + a.ku + 1;
+    return a;
+}
+
+void band_status(int G, const int* info, const int* flags, int32_t* status) {
+    for (int g = 0; g < G; ++g) {
+        if (flags[g] & 1) status[g] = -1;
+        else if (info[g] > 0) status[g] = info[g];
+        else if (flags[g] & 2) status[g] = -2;
+        else status[g] = 0;
+    }
+}
+
+}  // namespace
+
+void maus_band_drop(maus_ctx* c) {
+    if (c->band_perm) (void)hipFree(c->band_perm);
+    if (c->band_iperm) (void)hipFree(c->band_iperm);
+    c->band_perm = nullptr; c->band_iperm = nullptr;
+    c->band_n = 0; c->band_kl = -1; c->band_ku = -1;
+    band_ws_free(c);
+}
+
+extern "C" {
+
+int maus_sparse_max_n(void) { return 1 << 20; }
+
+int maus_band_prepare(maus_ctx* c, const int32_t* perm, int n, int* kl_out, int* ku_out) {
+    if (!c) return -1;
+    if (!c->csr) FAIL(c, "maus_band_prepare: no sparse matrix bound (maus_set_matrix_csr)");
+    if (c->rows != c->cols || n != c->rows) FAIL(c, "maus_band_prepare: the ordering must have the bound square matrix's n entries");
+    if (!perm) FAIL(c, "maus_band_prepare: null ordering");
+    if (n > maus_sparse_max_n()) FAIL(c, "maus_band_prepare: n exceeds maus_sparse_max_n()");
+    std::vector<int> iperm((size_t)n, -1);
+    for (int i = 0; i < n; ++i) {
+        const int r = perm[i];
+        if (r < 0 || r >= n || iperm[r] >= 0) FAIL(c, "maus_band_prepare: perm is not a permutation of 0..n-1");
+        iperm[r] = i;
+    }
+    // kl / ku of A[perm][:, perm] from the pattern of the bound CSR matrix
+    std::vector<int> ptr((size_t)n + 1), idx((size_t)c->Acsr.nnz);
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(ptr.data(), c->Acsr.ptr, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost));
+    if (c->Acsr.nnz) HIPCHK(c, hipMemcpy(idx.data(), c->Acsr.idx, sizeof(int) * (size_t)c->Acsr.nnz, hipMemcpyDeviceToHost));
+    int kl = 0, ku = 0;
+    for (int r = 0; r < n; ++r) {
+        const int i = iperm[r];
+        for (int p = ptr[r]; p < ptr[r + 1]; ++p) {
+            const int d = i - iperm[idx[p]];
+            kl = std::max(kl, d); ku = std::max(ku, -d);
+        }
+    }
+    maus_band_drop(c);
+    HIPCHK(c, hipMalloc((void**)&c->band_perm, sizeof(int) * (size_t)n));
+    HIPCHK(c, hipMalloc((void**)&c->band_iperm, sizeof(int) * (size_t)n));
+    HIPCHK(c, hipMemcpy(c->band_perm, perm, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->band_iperm, iperm.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+    c->band_n = n; c->band_kl = kl; c->band_ku = ku;
+    if (kl_out) *kl_out = kl;
+    if (ku_out) *ku_out = ku;
+    return 0;
+}
+
+int maus_band_reserve(maus_ctx* c, int count, int* capacity_out) {
+    if (!c) return -1;
+    if (!c->band_perm) FAIL(c, "maus_band_reserve: no ordering (maus_band_prepare)");
+    if (count < 0) FAIL(c, "maus_band_reserve: bad count");
+    if (count > 0 && ensure_band_ws(c, count)) return -1;
+    if (capacity_out) *capacity_out = c->band_g;
+    return 0;
+}
+
+int maus_band_solve(maus_ctx* c, const int* slots, int count, const double* shift, const double* psi, int rhs_mode, int32_t* status) {
+    if (!c) return -1;
+    maus_av_drop_all(c);
+    if (!c->csr || !c->X) FAIL(c, "maus_band_solve: sparse matrix/population missing");
+    if (!c->band_perm || c->band_n != c->rows) FAIL(c, "maus_band_solve: no ordering for the bound matrix (maus_band_prepare)");
+    if (rhs_mode != 0 && rhs_mode != 1) FAIL(c, "maus_band_solve: rhs_mode must be 0 (X[slot]) or 1 (b)");
+    if (rhs_mode == 1 && (!c->b || c->bn != c->rows)) FAIL(c, "maus_band_solve: rhs b not set");
+    if (count == 0) return 0;
+    if (check_slots(c, slots, count)) return -1;
+    if (ensure_scalars(c, count)) return -1;
+    if (ensure_band_ws(c, count)) return -1;
+    const int nchunks = (count + c->band_g - 1) / c->band_g;            // balanced chunks, as maus_shifted_lu_solve
+    const int Gmax = (count + nchunks - 1) / nchunks;
+    std::vector<int> h_info(Gmax), h_flags(Gmax);
+    const BandArgs a = band_args(c);
+    for (int off = 0; off < count; off += Gmax) {
+        const int G = std::min(Gmax, count - off);
+        if (maus_h2d(c, c->d_slots, slots + off, sizeof(int) * G, c->st)) return -1;
+        if (maus_h2d(c, c->d_c1, shift + 2 * (size_t)off, sizeof(c128) * G, c->st)) return -1;
+        if (maus_h2d(c, c->d_r1, psi + off, sizeof(double) * G, c->st)) return -1;
+        {
+            ProfScope ps(c, KC_BAND, band_flops(a.n, a.kl, a.ku, G), band_bytes(a.n, a.ldab, G));
+            HIPCHK(c, hipMemsetAsync(a.info, 0, sizeof(int) * G, c->st));
+            HIPCHK(c, hipMemsetAsync(a.flags, 0, sizeof(int) * G, c->st));
+            HIPCHK(c, hipMemsetAsync(a.ab, 0, sizeof(c128) * (size_t)a.ldab * a.n * G, c->st));
+            hipLaunchKernelGGL(band_build_csr_kernel, dim3((a.n + 255) / 256, G), dim3(256), 0, c->st, a, c->Acsr.ptr, c->Acsr.idx,
+                               c->Acsr.val, c->band_perm, c->band_iperm, c->d_c1, c->d_r1, rhs_mode, c->X, c->ldp, c->d_slots, c->b);
+            launch_factor(a, G, c->st);
+            launch_back(a, G, c->st, c->W, c->ldp, c->d_slots, c->band_perm);
+        }
+        if (maus_d2h(c, h_info.data(), a.info, sizeof(int) * G, c->st)) return -1;
+        if (maus_d2h(c, h_flags.data(), a.flags, sizeof(int) * G, c->st)) return -1;
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        HIPCHK(c, hipGetLastError());
+        band_status(G, h_info.data(), h_flags.data(), status + off);
+    }
+    return 0;
+}
+
+int maus_band_workspace_allocs(maus_ctx* c) { return c ? c->band_allocs : -1; }
+
+int maus_band_lu_host(maus_ctx* c, int count, int n, int kl, int ku, const double* ab, const double* b, double* x_out,
+                      int32_t* ipiv_out, int32_t* info_out) {
+    if (!c) return -1;
+    if (count <= 0 || n <= 0 || kl < 0 || ku < 0 || n > maus_sparse_max_n()) FAIL(c, "maus_band_lu_host: bad sizes");
+    if (!ab || !b || !x_out || !info_out) FAIL(c, "maus_band_lu_host: null array");
+    BandArgs a;
+    a.n = n; a.kl = kl; a.ku = ku; a.ldab = 2 * kl + ku + 1;
+    const size_t abb = sizeof(c128) * (size_t)a.ldab * n, xb = sizeof(c128) * (size_t)n, ib = sizeof(int) * (size_t)n;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    const size_t o_ab = take(abb * count), o_x = take(xb * count), o_o = take(xb * count), o_p = take(ib * count),
+                 o_i = take(sizeof(int) * count), o_f = take(sizeof(int) * count);
+    if (ensure_scratch(c, off)) return -1;
+    char* base = (char*)c->scratch;
+    a.ab = (c128*)(base + o_ab); a.x = (c128*)(base + o_x); a.ipiv = (int*)(base + o_p); a.info = (int*)(base + o_i); a.flags = (int*)(base + o_f);
+    c128* out = (c128*)(base + o_o);
+    if (maus_stage_h2d(c, a.ab, ab, abb * count, c->st)) return -1;
+    if (maus_stage_h2d(c, a.x, b, xb * count, c->st)) return -1;
+    HIPCHK(c, hipMemsetAsync(a.info, 0, sizeof(int) * count, c->st));
+    HIPCHK(c, hipMemsetAsync(a.flags, 0, sizeof(int) * count, c->st));
+    {
+        ProfScope ps(c, KC_BAND, band_flops(n, kl, ku, count), band_bytes(n, a.ldab, count));
+        hipLaunchKernelGGL(band_scan_kernel, dim3(64, count), dim3(256), 0, c->st, a);
+        launch_factor(a, count, c->st);
+        launch_back(a, count, c->st, out, n, nullptr, nullptr);
+    }
+    std::vector<int> h_info(count), h_flags(count);
+    if (maus_stage_d2h(c, x_out, out, xb * count, c->st)) return -1;
+    if (ipiv_out && maus_stage_d2h(c, ipiv_out, a.ipiv, ib * count, c->st)) return -1;
+    if (maus_d2h(c, h_info.data(), a.info, sizeof(int) * count, c->st)) return -1;
+    if (maus_d2h(c, h_flags.data(), a.flags, sizeof(int) * count, c->st)) return -1;
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipGetLastError());
+    band_status(count, h_info.data(), h_flags.data(), info_out);
+    return 0;
+}
+
+}  // extern "C"

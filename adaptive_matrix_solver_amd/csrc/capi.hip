@@ -264,6 +264,7 @@ int maus_ctx_destroy(maus_ctx* c) {
                     c->H, c->ipiv, c->perm, c->ident, c->mw_sync, c->info, c->flags, c->Upert, c->scratch, c->hq, c->htau, c->hz, c->S};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     maus_csr_free(c->Acsr); maus_csr_free(c->AHcsr);
+    maus_band_drop(c);
     if (c->Adiag) (void)hipFree(c->Adiag);
     if (c->pin) (void)hipHostFree(c->pin);
     if (c->pin_small) (void)hipHostFree(c->pin_small);
@@ -314,6 +315,7 @@ static void free_population(maus_ctx* c) {
 // drops the CSR operands of a sparse matrix (spmm.hip)
 static void csr_drop(maus_ctx* c) {
     maus_csr_free(c->Acsr); maus_csr_free(c->AHcsr);
+    maus_band_drop(c);
     if (c->Adiag) { (void)hipFree(c->Adiag); c->Adiag = nullptr; }
     c->csr = false; c->csr_sched = 0;
 }
@@ -1188,6 +1190,23 @@ int maus_gram(maus_ctx* c, int which, const int* slots, int count, int len, doub
 int maus_gmres(maus_ctx* c, const int* slots, int count, const double* shift, const double* psi, int rhs_mode,
                const int32_t* use_jacobi, double rtol, int restart, int maxiter, int32_t* info_out, int32_t* inner_out, int32_t* status) {
     av_drop_all(c);
+    // Above maus_lu_max_n() (CSR only) one candidate's basis, iterate and product take (R + 3) n complex entries, 386 MB at
+    // n = 2^20: a batch runs in chunks whose scratch stays within 1/16 of the device's total HBM (a rule of n and the device).
+    // Candidates never share arithmetic (per-row SpMM, one workgroup per candidate), so the chunking changes no result.
+    if (c && c->csr && c->rows > maus_lu_max_n() && count > 1 && slots && shift && psi && use_jacobi && info_out && inner_out && status) {
+        size_t fr = 0, tot = 0;
+        HIPCHK(c, hipMemGetInfo(&fr, &tot));
+        const size_t per = sizeof(c128) * (size_t)(std::max(1, std::min(restart, 20)) + 3) * c->rows + 4096;
+        const int chunk = (int)std::max<size_t>(1, tot / 16 / per);
+        if (count > chunk) {
+            for (int off = 0; off < count; off += chunk) {
+                const int g = std::min(chunk, count - off);
+                if (maus_gmres_run(c, slots + off, g, shift + 2 * (size_t)off, psi + off, rhs_mode, use_jacobi + off, rtol, restart, maxiter,
+                                   info_out + off, inner_out + off, status + off, nullptr, 0, 0, nullptr)) return -1;
+            }
+            return 0;
+        }
+    }
     return maus_gmres_run(c, slots, count, shift, psi, rhs_mode, use_jacobi, rtol, restart, maxiter, info_out, inner_out, status,
                           nullptr, 0, 0, nullptr);
 }

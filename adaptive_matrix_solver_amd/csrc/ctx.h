@@ -50,6 +50,7 @@ void maus_build_h_csr(const LuWs& w, const MausCsr& A, const c128* d_shift, cons
 int maus_gmres_run(maus_ctx* ctx, const int* slots, int count, const double* shift, const double* psi, int rhs_mode,
                    const int32_t* use_jacobi, double rtol, int restart, int maxiter, int32_t* info_out, int32_t* inner_out, int32_t* status,
                    const c128* Hdense, long ldh, long strideH, int32_t* jacobi_out);
+void maus_band_drop(maus_ctx* c);            // band.hip: the ordering and workspace of the previous sparse matrix
 int maus_jacobi_check_run(maus_ctx* ctx, int count, const double* shift, const double* psi, int32_t* ok);
 
 // ---- context ---------------------------------------------------------------------------
@@ -62,6 +63,11 @@ struct maus_ctx {
     c128* A = nullptr; int rows = 0, cols = 0;      // problem matrix
     // sparse problem matrix (maus_set_matrix_csr): A and A^H in CSR, the diagonal of A, the SpMM schedule; A stays null
     bool csr = false; MausCsr Acsr, AHcsr; c128* Adiag = nullptr; int csr_sched = 0;
+    // band solves of a sparse matrix (band.hip): the ordering of maus_band_prepare, the half-bandwidths of A[perm][:, perm], and
+    // the batched band workspace (maus_band_reserve); dropped with the CSR operands
+    int* band_perm = nullptr; int* band_iperm = nullptr; int band_n = 0, band_kl = -1, band_ku = -1;
+    c128* band_ab = nullptr; c128* band_x = nullptr; int *band_ipiv = nullptr, *band_info = nullptr, *band_flags = nullptr;
+    int band_g = 0, band_allocs = 0; bool band_at_limit = false; unsigned long long band_ws_key = 0;
     c128* b = nullptr; int bn = 0;                  // rhs
     c128* V = nullptr; int vn = 0;                  // eigenvectors (Hermitian shortcut)
     c128* hq = nullptr; c128* htau = nullptr; int hqn = 0;   // Householder reflectors of maus_herm_tridiag, until the back-transformation (herm.hip)

@@ -447,6 +447,156 @@ gmres_post_kernel(GArgs a, const int* __restrict__ act) {
     }
 }
 
+// gmres_post_kernel for 16384 < n (CSR matrices only): w is not held in registers but streamed through the basis row it
+// becomes, V[col + 1] (the Arnoldi step) or V[0] (the residual of a new cycle); thread t owns the entries t, t + NT, ... of
+// every vector, as the register kernels do.  Same modified Gram-Schmidt order, state machine and exits; the variant is picked
+// from n alone.
+template <int NT>
+__global__ void __launch_bounds__(NT)
+gmres_post_stream_kernel(GArgs a, const int* __restrict__ act) {
+    __shared__ double sbuf[NT / 64];
+    __shared__ c128 s_h[MAXR + 2];
+    __shared__ c128 s_y[MAXR + 1];
+    __shared__ int s_flag[2];
+    const int k = act[blockIdx.x];
+    GState& s = a.st[k];
+    const int n = a.n, R = a.R, tid = threadIdx.x;
+    const int phase = s.phase, col = s.col;
+    c128* Vk = a.Vb + (long)k * a.rows_per * n;
+    c128* x = Vk + (long)(R + 1) * n;
+    const c128* y = a.Y + (long)k * n;
+    const c128 lam = a.shift[k];
+    const c128 sh = a.Hd ? cmake(0.0, 0.0) : cmake(a.psi[k] - lam.x, -lam.y);
+
+    if (phase == 1) {
+        const c128* b = rhs_of(a, k);
+        c128* w = Vk;
+        double ss = 0.0;
+        for (int i = tid; i < n; i += NT) {
+            c128 hx = y[i]; cfma(hx, sh, x[i]);
+            const c128 r = cmake(b[i].x - hx.x, b[i].y - hx.y);
+            w[i] = r;
+            ss = fma(r.x, r.x, ss); ss = fma(r.y, r.y, ss);
+        }
+        const double rnorm = sqrt(blk_sum<NT>(ss, sbuf));
+        bool done = false; int info = 0;
+        double pmf = s.pmf, ptol = s.ptol; int cycle = s.cycle;
+        if (!(rnorm == rnorm)) { done = true; info = a.maxiter; }
+        else if (s.first) { if (rnorm < s.atol) { done = true; info = 0; } }
+        else {
+            if (rnorm <= s.atol) { done = true; info = 0; }
+            else if (s.breakdown) { done = true; info = a.maxiter; }
+            else {
+                if (s.presid <= s.ptol) pmf = fmax(EPS, 0.25 * pmf); else pmf = fmin(1.0, 1.5 * pmf);
+                ptol = s.presid * fmin(pmf, s.atol / rnorm);
+                cycle += 1;
+                if (cycle >= a.maxiter) { done = true; info = a.maxiter; }
+            }
+        }
+        if (done) {
+            __syncthreads();
+            if (tid == 0) { s.rnorm = rnorm; s.info = info; s.phase = 2; }
+            return;
+        }
+        double sv = 0.0;
+        for (int i = tid; i < n; i += NT) {
+            const c128 v = psolve1(a, k, i, w[i]);
+            w[i] = v;
+            sv = fma(v.x, v.x, sv); sv = fma(v.y, v.y, sv);
+        }
+        const double tmp = sqrt(blk_sum<NT>(sv, sbuf));
+        const double inv = 1.0 / tmp;
+        for (int i = tid; i < n; i += NT) w[i] = cmake(w[i].x * inv, w[i].y * inv);
+        if (tid == 0) {
+            s.rnorm = rnorm; s.pmf = pmf; s.ptol = ptol; s.cycle = cycle; s.first = 0;
+            for (int j = 0; j <= R; ++j) s.S[j] = cmake(0.0, 0.0);
+            s.S[0] = cmake(tmp, 0.0);
+            s.col = 0; s.breakdown = 0; s.phase = 0;
+        }
+        return;
+    }
+
+    const c128* z = Vk + (long)col * n;
+    c128* w = Vk + (long)(col + 1) * n;
+    double ss = 0.0;
+    for (int i = tid; i < n; i += NT) {
+        c128 av = y[i]; cfma(av, sh, z[i]);
+        const c128 v = psolve1(a, k, i, av);
+        w[i] = v;
+        ss = fma(v.x, v.x, ss); ss = fma(v.y, v.y, ss);
+    }
+    const double h0 = sqrt(blk_sum<NT>(ss, sbuf));
+    for (int kk = 0; kk <= col; ++kk) {                        // modified Gram-Schmidt
+        const c128* vk = Vk + (long)kk * n;
+        double tr = 0.0, ti = 0.0;
+        for (int i = tid; i < n; i += NT) {
+            const c128 v = vk[i], wi = w[i];
+            tr = fma(v.x, wi.x, tr); tr = fma(v.y, wi.y, tr);
+            ti = fma(v.x, wi.y, ti); ti = fma(-v.y, wi.x, ti);
+        }
+        tr = blk_sum<NT>(tr, sbuf); ti = blk_sum<NT>(ti, sbuf);
+        const c128 t = cmake(tr, ti);
+        if (tid == 0) s_h[kk] = t;
+        for (int i = tid; i < n; i += NT) { c128 wi = w[i]; cfms(wi, t, vk[i]); w[i] = wi; }
+    }
+    ss = 0.0;
+    for (int i = tid; i < n; i += NT) { const c128 wi = w[i]; ss = fma(wi.x, wi.x, ss); ss = fma(wi.y, wi.y, ss); }
+    const double h1 = sqrt(blk_sum<NT>(ss, sbuf));
+    const bool brk = h1 <= EPS * h0;
+    {
+        const double inv = brk ? 1.0 : 1.0 / h1;
+        for (int i = tid; i < n; i += NT) w[i] = cmake(w[i].x * inv, w[i].y * inv);
+    }
+    if (tid == 0) {
+        s_h[col + 1] = cmake(brk ? 0.0 : h1, 0.0);
+        for (int kk = 0; kk < col; ++kk) {
+            const double c = s.gc[kk]; const c128 sg = s.gs[kk];
+            const c128 n0 = s_h[kk], n1 = s_h[kk + 1];
+            c128 a0 = cmake(c * n0.x, c * n0.y); cfma(a0, sg, n1);
+            c128 a1 = cmake(c * n1.x, c * n1.y); cfms(a1, cconj(sg), n0);
+            s_h[kk] = a0; s_h[kk + 1] = a1;
+        }
+        double c; c128 sg, mag;
+        zlartg_dev(s_h[col], s_h[col + 1], c, sg, mag);
+        s.gc[col] = c; s.gs[col] = sg;
+        s_h[col] = mag; s_h[col + 1] = cmake(0.0, 0.0);
+        const c128 Sc = s.S[col];
+        const c128 tmp = cmul(cmake(-sg.x, sg.y), Sc);
+        s.S[col] = cmake(c * Sc.x, c * Sc.y);
+        s.S[col + 1] = tmp;
+        const double presid = hypot(tmp.x, tmp.y);
+        s.presid = presid;
+        s.inner += 1;
+        for (int j = 0; j <= col + 1; ++j) s.h[col][j] = s_h[j];
+        if (brk) s.breakdown = 1;
+        const bool end_inner = (presid <= s.ptol) || brk || (col == R - 1);
+        s_flag[0] = end_inner ? 1 : 0;
+        if (end_inner) {
+            if (s.h[col][col].x == 0.0 && s.h[col][col].y == 0.0) s.S[col] = cmake(0.0, 0.0);
+            for (int j = 0; j <= col; ++j) s_y[j] = s.S[j];
+            for (int kk = col; kk > 0; --kk) {
+                if (s_y[kk].x != 0.0 || s_y[kk].y != 0.0) {
+                    s_y[kk] = cdiv_np(s_y[kk], s.h[kk][kk]);
+                    const c128 t = s_y[kk];
+                    for (int j = 0; j < kk; ++j) cfms(s_y[j], t, s.h[kk][j]);
+                }
+            }
+            if (s_y[0].x != 0.0 || s_y[0].y != 0.0) s_y[0] = cdiv_np(s_y[0], s.h[0][0]);
+            s.phase = 1;
+        } else {
+            s.col = col + 1;
+        }
+    }
+    __syncthreads();
+    if (s_flag[0]) {                                           // x += y @ V[:col+1]
+        for (int i = tid; i < n; i += NT) {
+            c128 acc = x[i];
+            for (int j = 0; j <= col; ++j) cfma(acc, s_y[j], Vk[(long)j * n + i]);
+            x[i] = acc;
+        }
+    }
+}
+
 // W[slot] <- x ; outputs
 __global__ void __launch_bounds__(GT)
 gmres_finish_kernel(GArgs a, c128* __restrict__ W, long ldw, int* __restrict__ info, int* __restrict__ inner, int* __restrict__ status) {
@@ -496,7 +646,8 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
     if (rhs_mode == 1 && (!c->b || c->bn != c->rows)) FAIL(c, "maus_gmres: rhs b not set");
     if (count <= 0) return 0;
     const int n = c->rows;
-    if (n > maus_lu_max_n()) FAIL(c, "maus_gmres: n <= 16384 in this build");
+    if (n > maus_lu_max_n() && !c->csr) FAIL(c, "maus_gmres: n <= 16384 in this build (a CSR matrix: n <= maus_sparse_max_n())");
+    if (n > maus_sparse_max_n()) FAIL(c, "maus_gmres: n exceeds maus_sparse_max_n()");
     const int R = std::max(1, std::min(std::min(restart, MAXR), n));
     if (maxiter < 1) maxiter = 1;
     if (upload_slots(c, slots, count)) return -1;
@@ -555,7 +706,8 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
           if (n <= 4 * GT) hipLaunchKernelGGL((gmres_post_kernel<4>), dim3(h_nact), dim3(GT), 0, c->st, a, act);
           else if (n <= 16 * GT) hipLaunchKernelGGL((gmres_post_kernel<16>), dim3(h_nact), dim3(GT), 0, c->st, a, act);
           else if (n <= 32 * GT) hipLaunchKernelGGL((gmres_post_kernel<32>), dim3(h_nact), dim3(GT), 0, c->st, a, act);
-          else hipLaunchKernelGGL((gmres_post_kernel<32, 2 * GT>), dim3(h_nact), dim3(2 * GT), 0, c->st, a, act); }
+          else if (n <= 64 * GT) hipLaunchKernelGGL((gmres_post_kernel<32, 2 * GT>), dim3(h_nact), dim3(2 * GT), 0, c->st, a, act);
+          else hipLaunchKernelGGL((gmres_post_stream_kernel<4 * GT>), dim3(h_nact), dim3(4 * GT), 0, c->st, a, act); }
     }
     hipLaunchKernelGGL(gmres_finish_kernel, dim3(count), dim3(GT), 0, c->st, a, c->W, c->ldp, outs, outs + count, outs + 2 * count);
     if (maus_d2h(c, info_out, outs, sizeof(int) * count, c->st)) return -1;

@@ -237,6 +237,17 @@ def tridiagonal_eigenvalues(ctx, d, e):
     return np.sort(sla.eigvalsh_tridiagonal(d, e))
 
 
+SPARSE_DIRECT_MODES = ("auto", "dense", "band")
+
+
+def sparse_direct_mode(mode):
+    """The `sparse_direct` keyword: an explicit value, else MAUS_SPARSE_DIRECT, else 'auto'."""
+    mode = mode if mode is not None else os.environ.get("MAUS_SPARSE_DIRECT", "auto")
+    if mode not in SPARSE_DIRECT_MODES:
+        raise ValueError(f"sparse_direct must be one of {SPARSE_DIRECT_MODES}, not {mode!r}")
+    return mode
+
+
 def _is_sparse_matrix(A) -> bool:
     try:
         import scipy.sparse as sp
@@ -251,7 +262,7 @@ class DeviceEngine:
     _default = None
 
     def __init__(self, device: int = 0, pert_mode: str = "auto", gmres_compat: str = "rtol",
-                 comm=None, ctx=None, eigh_mode: str = "auto", sparse_mode=None):
+                 comm=None, ctx=None, eigh_mode: str = "auto", sparse_mode=None, sparse_direct=None):
         self.ctx = ctx if ctx is not None else _cabi.Context(device)
         cap_blas_threads()
         # Hermitian eigendecomposition (AMS:161), once per matrix: 'host' = scipy.linalg.eigh, the reference's call, (lambda, V)
@@ -264,6 +275,13 @@ class DeviceEngine:
         if self.sparse_mode not in ("reject", "device"):
             raise ValueError(f"sparse_mode must be 'reject' or 'device', not {self.sparse_mode!r}")
         self._sparse = False                    # the bound matrix is sparse (CSR on the device)
+        # direct solves of a sparse matrix: 'dense' densifies H_k into the LU workspace (n <= maus_lu_max_n()),
+        # 'band' runs the band LU in the ordering of band.band_order, 'auto' the first up to maus_lu_max_n() and the second
+        # above.  MAUS_SPARSE_DIRECT sets the default.  Chosen once per bound matrix (_band).
+        self.sparse_direct = sparse_direct_mode(sparse_direct)
+        self._band = False                      # the bound sparse matrix takes the band solve
+        self._band_ready = False                # ... and its ordering is on the device (prepared at the first band solve)
+        self._band_cache = None                 # (matrix obj, perm, kl, ku) of band_shape
         self._owner = {}                        # id(candidate) -> rank that executes it this step
         self.pert_mode = pert_mode              # 'auto' | 'uniform' | 'mt19937' | 'none'
         self.gmres_compat = gmres_compat        # 'rtol' | 'scipy-legacy'  
@@ -309,6 +327,8 @@ class DeviceEngine:
                 raise NotImplementedError("sharded runs (comm.world > 1) with a sparse matrix are not supported")
             self.ctx.set_matrix_csr(A)
             self._sparse = True
+            self._band = self.uses_band(A.shape[0]) and A.shape[0] == A.shape[1]
+            self._band_ready = False            # set_matrix_csr dropped the previous ordering
             self._bound = A
             if shape_changed:
                 self._free = []
@@ -317,6 +337,7 @@ class DeviceEngine:
                 self.store = CandidateStore()
             return
         self._sparse = False
+        self._band = False
         if collective:
             self.ctx.comm_set_matrix(A, comm.rank, 0, resident_on_root=(comm.rank == 0 and solo and A is self._bound))
             comm.collectives += 1
@@ -331,6 +352,31 @@ class DeviceEngine:
             self._next_slot = 0
             self._bound_b = None
             self.store = CandidateStore()       # the slots start again at 0: candidates of the old shape keep the old store
+
+    def uses_band(self, n: int) -> bool:
+        """Whether a sparse n x n matrix takes the band solve (sparse_direct; 'auto': above maus_lu_max_n())."""
+        if self.sparse_direct == "band":
+            return True
+        if self.sparse_direct == "dense":
+            return False
+        lu_max = getattr(self.ctx, "lu_max_n", None)
+        return n > (lu_max() if lu_max is not None else 16384)
+
+    def prepare_band(self):
+        """The bound sparse matrix's ordering on the device, at its first band solve: problems that never solve directly (SVD)
+        pay neither the ordering nor the host copy of the pattern."""
+        if not self._band_ready:
+            perm, kl, ku = self.band_shape(self._bound)
+            self.ctx.band_prepare(perm)
+            self._band_ready = True
+
+    def band_shape(self, A):
+        """(perm, kl, ku) of band.band_order for the sparse matrix A, once per matrix object."""
+        c = self._band_cache
+        if c is None or c[0] is not A:
+            from .band import band_order
+            c = self._band_cache = (A,) + band_order(A)
+        return c[1], c[2], c[3]
 
     def pert_matters(self, psi) -> np.ndarray:
         """AMS:49-52 adds 0.15*psi*((U1-.5)+i(U2-.5)) to H for GMRES as for the direct solve.  The device GMRES shares one
@@ -526,6 +572,9 @@ class DeviceEngine:
         return f[:, 0] + 1j * f[:, 1], f[:, 2] + 1j * f[:, 3]
 
     def d_lu_solve(self, cands, shift, psi, rhs_mode, pert, pert_data):
+        if self._band:                          # sparse matrix on the band path (no random term, never sharded)
+            self.prepare_band()
+            return self.ctx.band_solve([c._slot for c in cands], shift, psi, rhs_mode)
         mine = self._mine(cands)
         if mine is None:
             return self.ctx.shifted_lu_solve([c._slot for c in cands], shift, psi, rhs_mode=rhs_mode,
@@ -950,7 +999,10 @@ class DeviceEngine:
         # step (freeing and mapping ~100 GB takes seconds; HBM is otherwise idle)
         world = self.comm.world if self.comm is not None else 1
         share = -(-len(cands) // world)
-        if pref == DIRECT or self.gmres_compat == "scipy-legacy":
+        if self._band and (pref == DIRECT or self.gmres_compat == "scipy-legacy"):
+            self.prepare_band()
+            self.ctx.band_reserve(max(2 * share, share + 320))
+        elif pref == DIRECT or self.gmres_compat == "scipy-legacy":
             self.ctx.lu_reserve(n, max(2 * share, share + -(-320 // world)))
         # (GMRES preferred: the LU only serves the candidates whose GMRES attempt fails, and its workspace is sized for them
         # when that happens -- reserving the whole population's H_k here cost configs[2] 4.7 s in its first loop body and a

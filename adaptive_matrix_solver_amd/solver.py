@@ -31,7 +31,7 @@ import numpy as np
 from . import _cabi
 from ._cabi import POP_U, POP_X
 from .candstore import C_NP as _C_NP, C_PY as _C_PY, EXACT as _EXACT, F_NP as _F_NP, F_PY as _F_PY, HREF as _HREF, MISSING as _MISSING
-from .engine import DIRECT, GMRES, DeviceEngine, _advance_numpy_stream
+from .engine import DIRECT, GMRES, DeviceEngine, _advance_numpy_stream, sparse_direct_mode
 
 
 class ProblemType(Enum):                     # AMS:10-13
@@ -126,7 +126,7 @@ class InverseIterateSolver:
     _engine = None          # private context: every call uploads its own A_target
 
     def __init__(self, N, base_psi_epsilon, max_attempts, preferred_method="direct_solve", is_sparse=False,
-                 gmres_compat="rtol", pert_mode="uniform", sparse_mode=None):
+                 gmres_compat="rtol", pert_mode="uniform", sparse_mode=None, sparse_direct=None):
         self.N = N
         self.base_psi_epsilon = base_psi_epsilon
         self.max_attempts = max_attempts
@@ -136,6 +136,7 @@ class InverseIterateSolver:
         self.gmres_compat = gmres_compat
         self.pert_mode = pert_mode
         self.sparse_mode = _sparse_mode(sparse_mode)
+        self.sparse_direct = sparse_direct_mode(sparse_direct)
         self.last_trace = []
 
     @classmethod
@@ -154,8 +155,15 @@ class InverseIterateSolver:
             # AMS:46-47, 55-56: H = A_target + psi*I, no random term; the direct solve densifies H on the device (spsolve's
             # NaNs on a singular H land in the same ValueError -> retry branch as the LU's info > 0)
             import scipy.sparse as sp
-            ctx.set_matrix_csr(A_target if _is_sparse(A_target) else sp.csr_matrix(A_target))
+            A_sp = A_target if _is_sparse(A_target) else sp.csr_matrix(A_target)
+            ctx.set_matrix_csr(A_sp)
+            # direct solves above maus_lu_max_n() (or with sparse_direct='band'): the band LU of csrc/band.hip
+            band = self.sparse_direct == "band" or (self.sparse_direct == "auto" and n > ctx.lu_max_n())
+            if band:
+                from .band import band_order
+                ctx.band_prepare(band_order(A_sp)[0])
         else:
+            band = False
             A_target = np.ascontiguousarray(A_target, dtype=np.complex128)
             ctx.set_matrix(A_target)
         ctx.set_rhs(np.ascontiguousarray(b_rhs, dtype=np.complex128))
@@ -184,7 +192,10 @@ class InverseIterateSolver:
             rec = {"method": method, "attempt": num_psi_attempts, "psi": psi}
             try:
                 if method == "direct_solve":
-                    st = ctx.shifted_lu_solve([0], zero, ps, rhs_mode=1, pert_mode=pmode, pert_data=pert_data)[0]
+                    if band:
+                        st = ctx.band_solve([0], zero, ps, rhs_mode=1)[0]
+                    else:
+                        st = ctx.shifted_lu_solve([0], zero, ps, rhs_mode=1, pert_mode=pmode, pert_data=pert_data)[0]
                     if st > 0:
                         raise np.linalg.LinAlgError("Matrix is singular.")
                     if st == -1:
@@ -705,8 +716,9 @@ class MAUS_Solver:
     def __init__(self, problem_matrix, problem_type, b_vector=None, initial_num_candidates=None,
                  global_convergence_tol=1e-8, *, device=0, pert_mode="auto", gmres_compat="rtol",
                  record_history=None, comm=None, quiet=False, engine=None, gram_min=8, cond_exact_max=1024,
-                 diag_info=None, eigh_mode="auto", sparse_mode=None):
+                 diag_info=None, eigh_mode="auto", sparse_mode=None, sparse_direct=None):
         sparse_mode = _sparse_mode(sparse_mode)
+        sparse_direct = sparse_direct_mode(sparse_direct)
         if _is_sparse(problem_matrix):
             if sparse_mode != "device":
                 _reject_sparse("scipy.sparse matrices")
@@ -726,7 +738,7 @@ class MAUS_Solver:
         # code never passes it, and DeviceEngine() raises if libmaus_hip / the device is missing
         self.engine = engine if engine is not None else DeviceEngine(device=device, pert_mode=pert_mode,
                                                                      gmres_compat=gmres_compat, comm=comm, eigh_mode=eigh_mode,
-                                                                     sparse_mode=sparse_mode)
+                                                                     sparse_mode=sparse_mode, sparse_direct=sparse_direct)
         # `diag_info`: start-up diagnostics of the same matrix taken from an earlier solver (bench side runs)
         if diag_info is not None:
             self.diag_info = dict(diag_info)
@@ -769,9 +781,13 @@ class MAUS_Solver:
             if comm is not None and comm.world > 1:
                 raise NotImplementedError("sharded runs (comm.world > 1) with a sparse matrix are not supported")
             lu_max = getattr(self.engine.ctx, "lu_max_n", None)
-            if self.problem_type != ProblemType.SVD and lu_max is not None and self.N_rows > lu_max():
-                raise NotImplementedError(f"sparse eigenvalue / linear problems need n <= {lu_max()} (the direct fallback "
-                                          f"densifies H_k): n = {self.N_rows}")
+            if self.problem_type != ProblemType.SVD and lu_max is not None:
+                use_band = getattr(self.engine, "uses_band", None)
+                if use_band is not None and use_band(self.N_rows):
+                    self._check_band_fits()
+                elif self.N_rows > lu_max():
+                    raise NotImplementedError(f"sparse eigenvalue / linear problems need n <= {lu_max()} (the direct fallback "
+                                              f"densifies H_k): n = {self.N_rows}")
         self._sparse = _is_sparse(self.M)
         self.strat_params = {
             "overall_psi_aggression_factor": 1.0, "max_psi_retries": GLOBAL_MAX_PSI_ATTEMPTS,
@@ -1345,11 +1361,31 @@ class MAUS_Solver:
             print(f"NumPy reference calculation failed: {e}.")
             return None
 
+    def _check_band_fits(self):
+        """A sparse eigenvalue / linear problem on the band path: n <= maus_sparse_max_n() and one band solve in at
+        most 1/16 of the device's total HBM -- a rule of the matrix and the device, never of free memory or the batch."""
+        from .band import band_bytes_per_solve
+        n = self.N_rows
+        ctx = self.engine.ctx
+        max_n = ctx.sparse_max_n()
+        if n > max_n:
+            raise NotImplementedError(f"sparse eigenvalue / linear problems need n <= {max_n}: n = {n}")
+        perm, kl, ku = self.engine.band_shape(self.M)
+        per = band_bytes_per_solve(n, kl, ku)
+        hbm = int(ctx.device_info()["hbm_total"])
+        if per * 16 > hbm:
+            raise NotImplementedError(f"sparse eigenvalue / linear problem too wide for the band solve: n = {n}, kl = {kl}, "
+                                      f"ku = {ku} after reordering, {per} bytes per solve > 1/16 of the device's {hbm} bytes")
+
     def _reference_solution_sparse(self):
         """AMS:554-570 for a sparse matrix, on its dense copy (M.todense(), AMS:555): eigenvalues and the linear solution as
         for a dense matrix (the solution by the device LU above n = 512); singular values as svds(k = min(shape) - 1) reports
-        them -- the min(shape) - 1 largest, from a dense SVD."""
+        them -- the min(shape) - 1 largest, from a dense SVD.  Above maus_lu_max_n() the dense copy is never made:
+        the linear solution comes from one band solve on the device (shift 0, psi 0), eigenvalues are not computed."""
         import scipy.linalg as sla
+        lu_max = getattr(self.engine.ctx, "lu_max_n", None)
+        if self.problem_type != ProblemType.SVD and lu_max is not None and self.N_rows > lu_max():
+            return self._reference_solution_band()
         try:
             M = np.asarray(self.M.todense())
             if M.size == 0:
@@ -1376,6 +1412,34 @@ class MAUS_Solver:
             k = min(M.shape) - 1 if min(M.shape) > 1 else 1
             s = sorted(sla.svd(M, compute_uv=False).tolist(), reverse=True)
             return s[:k]
+        except (np.linalg.LinAlgError, ValueError) as e:
+            print(f"NumPy reference calculation failed: {e}.")
+            return None
+
+    def _reference_solution_band(self):
+        if self.problem_type == ProblemType.EIGENVALUE:
+            print(f"(reference eigenvalues not computed for a sparse matrix with n = {self.N_rows} > "
+                  f"{self.engine.ctx.lu_max_n()}: true_solution stays None)")
+            return None
+        try:
+            if self.b is None:
+                raise ValueError("b_vector is None.")
+            if self.N_rows != self.b.shape[0]:
+                raise ValueError("A,b shape mismatch.")
+            eng = self.engine
+            eng.bind_matrix(self.M)
+            eng.bind_rhs(self.b)
+            eng.prepare_band()
+            slot = eng.alloc_slot()
+            try:
+                st = eng.ctx.band_solve([slot], np.zeros(1, dtype=np.complex128), np.zeros(1), rhs_mode=1)[0]
+                if st > 0:
+                    raise np.linalg.LinAlgError("Matrix is singular.")
+                if st < 0:
+                    raise ValueError("array must not contain infs or NaNs" if st == -1 else "Solution vector not finite after solve.")
+                return eng.ctx.pop_get(_cabi.POP_W, [slot], self.N_rows)[0]
+            finally:
+                eng.free_slot(slot)
         except (np.linalg.LinAlgError, ValueError) as e:
             print(f"NumPy reference calculation failed: {e}.")
             return None

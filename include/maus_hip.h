@@ -97,6 +97,32 @@ int maus_set_matrix(maus_ctx* ctx, const double* a_c128, int rows, int cols);
 int maus_set_matrix_csr(maus_ctx* ctx, int rows, int cols, int64_t nnz,
                         const int64_t* indptr, const int32_t* indices, const double* values_c128);
 int maus_matrix_is_sparse(maus_ctx* ctx);
+
+/* ---- band solves of a sparse matrix --------------------------
+ * maus_sparse_max_n: the largest n of the CSR eigenvalue / linear path (1 << 20); maus_gmres accepts it for a CSR matrix,
+ *   the dense modes keep maus_lu_max_n().
+ * maus_band_prepare: the ordering perm[n] (a permutation of 0..n-1, checked on the host) of the bound square CSR matrix;
+ *   returns kl / ku, the lower / upper half-bandwidths of A[perm][:, perm], computed from the bound pattern.  Bad input
+ *   returns -1 and launches nothing.  Binding another matrix drops the ordering.
+ * maus_band_reserve: the band workspace for `count` simultaneous solves, sized once as maus_lu_reserve sizes the dense one
+ *   (MAUS_BAND_BATCH caps it, default 512); capacity_out (may be NULL): solves it holds.
+ * maus_band_solve: the contract of maus_shifted_lu_solve with pert_mode NONE, on H_k = A - shift_k I + psi_k I in band
+ *   storage: W[slot] = H_k^-1 (rhs_mode 0: X[slot], 1: b).  status[k]: 0, -1 non-finite H_k or right-hand side, > 0 the
+ *   1-based column of the first exact zero pivot in the permuted order (zgbtrf's info), -2 non-finite solution.
+ * maus_band_lu_host: `count` band matrices given in LAPACK's zgbtrf input layout, ab[count][n][ldab] (column j holds
+ *   ldab = 2 kl + ku + 1 entries, A(i, j) at row kl + ku + i - j; the first kl rows are workspace), and b[count][n]:
+ *   x_out[count][n], ipiv_out[count][n] (may be NULL; LAPACK's 1-based rows) and info_out[count] with the status values
+ *   above.  Test entry point.
+ * maus_band_workspace_allocs: (re-)allocations of the band workspace on this context. */
+int maus_sparse_max_n(void);
+int maus_band_prepare(maus_ctx* ctx, const int32_t* perm, int n, int* kl_out, int* ku_out);
+int maus_band_reserve(maus_ctx* ctx, int count, int* capacity_out);
+int maus_band_solve(maus_ctx* ctx, const int* slots, int count, const double* shift_c128, const double* psi, int rhs_mode,
+                    int32_t* status);
+int maus_band_lu_host(maus_ctx* ctx, int count, int n, int kl, int ku, const double* ab_c128, const double* b_c128,
+                      double* x_out_c128, int32_t* ipiv_out, int32_t* info_out);
+int maus_band_workspace_allocs(maus_ctx* ctx);
+
 /* Upload b (AMS:146, 275). */
 int maus_set_rhs(maus_ctx* ctx, const double* b_c128, int n);
 

@@ -1,0 +1,156 @@
+"""Band solve rates (csrc/band.hip) -> profiles/band_rates.txt.
+
+The 2-D 5-point operator (complex values, shuffled, then reordered by band.band_order) at n = 16384, 65536 and 262144: a lone
+shifted solve and a batch, timed by the library's HIP-event profile of the "band" class (build + factorisation + solve).
+Flops 8 n kl (kl + ku) + 8 n (2 kl + ku), bytes = the band storage read and written once; the bound is the larger of the
+fp64 peak (MI355X: 78.6 TFLOP/s, no MFMA in this kernel) and HBM (8 TB/s).  Then band against the densified dense LU at
+n = 16384 for the same 64 shifted systems, both paths in one process, and MAUS_Solver linear loop bodies at n = 65536, P = 64
+(5-point operator + 2 I) on the direct path (gmres_compat='scipy-legacy': every solve a band solve) and on the GMRES path.
+
+    python tools/band_rates.py [--out profiles/band_rates.txt]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import scipy.sparse as sp
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from adaptive_matrix_solver_amd import _cabi  # noqa: E402
+from adaptive_matrix_solver_amd.band import band_order  # noqa: E402
+
+PEAK_F64, HBM = 78.6e12, 8.0e12
+
+
+def five_point(m, seed=0):
+    rng = np.random.default_rng(seed)
+    T = sp.diags([-1.0, 4.0, -1.0], [-1, 0, 1], shape=(m, m))
+    L = (sp.kron(sp.identity(m), T) + sp.kron(sp.diags([-1.0, -1.0], [-1, 1], shape=(m, m)), sp.identity(m))).tocsr()
+    L = L.astype(np.complex128)
+    L.data = L.data * (1.0 + 0.3j * rng.standard_normal(L.nnz))
+    p = rng.permutation(m * m)
+    return L[p][:, p].tocsr()
+
+
+def bind(ctx, A, P):
+    ctx.set_matrix_csr(A)
+    perm, kl, ku = band_order(A)
+    ctx.band_prepare(perm)
+    ctx.pop_reserve(P)
+    rng = np.random.default_rng(1)
+    n = A.shape[0]
+    ctx.pop_put(_cabi.POP_X, np.arange(P), rng.standard_normal((P, n)) + 1j * rng.standard_normal((P, n)))
+    return kl, ku
+
+
+def timed_band(ctx, count, reps=2):
+    rng = np.random.default_rng(2)
+    shift = rng.standard_normal(count) + 1j * rng.standard_normal(count)
+    psi = np.full(count, 1e-3)
+    slots = np.arange(count)
+    ctx.band_reserve(count)
+    ctx.band_solve(slots, shift, psi, 0)                       # warm-up
+    best = None
+    for _ in range(reps):
+        ctx.profile_enable(False)
+        ctx.profile_enable(True)
+        t0 = time.perf_counter()
+        st = ctx.band_solve(slots, shift, psi, 0)
+        wall = time.perf_counter() - t0
+        pr = ctx.profile_read()["band"]
+        assert (st == 0).all(), st
+        if best is None or pr["ms"] < best[0]["ms"]:
+            best = (pr, wall)
+    ctx.profile_enable(False)
+    return best
+
+
+def loop_rate(compat, bodies=3):
+    import random
+    from adaptive_matrix_solver_amd.solver import MAUS_Solver, ProblemType, SolutionCandidate
+    A = (five_point(256, 7) + 2.0 * sp.identity(65536)).tocsr()
+    rng = np.random.default_rng(8)
+    b = rng.standard_normal(65536) + 1j * rng.standard_normal(65536)
+    np.random.seed(3); random.seed(3); SolutionCandidate._candidate_id_counter = 0
+    diag = {"is_sparse_init": True, "condition_number": 1e7, "is_singular": False, "is_hermitian": False,
+            "is_complex_symmetric": False}
+    s = MAUS_Solver(A, ProblemType.SOLVE_LINEAR_SYSTEM, b_vector=b, initial_num_candidates=64, quiet=True, sparse_mode="device",
+                    gmres_compat=compat, diag_info=diag)
+    s.loop_body(1)
+    ctx = s.engine.ctx
+    ctx.profile_enable(False)
+    ctx.profile_enable(True)
+    steps, t0 = 0, time.perf_counter()
+    for it in range(bodies):
+        steps += len(s.candidates)
+        s.loop_body(it + 2)
+    ctx.sync()
+    wall = time.perf_counter() - t0
+    pr = ctx.profile_read()
+    ctx.profile_enable(False)
+    return steps / wall, pr["band"]["ms"] / bodies, pr["spmm"]["ms"] / bodies
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default="profiles/band_rates.txt")
+    ap.add_argument("--sizes", default="128:1,128:64,256:1,256:64,512:1,512:8")
+    args = ap.parse_args()
+    ctx = _cabi.Context(0)
+    info = ctx.device_info()
+    lines = [f"# band solves, csrc/band.hip -- {info['name']}, {info['cus']} CUs",
+             "# ms / solve from the 'band' profile class (HIP events around build + factor + solve of one batch);",
+             "# bound = max(flops / 78.6 TFLOP/s fp64, bytes / 8 TB/s); share = bound time / measured time",
+             f"{'n':>7} {'kl':>4} {'ku':>4} {'batch':>5} {'ms/solve':>9} {'TFLOP/s':>8} {'TB/s':>6} {'bound':>5} {'share':>7}"]
+    cache = {}
+    for item in args.sizes.split(","):
+        m, P = (int(v) for v in item.split(":"))
+        n = m * m
+        if m not in cache:
+            A = five_point(m, m)
+            cache.clear()
+            cache[m] = (A, bind(ctx, A, 64))
+        A, (kl, ku) = cache[m]
+        pr, wall = timed_band(ctx, P)
+        s = pr["ms"] / 1e3
+        tf, tb = pr["flops"] / s / 1e12, pr["bytes"] / s / 1e12
+        tc, tm = pr["flops"] / PEAK_F64, pr["bytes"] / HBM
+        bound = "fp64" if tc >= tm else "HBM"
+        lines.append(f"{n:>7} {kl:>4} {ku:>4} {P:>5} {pr['ms'] / P:>9.3f} {tf:>8.3f} {tb:>6.2f} {bound:>5} {max(tc, tm) / s:>7.2%}")
+        print(lines[-1], flush=True)
+    # band against dense at n = 16384: the same 64 shifted systems
+    m, P = 128, 64
+    A = five_point(m, 3)
+    n = m * m
+    bind(ctx, A, P)
+    rng = np.random.default_rng(4)
+    shift = rng.standard_normal(P) + 1j * rng.standard_normal(P)
+    psi = np.full(P, 1e-3)
+    slots = np.arange(P)
+    ctx.band_reserve(P)
+    ctx.band_solve(slots, shift, psi, 0)
+    t0 = time.perf_counter(); ctx.band_solve(slots, shift, psi, 0); tb = time.perf_counter() - t0
+    Wb = ctx.pop_get(_cabi.POP_W, slots, n)
+    ctx.lu_reserve(n, P)
+    t0 = time.perf_counter(); ctx.shifted_lu_solve(slots, shift, psi, 0); td = time.perf_counter() - t0
+    Wd = ctx.pop_get(_cabi.POP_W, slots, n)
+    rel = max(np.linalg.norm(Wb[k] - Wd[k]) / np.linalg.norm(Wd[k]) for k in range(P))
+    lines += ["", "# band vs dense (densified H_k, maus_shifted_lu_solve) at n = 16384, 64 shifted 5-point systems, wall clock per call",
+              f"band  {tb * 1e3 / P:9.3f} ms/solve", f"dense {td * 1e3 / P:9.3f} ms/solve",
+              f"speed-up {td / tb:.1f}x, largest relative difference of the solutions {rel:.2e}"]
+    print("\n".join(lines[-4:]), flush=True)
+    ctx.close()                                                # its workspaces would crowd out the solver's own context
+    lines += ["", "# MAUS_Solver linear loop bodies at n = 65536, P = 64 (5-point + 2 I, GMRES preferred): 1 untimed + 3 timed bodies;",
+              "# candidate-steps = candidates in the population at the start of each timed body"]
+    for compat, path in (("scipy-legacy", "direct (band)"), ("rtol", "GMRES")):
+        rate, band_ms, spmm_ms = loop_rate(compat)
+        lines.append(f"{path:<14} {rate:9.1f} candidate-steps/s   (band class {band_ms:8.1f} ms, spmm class {spmm_ms:8.1f} ms per body)")
+        print(lines[-1], flush=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
