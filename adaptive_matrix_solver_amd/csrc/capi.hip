@@ -305,6 +305,10 @@ int maus_sync(maus_ctx* c) { HIPCHK(c, hipStreamSynchronize(c->st)); return 0; }
 static void free_population(maus_ctx* c) {
     c128** ps[] = {&c->X, &c->U, &c->W, &c->Y};
     for (auto p : ps) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    // S (A^H u of the SVD step) has the population's shape, Scap rows of ldp: it goes with it.  (Kept, a context that had run an
+    // SVD step and was then bound to a matrix with longer vectors wrote A^H u past the end of the old, smaller S.)
+    if (c->S) { (void)hipFree(c->S); c->S = nullptr; }
+    c->Scap = 0;
     c->cap = 0; c->ldp = 0;
 }
 

@@ -5,6 +5,13 @@
 //   SVD normalisations   AMS:233-242      Hermitian arg-max   AMS:165-173
 #include "common.h"
 
+// The element-wise results below promise NumPy's rounding order: one rounding per __dmul_rn / __dadd_rn / __dsub_rn.  hipcc
+// defines these as plain `x * y`, `x + y`, `x - y` and its default for device code, -ffp-contract=fast, lets the backend fuse a
+// product into the sum that uses it whatever a pragma in the source says: half of the complex products of relax_normalise /
+// residual / svd_resid had become FMAs and 27 % of the relaxed entries differed from the stated rounding in the last bit
+// (tests/test_gpu_vector_kernels.py).  The Makefile therefore compiles THIS FILE with -ffp-contract=off; the dot products and
+// norms ask for their FMAs by name (fma()).
+
 namespace {
 
 constexpr int VT = 256;   // threads per candidate
@@ -174,8 +181,15 @@ norm_kernel(const c128* __restrict__ S, long ld, const int* __restrict__ slots, 
     if (threadIdx.x == 0) norm_out[(long)g * stride_out + off_out] = sqrt(ss);
 }
 
-// Hermitian match: scores S[slot][j] = |v^H V[:,j]| (already as complex dots in S) -> argmax (first max),
-// then X[slot] <- V[:, idx] / ||V[:, idx]||.
+// Hermitian match: scores S[slot][j] = |v^H V[:,j]| (already as complex dots in S) -> np.argmax (AMS:169): the first maximum,
+// and a NaN score ranks above every number (np.argmax returns the index of the first NaN as soon as one score is NaN), so
+// the order is "NaN before any number, then the larger value, then the smaller index"; then X[slot] <- V[:, idx] / ||V[:, idx]||.
+__device__ __forceinline__ bool herm_better(double v, int j, double best, int bidx) {
+    const bool vn = v != v, bn = best != best;
+    if (vn || bn) return vn && (!bn || j < bidx);
+    return v > best || (v == best && j < bidx);
+}
+
 __global__ void __launch_bounds__(VT)
 herm_pick_kernel(const c128* __restrict__ S, long lds_, c128* __restrict__ X, long ldx, const int* __restrict__ slots,
                  const c128* __restrict__ V, int n, int* __restrict__ idx_out, double* __restrict__ norm_out)
@@ -185,23 +199,22 @@ herm_pick_kernel(const c128* __restrict__ S, long lds_, c128* __restrict__ X, lo
     __shared__ double sbuf[VT / 64];
     const int g = blockIdx.x;
     const c128* s = S + (long)slots[g] * lds_;
-    double best = -1.0; int bidx = 0x7fffffff;
+    double best = -1.0; int bidx = 0x7fffffff;           // (threads without a score: below every |score| >= 0 and every NaN)
     for (int j = threadIdx.x; j < n; j += VT) {
         const double v = hypot(s[j].x, s[j].y);
-        if (v > best) { best = v; bidx = j; }
+        if (herm_better(v, j, best, bidx)) { best = v; bidx = j; }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         double ov = __shfl_xor(best, o, 64); int oi = __shfl_xor(bidx, o, 64);
-        if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
+        if (herm_better(ov, oi, best, bidx)) { best = ov; bidx = oi; }
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) { sval[wave] = best; sidx[wave] = bidx; }
     __syncthreads();
     best = sval[0]; bidx = sidx[0];
 #pragma unroll
-    for (int w = 1; w < VT / 64; ++w) if (sval[w] > best || (sval[w] == best && sidx[w] < bidx)) { best = sval[w]; bidx = sidx[w]; }
-    if (bidx == 0x7fffffff) bidx = 0;       // all-NaN scores: np.argmax returns the first NaN; flagged by the residual
+    for (int w = 1; w < VT / 64; ++w) if (herm_better(sval[w], sidx[w], best, bidx)) { best = sval[w]; bidx = sidx[w]; }
     c128* x = X + (long)slots[g] * ldx;
     double ss = 0.0;
     for (int i = threadIdx.x; i < n; i += VT) { const c128 a = V[(long)i * n + bidx]; ss = fma(a.x, a.x, ss); ss = fma(a.y, a.y, ss); }

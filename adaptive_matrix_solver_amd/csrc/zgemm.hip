@@ -336,7 +336,7 @@ zgemm_kernel(int M, int N, int K,
 // the third product's operand sums become differences (one VALU op either way) and the epilogue takes P2 = Ai Bi with the sign
 // sa sb; the MFMA stream is unchanged.  With these the population products (A@X of the Rayleigh / residual phases and of every
 // GMRES inner iteration, A^H u of the SVD step, conj(X) V of the Hermitian match) run 6 M N K on the pipe instead of the 4M
-// kernel's 8 M N K (MAUS_POPGEMM_3M=0: back to 4M).
+// kernel's 8 M N K.
 template <int NST, int MINW, int MB, int NB, bool TILED = false, int BLAY = 0, bool CONJA = false, bool CONJB = false>
 __global__ void __launch_bounds__(256, MINW)
 zgemm3m_dma_kernel(int M, int N, int K,
@@ -564,6 +564,8 @@ void launch_lu_only(hipStream_t st, int M, int N, int K, const c128* A, long lda
 }  // namespace
 
 // Host-side launcher (device pointers).  batch matrices at element strides sA/sB/sC.
+// tests/test_gpu_zgemm_variants.py carries a Python copy of the rule below (variant()) and a table of shapes that reaches every
+// kernel it can pick: a change to the rule has to be made there too.
 // a_rows / c_rows (device int arrays of length M, or null): row gather for A / row scatter
 // for C -- the population's candidate vectors live in arbitrary slots of one array.
 void maus_zgemm_launch_rows(hipStream_t st, int M, int N, int K, const c128* A, long lda, long sA,
