@@ -21,6 +21,7 @@ SYMBOLS = [
     "maus_svd_power_step", "maus_svd_power_propose", "maus_svd_commit", "maus_set_eigvecs", "maus_herm_match", "maus_herm_tridiag", "maus_herm_release", "maus_herm_tridiag_eig", "maus_herm_tridiag_eigvals", "maus_herm_backtransform", "maus_get_eigvecs", "maus_gmres", "maus_gmres_pert", "maus_jacobi_check",
     "maus_profile_union_ms", "maus_gram", "maus_zgemm_host", "maus_lu_solve_host", "maus_timer_start", "maus_timer_stop",
     "maus_profile_enable", "maus_profile_read", "maus_sync", "maus_mt19937_jump",
+    "maus_lanczos_begin", "maus_lanczos_inject", "maus_lanczos_extend", "maus_lanczos_restart", "maus_lanczos_finish", "maus_herm_match_rows", "maus_get_ritz_rows",
     "maus_sparse_max_n", "maus_band_prepare", "maus_band_reserve", "maus_band_solve", "maus_band_lu_host", "maus_band_workspace_allocs",
     "maus_device_count", "maus_comm_unique_id", "maus_comm_init", "maus_comm_destroy", "maus_comm_info",
     "maus_comm_allgather_records", "maus_comm_allgather_rows", "maus_comm_bcast", "maus_comm_bcast_eigvecs", "maus_comm_set_matrix", "maus_comm_stats",
@@ -32,7 +33,7 @@ POP_X, POP_U, POP_W, POP_Y = 0, 1, 2, 3
 KIND_EIG, KIND_LINEAR, KIND_SVD = 1, 2, 3
 PERT_NONE, PERT_UNIFORM, PERT_MT19937 = 0, 1, 2
 KC_NAMES = ["zgemm", "lu_panel", "trsm", "laswp", "build_h", "backsolve", "vector",
-            "zgemm_k128", "zgemm_k64", "zgemm_k32", "zgemm_k16", "spmm", "band"]
+            "zgemm_k128", "zgemm_k64", "zgemm_k32", "zgemm_k16", "spmm", "band", "lanczos"]
 SPMM_SCHEDULES = {0: None, 1: "rows", 2: "wave"}     # maus_matrix_is_sparse: dense / lane per row / wave per row
 
 
@@ -115,6 +116,13 @@ def load_library():
         "maus_profile_read": ([vp, C.c_int, ip, dp, dp, dp], C.c_int),
         "maus_sync": ([vp], C.c_int),
         "maus_mt19937_jump": ([vp, i32p, C.c_uint64], C.c_int),
+        "maus_lanczos_begin": ([vp, vp, C.c_int], C.c_int),
+        "maus_lanczos_inject": ([vp, C.c_int, vp], C.c_int),
+        "maus_lanczos_extend": ([vp, C.c_int, C.c_int, C.c_double, vp, vp], C.c_int),
+        "maus_lanczos_restart": ([vp, vp, C.c_int, C.c_int], C.c_int),
+        "maus_lanczos_finish": ([vp, vp, C.c_int, C.c_int], C.c_int),
+        "maus_herm_match_rows": ([vp, vp, C.c_int, vp, vp], C.c_int),
+        "maus_get_ritz_rows": ([vp, vp, C.c_int, C.c_int], C.c_int),
         "maus_sparse_max_n": ([], C.c_int),
         "maus_band_prepare": ([vp, vp, C.c_int, ip, ip], C.c_int),
         "maus_band_reserve": ([vp, C.c_int, ip], C.c_int),
@@ -486,6 +494,51 @@ class Context:
         nrm = np.empty(s.shape[0], dtype=np.float64)
         self._ck(self.lib.maus_herm_match(self.h, _ptr(s), s.shape[0], _ptr(idx), _ptr(nrm)), "maus_herm_match")
         return idx, nrm
+
+    # -- thick-restart Lanczos of the sparse Hermitian shortcut (csrc/lanczos.hip) ---------------------------------------
+    def lanczos_begin(self, v0, ncv):
+        """Room for a basis of ncv + 1 rows on the device; row 0 = v0 / ||v0||."""
+        v = _c128(v0, (self.rows,))
+        self._ck(self.lib.maus_lanczos_begin(self.h, _ptr(v), int(ncv)), "maus_lanczos_begin")
+
+    def lanczos_inject(self, j, v):
+        """Row j = v, orthogonalised against rows 0 .. j - 1 and normalised (continuation after a breakdown)."""
+        v = _c128(v, (self.rows,))
+        self._ck(self.lib.maus_lanczos_inject(self.h, int(j), _ptr(v)), "maus_lanczos_inject")
+
+    def lanczos_extend(self, j0, j1, tol_abs):
+        """Lanczos steps j0 .. j1 - 1 with full reorthogonalisation -> (alpha[j1 - j0], beta[j1 - j0]); a step whose beta
+        is not above tol_abs leaves a zero row."""
+        alpha = np.empty(j1 - j0, dtype=np.float64)
+        beta = np.empty(j1 - j0, dtype=np.float64)
+        self._ck(self.lib.maus_lanczos_extend(self.h, int(j0), int(j1), float(tol_abs), _ptr(alpha), _ptr(beta)),
+                 "maus_lanczos_extend")
+        return alpha, beta
+
+    def lanczos_restart(self, S):
+        """Thick restart: rows 0 .. keep - 1 <- S^T rows 0 .. m - 1 for the real S[m, keep]; row keep <- row m."""
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        self._ck(self.lib.maus_lanczos_restart(self.h, _ptr(S), S.shape[0], S.shape[1]), "maus_lanczos_restart")
+
+    def lanczos_finish(self, S):
+        """The k Ritz rows S^T rows 0 .. m - 1 for the real S[m, k] stay resident (herm_match_rows); the basis is freed."""
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        self._ck(self.lib.maus_lanczos_finish(self.h, _ptr(S), S.shape[0], S.shape[1]), "maus_lanczos_finish")
+        self._ritz_k = int(S.shape[1])
+
+    def herm_match_rows(self, slots):
+        s = self._slots(slots)
+        idx = np.empty(s.shape[0], dtype=np.int32)
+        nrm = np.empty(s.shape[0], dtype=np.float64)
+        self._ck(self.lib.maus_herm_match_rows(self.h, _ptr(s), s.shape[0], _ptr(idx), _ptr(nrm)), "maus_herm_match_rows")
+        return idx, nrm
+
+    def get_ritz_rows(self):
+        """The resident Ritz rows, k x n, ascending in lambda."""
+        k = int(getattr(self, "_ritz_k", 0))
+        out = np.empty((k, self.rows), dtype=np.complex128)
+        self._ck(self.lib.maus_get_ritz_rows(self.h, _ptr(out), k, self.rows), "maus_get_ritz_rows")
+        return out
 
     def gram(self, which, slots, length):
         """G[i, j] = np.vdot(x_i, x_j) for the rows `slots` of population array `which` (first `length` entries)."""

@@ -265,6 +265,7 @@ int maus_ctx_destroy(maus_ctx* c) {
     for (void* p : ptrs) if (p) (void)hipFree(p);
     maus_csr_free(c->Acsr); maus_csr_free(c->AHcsr);
     maus_band_drop(c);
+    maus_lanczos_drop(c);
     if (c->Adiag) (void)hipFree(c->Adiag);
     if (c->pin) (void)hipHostFree(c->pin);
     if (c->pin_small) (void)hipHostFree(c->pin_small);
@@ -320,6 +321,7 @@ static void free_population(maus_ctx* c) {
 static void csr_drop(maus_ctx* c) {
     maus_csr_free(c->Acsr); maus_csr_free(c->AHcsr);
     maus_band_drop(c);
+    maus_lanczos_drop(c);
     if (c->Adiag) { (void)hipFree(c->Adiag); c->Adiag = nullptr; }
     c->csr = false; c->csr_sched = 0;
 }

@@ -51,9 +51,17 @@ int maus_gmres_run(maus_ctx* ctx, const int* slots, int count, const double* shi
                    const int32_t* use_jacobi, double rtol, int restart, int maxiter, int32_t* info_out, int32_t* inner_out, int32_t* status,
                    const c128* Hdense, long ldh, long strideH, int32_t* jacobi_out);
 void maus_band_drop(maus_ctx* c);            // band.hip: the ordering and workspace of the previous sparse matrix
+void maus_lanczos_drop(maus_ctx* c);         // lanczos.hip: the basis and the Ritz rows of the previous sparse matrix
 int maus_jacobi_check_run(maus_ctx* ctx, int count, const double* shift, const double* psi, int32_t* ok);
 
 // ---- context ---------------------------------------------------------------------------
+// Thick-restart Lanczos of the sparse Hermitian shortcut (lanczos.hip): the basis B (ncv + 1 rows of n) with its reduction
+// buffers lives from maus_lanczos_begin to maus_lanczos_finish; the k Ritz rows R stay until the matrix changes
+struct MausLanczos {
+    c128 *B = nullptr, *R = nullptr, *part = nullptr, *h = nullptr;
+    double *npart = nullptr, *ab = nullptr, *S = nullptr; int* ident = nullptr;
+    int n = 0, ncv = 0, nblk = 0, k = 0;
+};
 struct ProfRec { int klass; hipEvent_t e0, e1; double flops, bytes, weight; };
 
 struct maus_ctx {
@@ -68,6 +76,7 @@ struct maus_ctx {
     int* band_perm = nullptr; int* band_iperm = nullptr; int band_n = 0, band_kl = -1, band_ku = -1;
     c128* band_ab = nullptr; c128* band_x = nullptr; int *band_ipiv = nullptr, *band_info = nullptr, *band_flags = nullptr;
     int band_g = 0, band_allocs = 0; bool band_at_limit = false; unsigned long long band_ws_key = 0;
+    MausLanczos lz;
     c128* b = nullptr; int bn = 0;                  // rhs
     c128* V = nullptr; int vn = 0;                  // eigenvectors (Hermitian shortcut)
     c128* hq = nullptr; c128* htau = nullptr; int hqn = 0;   // Householder reflectors of maus_herm_tridiag, until the back-transformation (herm.hip)

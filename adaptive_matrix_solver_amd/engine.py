@@ -248,6 +248,91 @@ def sparse_direct_mode(mode):
     return mode
 
 
+SPARSE_EIGSH_MODES = ("auto", "dense", "lanczos")
+
+
+def sparse_eigsh_mode(mode):
+    """The `sparse_eigsh` keyword: an explicit value, else MAUS_SPARSE_EIGSH, else 'auto'."""
+    mode = mode if mode is not None else os.environ.get("MAUS_SPARSE_EIGSH", "auto")
+    if mode not in SPARSE_EIGSH_MODES:
+        raise ValueError(f"sparse_eigsh must be one of {SPARSE_EIGSH_MODES}, not {mode!r}")
+    return mode
+
+
+def eigsh_parameters(n: int):
+    """(k, ncv) of the reference's eigsh call (AMS:188-189) as SciPy completes it: k = min(6, N - 1), at least 1;
+    ncv = min(n, max(2 k + 1, 20))."""
+    k = min(6, n - 1)
+    if k < 1 and n >= 1:
+        k = 1
+    return k, min(n, max(2 * k + 1, 20))
+
+
+def thick_restart_lanczos(ctx, n, k, ncv, tol, breakdown, max_restarts, v0, fresh):
+    """The k eigenpairs of largest |lambda| of the Hermitian matrix bound to `ctx`, by thick-restart Lanczos (Wu and Simon) with
+    ARPACK's parameters and acceptance rule as SciPy's eigsh sets them (which='LM'): a Ritz pair (theta, y) of the wanted set is
+    accepted when |beta_m s_{m,i}| <= tol max(eps^(2/3), |theta|).  Everything of length n happens behind `ctx` (lanczos_begin /
+    _extend / _inject / _restart / _finish: csrc/lanczos.hip on the device); this loop solves the projected ncv x ncv problem,
+    chooses, tests and counts, once per restart.
+
+    A step whose beta is not above `breakdown` completes an invariant subspace: if it holds at least k pairs they are the
+    result, otherwise the run continues from `fresh()`, orthogonalised against the basis.  Returns a dict: converged, theta (the
+    k values ascending; their Ritz vectors are left resident in the same order), restarts, products, nconv."""
+    import scipy.linalg as sla
+    eps23 = np.finfo(np.float64).eps ** (2.0 / 3.0)
+    out = {"converged": False, "theta": None, "restarts": 0, "products": 0, "nconv": 0, "k": k, "ncv": ncv, "error": None}
+    ctx.lanczos_begin(v0, ncv)
+    T = np.zeros((ncv, ncv))
+    j0 = 0
+    while True:
+        m, beta_m, complete, j = ncv, 0.0, False, j0
+        while j < ncv:
+            alpha, beta = ctx.lanczos_extend(j, ncv, breakdown)
+            out["products"] += ncv - j
+            if not (np.isfinite(alpha).all() and np.isfinite(beta).all()):
+                ctx.lanczos_finish(np.zeros((ncv, 0)))
+                out["error"] = "the Lanczos recurrence left non-finite coefficients"
+                return out
+            small = np.nonzero(~(beta > breakdown))[0]
+            last = j + (int(small[0]) if small.size else ncv - 1 - j)        # last valid step of this stretch
+            for i in range(j, last + 1):
+                T[i, i] = alpha[i - j]
+                if i + 1 < ncv:
+                    T[i, i + 1] = T[i + 1, i] = beta[i - j] if i < last or not small.size else 0.0
+            if not small.size:
+                beta_m, j = float(beta[-1]), ncv
+            elif last == ncv - 1:
+                j = ncv                                                      # beta_m = 0: the whole basis is invariant
+            elif last + 1 >= k:
+                m, complete = last + 1, True                                 # rows 0 .. last span an invariant subspace with >= k pairs
+                break
+            else:
+                ctx.lanczos_inject(last + 1, fresh())
+                j = last + 1
+        theta, S = sla.eigh(T[:m, :m])
+        res = np.abs(beta_m * S[m - 1, :])
+        order = np.argsort(-np.abs(theta), kind="stable")
+        wanted = order[:k]
+        ok = res[wanted] <= tol * np.maximum(eps23, np.abs(theta[wanted]))
+        out["nconv"] = int(ok.sum())
+        if complete or ok.all():
+            sel = np.sort(wanted)                                            # eigh returns theta ascending
+            ctx.lanczos_finish(S[:, sel])
+            out["converged"], out["theta"] = True, np.ascontiguousarray(theta[sel], dtype=np.float64)
+            return out
+        if out["restarts"] >= max_restarts:
+            ctx.lanczos_finish(np.zeros((ncv, 0)))
+            return out
+        keep = min(k + min(out["nconv"], (ncv - k) // 2), ncv - 1)           # ARPACK's kev + min(nconv, np / 2)
+        kept = np.sort(order[:keep])
+        ctx.lanczos_restart(S[:, kept])
+        T[:] = 0.0
+        T[np.arange(keep), np.arange(keep)] = theta[kept]
+        T[keep, :keep] = T[:keep, keep] = beta_m * S[m - 1, kept]
+        j0 = keep
+        out["restarts"] += 1
+
+
 def _is_sparse_matrix(A) -> bool:
     try:
         import scipy.sparse as sp
@@ -262,7 +347,7 @@ class DeviceEngine:
     _default = None
 
     def __init__(self, device: int = 0, pert_mode: str = "auto", gmres_compat: str = "rtol",
-                 comm=None, ctx=None, eigh_mode: str = "auto", sparse_mode=None, sparse_direct=None):
+                 comm=None, ctx=None, eigh_mode: str = "auto", sparse_mode=None, sparse_direct=None, sparse_eigsh=None):
         self.ctx = ctx if ctx is not None else _cabi.Context(device)
         cap_blas_threads()
         # Hermitian eigendecomposition (AMS:161), once per matrix: 'host' = scipy.linalg.eigh, the reference's call, (lambda, V)
@@ -279,6 +364,14 @@ class DeviceEngine:
         # 'band' runs the band LU in the ordering of band.band_order, 'auto' the first up to maus_lu_max_n() and the second
         # above.  MAUS_SPARSE_DIRECT sets the default.  Chosen once per bound matrix (_band).
         self.sparse_direct = sparse_direct_mode(sparse_direct)
+        # sparse Hermitian shortcut (AMS:186-216): 'dense' = one scipy.linalg.eigh of A.toarray() per matrix, 'lanczos' =
+        # thick-restart Lanczos on the CSR matrix on the device, 'auto' the first up to maus_lu_max_n() and the second above.
+        # MAUS_SPARSE_EIGSH sets the default.
+        self.sparse_eigsh = sparse_eigsh_mode(sparse_eigsh)
+        self.lanczos_max_restarts = None        # None: SciPy's maxiter = 10 n
+        self.lanczos_stats = None               # the last Lanczos run: restarts, products, converged, ...
+        self._ritz_rows = False                 # the shortcut's vectors are resident as k Ritz rows (not an n x n matrix)
+        self._eig_noconv = False                # the cached failure of the shortcut is a no-convergence report (AMS:211-212)
         self._band = False                      # the bound sparse matrix takes the band solve
         self._band_ready = False                # ... and its ordering is on the device (prepared at the first band solve)
         self._band_cache = None                 # (matrix obj, perm, kl, ku) of band_shape
@@ -320,6 +413,9 @@ class DeviceEngine:
         if A is self._bound and not (collective and solo):
             return
         shape_changed = (self.ctx.rows, self.ctx.cols) != tuple(A.shape)
+        if self._ritz_rows:                     # the Ritz rows go with the matrix they belong to
+            self._eig_cache = None
+            self._ritz_rows = False
         if _is_sparse_matrix(A):
             if self.sparse_mode != "device":
                 raise NotImplementedError("sparse problem matrices need sparse_mode='device' (or MAUS_SPARSE=device)")
@@ -358,6 +454,16 @@ class DeviceEngine:
         if self.sparse_direct == "band":
             return True
         if self.sparse_direct == "dense":
+            return False
+        lu_max = getattr(self.ctx, "lu_max_n", None)
+        return n > (lu_max() if lu_max is not None else 16384)
+
+    def uses_lanczos(self, n: int) -> bool:
+        """Whether the sparse Hermitian shortcut of an n x n matrix runs the device Lanczos (sparse_eigsh; 'auto': above
+        maus_lu_max_n())."""
+        if self.sparse_eigsh == "lanczos":
+            return True
+        if self.sparse_eigsh == "dense":
             return False
         lu_max = getattr(self.ctx, "lu_max_n", None)
         return n > (lu_max() if lu_max is not None else 16384)
@@ -659,6 +765,8 @@ class DeviceEngine:
             self.ctx.svd_commit([c._slot for c in own])
 
     def d_herm_match(self, cands):
+        if self._ritz_rows:                     # sparse matrix, never sharded: the k resident Ritz rows
+            return self.ctx.herm_match_rows([c._slot for c in cands])
         mine = self._mine(cands)
         if mine is None:
             return self.ctx.herm_match([c._slot for c in cands])
@@ -732,7 +840,7 @@ class DeviceEngine:
 
         todo = list(cands)
         if kind == ProblemType.EIGENVALUE and know.get("is_hermitian", False):   # AMS:155
-            todo = self._hermitian(todo, A, slots)
+            todo = self._hermitian(todo, A, slots, strat)
             if todo:
                 slots = self._slots(todo)
         if todo:
@@ -835,6 +943,19 @@ class DeviceEngine:
         comm.bcast_eigvecs(self.ctx, evecs, n)
         self._eig_cache = (A, ev)
 
+    @staticmethod
+    def _eigsh_refusal(A):
+        """The TypeError text SciPy raises where ARPACK cannot run (k >= N - 1 for complex input, which eigsh hands to eigs;
+        k >= N for real input), or None."""
+        n = A.shape[0]
+        k, _ = eigsh_parameters(n)
+        if np.issubdtype(A.dtype, np.complexfloating) and k >= n - 1:
+            return ("Cannot use scipy.linalg.eig for sparse A with k >= N - 1. "
+                    "Use scipy.linalg.eig(A.toarray()) or reduce k.")
+        if k >= n:
+            return "Cannot use scipy.linalg.eigh for sparse A with k >= N. Use scipy.linalg.eigh(A.toarray()) or reduce k."
+        return None
+
     def _sparse_eigh_k(self, A):
         """The sparse Hermitian shortcut's decomposition (AMS:186-216), once per matrix: eigsh(A, k=min(6, N-1), which='LM')
         per candidate becomes the k eigenpairs of largest |lambda| of one dense eigh.  Columns kept in ascending order of
@@ -843,14 +964,10 @@ class DeviceEngine:
         k >= N - 1 for complex input (eigs), k >= N for real input)."""
         import scipy.linalg as sla
         n = A.shape[0]
-        k = min(6, n - 1)
-        if k < 1 and n >= 1:
-            k = 1
-        if np.issubdtype(A.dtype, np.complexfloating) and k >= n - 1:
-            return None, ("Cannot use scipy.linalg.eig for sparse A with k >= N - 1. "
-                          "Use scipy.linalg.eig(A.toarray()) or reduce k.")
-        if k >= n:
-            return None, "Cannot use scipy.linalg.eigh for sparse A with k >= N. Use scipy.linalg.eigh(A.toarray()) or reduce k."
+        k, _ = eigsh_parameters(n)
+        err = self._eigsh_refusal(A)
+        if err is not None:
+            return None, err
         evals, evecs = sla.eigh(A.toarray())
         keep = np.sort(np.argsort(np.abs(evals), kind="stable")[-k:])
         V = np.zeros((n, n), dtype=np.complex128)
@@ -858,16 +975,51 @@ class DeviceEngine:
         self.ctx.set_eigvecs(V)
         return np.ascontiguousarray(evals[keep], dtype=np.float64), None
 
-    def _hermitian(self, cands, A, slots):
+    def _sparse_lanczos_k(self, A, v0, tol):
+        """The same k eigenpairs without a dense copy of A: thick_restart_lanczos on the bound CSR matrix, the k Ritz
+        vectors left resident as k rows of n, ascending in lambda.  v0 as AMS:192: the candidate's vector if its norm exceeds
+        1e-8, otherwise a fixed vector.  That vector and the continuation vectors after a breakdown come from a private
+        generator: eigsh draws from neither global stream (v0 is given, ARPACK's own generator covers the rest).  Returns
+        (eigenvalues, None) or (None, the text of the no-convergence report)."""
+        n = A.shape[0]
+        k, ncv = eigsh_parameters(n)
+        rng = np.random.default_rng(0x4C616E637A6F73)
+        if v0 is None or v0.shape[0] != n or not np.linalg.norm(v0) > 1e-8:
+            v0 = rng.standard_normal(n) + 1j * rng.standard_normal(n)
+        anorm = float(abs(A).sum(axis=0).max()) if A.nnz else 0.0            # ||A||_1 >= ||T||: known before the first sweep
+        limit = self.lanczos_max_restarts if self.lanczos_max_restarts is not None else 10 * n
+        run = thick_restart_lanczos(self.ctx, n, k, ncv, tol, np.finfo(np.float64).eps * anorm, limit, v0,
+                                    lambda: rng.standard_normal(n) + 1j * rng.standard_normal(n))
+        self.lanczos_stats = run
+        if run["converged"]:
+            return run["theta"], None
+        return None, run["error"] or (f"ARPACK error -1: No convergence ({run['restarts'] + 1} iterations, "
+                                      f"{run['nconv']}/{k} eigenvectors converged)")
+
+    def _hermitian(self, cands, A, slots, strat=None):
         from .solver import SolutionCandidate
         S = SolutionCandidate.State
         if self._sparse:
             if self._eig_cache is None or self._eig_cache[0] is not A:
-                evals, err = self._sparse_eigh_k(A)
+                n = A.shape[0]
+                err = self._eigsh_refusal(A)
+                self._eig_noconv = False
+                if err is not None:
+                    evals = None
+                elif self.uses_lanczos(n):
+                    tol = (strat or {}).get("convergence_tolerance", 1e-8) / 100          # AMS:194
+                    evals, err = self._sparse_lanczos_k(A, self.ctx.pop_get(POP_X, [int(slots[0])], n)[0], tol)
+                    self._ritz_rows = evals is not None
+                    self._eig_noconv = evals is None
+                else:
+                    evals, err = self._sparse_eigh_k(A)
                 self._eig_cache = (A, evals, err)
             if self._eig_cache[1] is None:
                 for c in cands:
-                    print(f"Candidate {c.id}: Unexpected error during sparse Hermitian solve: {self._eig_cache[2]}. Falling back.")
+                    if self._eig_noconv:                                                   # AMS:211-212
+                        print(f"Candidate {c.id}: Sparse Hermitian solver (eigsh) failed to converge: {self._eig_cache[2]}. Falling back.")
+                    else:
+                        print(f"Candidate {c.id}: Unexpected error during sparse Hermitian solve: {self._eig_cache[2]}. Falling back.")
                 return cands
         elif self._eig_cache is not None and self._eig_cache[0] is not A and self._eig_cache[0].shape == A.shape \
                 and not _is_sparse_matrix(self._eig_cache[0]) and np.array_equal(self._eig_cache[0], A):

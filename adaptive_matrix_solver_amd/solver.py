@@ -31,7 +31,7 @@ import numpy as np
 from . import _cabi
 from ._cabi import POP_U, POP_X
 from .candstore import C_NP as _C_NP, C_PY as _C_PY, EXACT as _EXACT, F_NP as _F_NP, F_PY as _F_PY, HREF as _HREF, MISSING as _MISSING
-from .engine import DIRECT, GMRES, DeviceEngine, _advance_numpy_stream, sparse_direct_mode
+from .engine import DIRECT, GMRES, DeviceEngine, _advance_numpy_stream, sparse_direct_mode, sparse_eigsh_mode
 
 
 class ProblemType(Enum):                     # AMS:10-13
@@ -101,6 +101,40 @@ def _sparse_mode(mode):
     if mode not in SPARSE_MODES:
         raise ValueError(f"sparse_mode must be one of {SPARSE_MODES}, not {mode!r}")
     return mode
+
+
+SPARSE_HERMITIAN_CHECKS = ("reference", "sparse")
+
+
+def _sparse_hermitian_check(mode):
+    """The `sparse_hermitian_check` keyword: 'reference' (default; AMS:386-396 as it is) or 'sparse'."""
+    mode = mode if mode is not None else "reference"
+    if mode not in SPARSE_HERMITIAN_CHECKS:
+        raise ValueError(f"sparse_hermitian_check must be one of {SPARSE_HERMITIAN_CHECKS}, not {mode!r}")
+    return mode
+
+
+def sparse_symmetry_verdicts(M):
+    """(is_hermitian, is_complex_symmetric) of a square scipy.sparse matrix as AMS:394-395 decides them on the dense copy --
+    np.allclose(D, D.conj().T) and np.allclose(D, D.T) -- computed on the stored entries alone: every position stored in M or
+    in its transpose is compared by np.allclose itself (|a - b| <= 1e-8 + 1e-5 |b|, b the transposed entry; a position stored on
+    one side only counts as 0 on the other; NaN anywhere gives False; equal infinities are close), every other position is
+    0 against 0.  O(nnz log nnz) time and memory at any n."""
+    import scipy.sparse as sp
+    C = sp.coo_matrix(M)
+    C.sum_duplicates()                                   # todense() adds duplicates too
+    n = np.int64(C.shape[1])
+    r, c, a = C.row.astype(np.int64), C.col.astype(np.int64), C.data
+    here, there = r * n + c, c * n + r                   # positions of the entries of M and of M^T
+    keys = np.union1d(here, there)
+    A = np.zeros(keys.shape[0], dtype=a.dtype)
+    A[np.searchsorted(keys, here)] = a
+    verdicts = []
+    for conj in (True, False):
+        B = np.zeros(keys.shape[0], dtype=a.dtype)
+        B[np.searchsorted(keys, there)] = a.conj() if conj else a
+        verdicts.append(bool(np.allclose(A, B)))
+    return verdicts[0], verdicts[1]
 
 
 def _reject_sparse(what):
@@ -716,9 +750,14 @@ class MAUS_Solver:
     def __init__(self, problem_matrix, problem_type, b_vector=None, initial_num_candidates=None,
                  global_convergence_tol=1e-8, *, device=0, pert_mode="auto", gmres_compat="rtol",
                  record_history=None, comm=None, quiet=False, engine=None, gram_min=8, cond_exact_max=1024,
-                 diag_info=None, eigh_mode="auto", sparse_mode=None, sparse_direct=None):
+                 diag_info=None, eigh_mode="auto", sparse_mode=None, sparse_direct=None, sparse_eigsh=None,
+                 sparse_hermitian_check=None):
         sparse_mode = _sparse_mode(sparse_mode)
         sparse_direct = sparse_direct_mode(sparse_direct)
+        sparse_eigsh = sparse_eigsh_mode(sparse_eigsh)
+        # symmetry test of a sparse matrix in the start-up diagnostics: 'reference' = AMS:386-396 (dense copy, given up above
+        # n^2 = 1e7), 'sparse' = the same two verdicts from the stored entries at any n (opt-in)
+        self._sparse_hermitian_check = _sparse_hermitian_check(sparse_hermitian_check)
         if _is_sparse(problem_matrix):
             if sparse_mode != "device":
                 _reject_sparse("scipy.sparse matrices")
@@ -738,7 +777,8 @@ class MAUS_Solver:
         # code never passes it, and DeviceEngine() raises if libmaus_hip / the device is missing
         self.engine = engine if engine is not None else DeviceEngine(device=device, pert_mode=pert_mode,
                                                                      gmres_compat=gmres_compat, comm=comm, eigh_mode=eigh_mode,
-                                                                     sparse_mode=sparse_mode, sparse_direct=sparse_direct)
+                                                                     sparse_mode=sparse_mode, sparse_direct=sparse_direct,
+                                                                     sparse_eigsh=sparse_eigsh)
         # `diag_info`: start-up diagnostics of the same matrix taken from an earlier solver (bench side runs)
         if diag_info is not None:
             self.diag_info = dict(diag_info)
@@ -846,7 +886,9 @@ class MAUS_Solver:
             diag_info["is_sparse_init"] = True
             try:
                 if matrix.shape[0] == matrix.shape[1]:
-                    if matrix.shape[0] * matrix.shape[1] > 1e7:
+                    if getattr(self, "_sparse_hermitian_check", "reference") == "sparse":
+                        diag_info["is_hermitian"], diag_info["is_complex_symmetric"] = sparse_symmetry_verdicts(matrix)
+                    elif matrix.shape[0] * matrix.shape[1] > 1e7:
                         print("Warning: Sparse matrix too large for dense conversion in property diagnosis. "
                               "Assuming False for Hermitian/Symmetric.")
                     else:

@@ -264,6 +264,34 @@ int maus_herm_tridiag_eig(maus_ctx* ctx, const double* d, const double* e, int n
  * the reporting prologue (AMS:559 / 567) */
 int maus_herm_tridiag_eigvals(maus_ctx* ctx, const double* d, const double* e, int n, double* w_out);
 
+/* Sparse Hermitian shortcut at any size                            AMS:186-216:
+ * eigsh(A, k = min(6, N - 1), which = 'LM', v0 = v_k, tol) is ARPACK's implicitly restarted Lanczos; here it is thick-restart
+ * Lanczos (Wu and Simon: the same subspaces for a Hermitian operator) on the bound CSR matrix (maus_set_matrix_csr, square;
+ * anything else is an error).  The basis lives on the device as ncv + 1 rows of n; the host solves the projected ncv x ncv
+ * problem once per restart and decides (engine.py).  One synchronisation per restart, none per Lanczos step: maus_lanczos_restart
+ * returns without one, the sweep that follows it (maus_lanczos_extend) ends in it.
+ *   maus_lanczos_begin    room for the basis (1 <= ncv <= min(n, 32)); row 0 = v0_c128[n] / ||v0||.
+ *   maus_lanczos_inject   row j = v_c128[n], orthogonalised against rows 0 .. j - 1 (classical Gram-Schmidt, twice) and
+ *                         normalised: the vector a run continues from after a breakdown.
+ *   maus_lanczos_extend   steps j = j0 .. j1 - 1 (j1 <= ncv): row j+1 = A row j, orthogonalised against rows 0 .. j (twice),
+ *                         alpha_out[j - j0] = Re(row j . A row j), beta_out[j - j0] = the norm that is left, row j+1 scaled by
+ *                         1 / beta.  A step whose beta is not above tol_abs (breakdown, or non-finite data) leaves a zero row.
+ *   maus_lanczos_restart  rows 0 .. keep - 1 <- S^T rows 0 .. m - 1 (s_real[m][keep], the Ritz vectors that are kept), row
+ *                         keep <- row m (the residual vector), 1 <= keep < m <= ncv.
+ *   maus_lanczos_finish   the k Ritz rows S^T rows 0 .. m - 1 (s_real[m][k], k <= min(m, 8)), orthonormalised, stay resident as k rows
+ *                         of n for maus_herm_match_rows until the matrix changes; the basis is freed.  k = 0 (a run that did
+ *                         not converge) frees the basis and keeps nothing.
+ *   maus_herm_match_rows  AMS:197-202, maus_herm_match for the resident rows: scores vdot(X[slot], row j), the first largest
+ *                         |score| as np.argmax, X[slot] <- row j / ||row j||.  idx_out[count], norm_out[count].
+ *   maus_get_ritz_rows    the k resident rows on the host (rows_c128_out[k][n]; tests, reports). */
+int maus_lanczos_begin(maus_ctx* ctx, const double* v0_c128, int ncv);
+int maus_lanczos_inject(maus_ctx* ctx, int j, const double* v_c128);
+int maus_lanczos_extend(maus_ctx* ctx, int j0, int j1, double tol_abs, double* alpha_out, double* beta_out);
+int maus_lanczos_restart(maus_ctx* ctx, const double* s_real, int m, int keep);
+int maus_lanczos_finish(maus_ctx* ctx, const double* s_real, int m, int k);
+int maus_herm_match_rows(maus_ctx* ctx, const int* slots, int count, int32_t* idx_out, double* norm_out);
+int maus_get_ritz_rows(maus_ctx* ctx, double* rows_c128_out, int k, int n);
+
 /* Gram block of candidate vectors for the distinctness / redundancy tests      AMS:432-437, 443-451, 509-520:
  * out[i*count + j] = vdot(x_i, x_j) = sum_k conj(x_i[k]) x_j[k] over the first `len` entries of rows `slots`
  * of population array `which` (MAUS_POP_X / MAUS_POP_U).  Replaces the reference's pairwise np.vdot calls
@@ -344,7 +372,8 @@ int maus_timer_start(maus_ctx* ctx);
 int maus_timer_stop(maus_ctx* ctx, float* ms_out);
 /* Per-kernel-class accounting (event pairs around each launch of the class while enabled).
  * classes: 0 zgemm (LU trailing update with K>=256 / A@X), 1 lu_panel, 2 trsm, 3 (unused since round 2: row-swap sweeps), 4 build_H, 5 backsolve,
- * 6 vector ops, 7..10 zgemm inside the LU recursion with K = 128 / 64 / 32 / 16 */
+ * 6 vector ops, 7..10 zgemm inside the LU recursion with K = 128 / 64 / 32 / 16, 11 CSR products, 12 band solves,
+ * 13 lanczos (reorthogonalisation, restart, match of the sparse Hermitian shortcut) */
 /* on = 1: event pairs around every launch of every class; on = 2: around the K>=256 zgemm launches only (class 0;
  * long kernels, so cheap enough for a timed region -- full bracketing costs 3-5 % of throughput; MAUS_PROF_STRIDE
  * can thin them out, each sample then stands for `stride` launches); 0: off */
