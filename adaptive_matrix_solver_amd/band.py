@@ -42,6 +42,20 @@ def band_order(A) -> tuple[np.ndarray, int, int]:
     return rcm, kl_r, ku_r
 
 
-def band_bytes_per_solve(n: int, kl: int, ku: int) -> int:
-    """Device memory of one band solve: the band storage, the right-hand side and the pivots (csrc/band.hip)."""
-    return 16 * ((2 * kl + ku + 1) * n + n) + 4 * n
+BLOCKED_NB = 16                 # block width of the blocked method (8 where kl + 16 > 1024), csrc/band.hip
+BLOCKED_MIN_KL = 16             # narrower bands run the column kernel under sparse_direct='blocked' too ...
+BLOCKED_MAX_KL = 1024           # ... and so do bands too tall for its one-workgroup panel
+
+
+def runs_blocked(kl: int, ku: int) -> bool:
+    """Whether the blocked method takes a (kl, ku) band when it is selected (band_runs_blocked in csrc/band.hip)."""
+    return BLOCKED_MIN_KL <= kl <= BLOCKED_MAX_KL
+
+
+def band_bytes_per_solve(n: int, kl: int, ku: int, blocked: bool = False) -> int:
+    """Device memory of one band solve: the band storage, the right-hand side and the pivots (csrc/band.hip); with
+    `blocked`, and a band the blocked method takes, its panel of L and its reach as well."""
+    per = 16 * ((2 * kl + ku + 1) * n + n) + 4 * n
+    if blocked and runs_blocked(kl, ku):
+        per += 16 * (kl + BLOCKED_NB) * BLOCKED_NB + 4
+    return per

@@ -15,8 +15,13 @@
 // maximum with the lowest index among equals: there is no summation order that the workgroup size or the batch could change.
 // The workgroup size is picked from (kl, ku) alone and only decides who does what.  A candidate's W row is therefore
 // bit-identical alone, in any batch and in any chunking of the workspace (DESIGN §9's rule).
+//
+// That is the column kernel, the default.  maus_band_set_method(ctx, 1) selects the blocked method further down (zgbtrf's
+// schedule, every step a launch over (matrix, tile)) for bands with BLK_MIN_KL <= kl <= BLK_MAX_KL; same storage, build kernel,
+// pivot rule and status contract.
 #include "ctx.h"
 #include <climits>
+#include <utility>
 
 namespace {
 
@@ -187,6 +192,298 @@ band_back_kernel(BandArgs a, c128* __restrict__ out, long ldo, const int* __rest
     if (tid == 0 && bad) atomicOr(&a.flags[g], 2);
 }
 
+// ---- the blocked method (maus_band_set_method(ctx, 1)) ------------------------------------------------------
+// zgbtrf's schedule, BNB columns at a time, every step a launch over (matrix, tile):
+//   panel    one workgroup per matrix holds the (kl + BNB) x BNB slice in registers (thread-owned rows, the pivot row and the
+//            row it displaces through LDS, two LDS barriers per column).  Interchanges are applied across the whole slice, as
+//            zgbtrf does inside a block, so L comes out in the block's final row order; it goes to a dense work array
+//            lw[matrix][(kl + BNB) x BNB] -- nothing reads L after its own block step, because the right-hand side is a
+//            column of the update below -- and U11 goes back into the band.
+//   update   one workgroup per BTC columns right of the panel, up to the reach ju of the pivot rows (zgbtrf's ju), plus one
+//            for the right-hand side: the tile goes through LDS once -- the BNB interchanges, U12 = L11^-1 A12, then
+//            A22 -= L21 U12 with the thread's row of L21 in registers -- and back.  Every element is owned by one thread and
+//            its BNB multiply-subtracts run in column order: no sum has an order that the grid or the batch could change.
+//   back     U x = y in blocks of BNB by one workgroup per matrix: the BNB x BNB triangle in LDS, then one pass over the
+//            kl + ku rows above it.
+// The block width and the workgroup sizes follow from (kl, ku) alone.
+constexpr int BNB = 16;                                 // columns per block step ...
+constexpr int BNB_TALL = 8;                             // ... and where kl + BNB rows no longer fit two per thread of the panel
+constexpr int BTC = 4;                                  // columns per update tile
+constexpr int BLK_MIN_KL = 16;                          // narrower bands run the column kernel ...
+constexpr int BLK_MAX_KL = 1024;                        // ... and so do bands too tall for the one-workgroup panel
+
+struct BlkArgs { c128* lw; int* ju; int lh; };          // lw: (lh x nb) column-major per matrix, lh = kl + nb; ju: reach so far
+
+bool band_runs_blocked(int method, int kl, int ku) { (void)ku; return method == 1 && kl >= BLK_MIN_KL && kl <= BLK_MAX_KL; }
+int band_nb(int kl, int ku) { (void)ku; return kl + BNB <= 1024 ? BNB : BNB_TALL; }
+
+// the fill-in rows of the band storage start at zero (zgbtf2 clears them column by column as it goes)
+__global__ void __launch_bounds__(256)
+band_zero_fill_kernel(BandArgs a)
+{
+    const int g = blockIdx.y;
+    const long per = (long)a.kl * a.n;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < per; e += (long)gridDim.x * 256)
+        a.ab[bix(a, g) + e % a.kl + e / a.kl * a.ldab] = cmake(0.0, 0.0);
+}
+
+// Panel of block step j0 on matrix blockIdx.x: columns j0 .. j0 + jb - 1, rows j0 .. j0 + H - 1.  Thread t owns the slice's
+// rows t, t + NT, ... (RP of them) in registers; the loop over the columns is unrolled so that every register index is static.
+// Pivot rule, ipiv and info as band_factor_kernel.
+template <int... I, class F>
+__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) { static_for_impl(std::make_integer_sequence<int, N>{}, f); }
+
+template <int NT, int RP, int NB>
+__global__ void __launch_bounds__(NT)
+band_panel_kernel(BandArgs a, BlkArgs w, int j0)
+{
+    constexpr int NW = NT / 64;
+    __shared__ double s_best[NW];
+    __shared__ int s_idx[NW];
+    __shared__ c128 s_piv[NB], s_top[NB];
+    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = a.n, kl = a.kl, ku = a.ku, kv = kl + ku, ldab = a.ldab;
+    c128* ab = a.ab + bix(a, g);
+    c128* lw = w.lw + (long)g * w.lh * NB;
+    int* ipiv = a.ipiv + (long)g * n;
+    const int jb = min(NB, n - j0), H = min(kl + jb, n - j0);
+    auto at = [&](int r, int j) -> c128& { return ab[r + (long)j * ldab]; };
+    c128 row[RP][NB];
+    static_for<RP>([&](auto mc) {
+        constexpr int m = decltype(mc)::value;
+        const int r = tid + m * NT;
+        static_for<NB>([&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            row[m][k] = (r < H && k < jb && r - k <= kl && k - r <= kv) ? at(kv + r - k, j0 + k) : cmake(0.0, 0.0);
+        });
+    });
+    int ju = w.ju[g], info = 0;
+    static_for<NB>([&](auto jc) {
+        constexpr int jj = decltype(jc)::value;
+        if (jj < jb) {
+            const int j = j0 + jj, km = min(kl, n - 1 - j);
+            double best = -1.0; int bidx = INT_MAX;
+            static_for<RP>([&](auto mc) {
+                constexpr int m = decltype(mc)::value;
+                const int r = tid + m * NT;
+                if (r >= jj && r <= jj + km) {
+                    const double v = cabs1(row[m][jj]);
+                    if (v > best) { best = v; bidx = r; }               // NaN never wins (izamax)
+                }
+            });
+            wave_argmax(best, bidx);
+            if (lane == 0) { s_best[wave] = best; s_idx[wave] = bidx; }
+            lds_barrier();
+            double mx = s_best[0]; int pr = s_idx[0];
+#pragma unroll
+            for (int v = 1; v < NW; ++v) {
+                if (s_best[v] > mx) { mx = s_best[v]; pr = s_idx[v]; }
+                else if (s_best[v] == mx) pr = min(pr, s_idx[v]);
+            }
+            if (pr == INT_MAX) pr = jj;
+            static_for<RP>([&](auto mc) {
+                constexpr int m = decltype(mc)::value;
+                const int r = tid + m * NT;
+                if (r == pr) static_for<NB>([&](auto kc) { s_piv[decltype(kc)::value] = row[m][decltype(kc)::value]; });
+                if (r == jj && pr != jj) static_for<NB>([&](auto kc) { s_top[decltype(kc)::value] = row[m][decltype(kc)::value]; });
+            });
+            lds_barrier();
+            const c128 piv = s_piv[jj];
+            const bool zero = piv.x == 0.0 && piv.y == 0.0;
+            if (zero && info == 0) info = j + 1;
+            // row jj of the slice is final: columns < jj of it are L11 in the block's row order, the others U11.  On a zero
+            // pivot nothing moves (zgbtf2), so the row that stays is the top one.
+            if (tid < jb) {
+                const c128 v = (zero && pr != jj) ? s_top[tid] : s_piv[tid];
+                if (tid < jj) lw[jj + (long)tid * w.lh] = v;
+                else if (tid - jj <= kv) at(kv + jj - tid, j0 + tid) = v;
+            }
+            if (tid == 0) ipiv[j] = j0 + pr + 1;                        // LAPACK's 1-based row
+            if (!zero) {
+                ju = max(ju, min(j + ku + pr - jj, n - 1));
+                const c128 rc = crecip(piv);
+                static_for<RP>([&](auto mc) {
+                    constexpr int m = decltype(mc)::value;
+                    const int r = tid + m * NT;
+                    if (pr != jj && r == pr) static_for<NB>([&](auto kc) { row[m][decltype(kc)::value] = s_top[decltype(kc)::value]; });
+                    if (r > jj && r <= jj + km) {
+                        const c128 l = cmul(row[m][jj], rc);
+                        row[m][jj] = l;
+                        static_for<NB - 1 - jj>([&](auto kc) {
+                            constexpr int k = jj + 1 + decltype(kc)::value;
+                            cfms(row[m][k], l, s_piv[k]);
+                        });
+                    }
+                });
+            }
+        }
+    });
+    // rows below the block: L21
+    static_for<RP>([&](auto mc) {
+        constexpr int m = decltype(mc)::value;
+        const int r = tid + m * NT;
+        if (r >= jb && r < H)
+            static_for<NB>([&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                if (k < jb) lw[r + (long)k * w.lh] = row[m][k];
+            });
+    });
+    if (tid == 0) {
+        w.ju[g] = ju;
+        if (info && a.info[g] == 0) a.info[g] = info;
+    }
+}
+
+// Block row and trailing update of block step j0: workgroup (t, g) takes columns c0 .. c0 + BTC - 1 right of the panel of
+// matrix g, workgroup (ntile, g) its right-hand side.  Rows above a column's first stored row (i < c - kv) are zero and stay
+// zero (a pivot row never reaches them), so they are read as zero and not written.
+template <int NB>
+__global__ void __launch_bounds__(256)
+band_update_kernel(BandArgs a, BlkArgs w, int j0, int ntile)
+{
+    constexpr int NT = 256;
+    extern __shared__ c128 s_v[];                                       // [BTC][lh]
+    __shared__ c128 s_l11[NB * NB];
+    __shared__ int s_pr[NB];
+    const int t = blockIdx.x, g = blockIdx.y, tid = threadIdx.x;
+    const int n = a.n, kl = a.kl, kv = kl + a.ku, ldab = a.ldab, lh = w.lh;
+    const int jb = min(NB, n - j0), H = min(kl + jb, n - j0);
+    const bool rhs = t == ntile;
+    const int c0 = j0 + jb + t * BTC;
+    int ncol = 1;
+    if (!rhs) {
+        const int ju = w.ju[g];
+        if (c0 > ju) return;
+        ncol = min(BTC, ju - c0 + 1);
+    }
+    c128* ab = a.ab + bix(a, g);
+    const c128* lw = w.lw + (long)g * lh * NB;
+    // element i of column q at col(q)[i], stored from row lo(q) on
+    auto col = [&](int q) -> c128* { return rhs ? a.x + (long)g * n : ab + (long)(c0 + q) * ldab + kv - (c0 + q); };
+    auto lo = [&](int q) { return rhs ? 0 : c0 + q - kv; };
+    for (int q = 0; q < ncol; ++q) {
+        c128* p = col(q);
+        const int l0 = lo(q);
+        for (int r = tid; r < H; r += NT) s_v[q * lh + r] = (j0 + r >= l0) ? p[j0 + r] : cmake(0.0, 0.0);
+    }
+    if (tid < NB) s_pr[tid] = tid < jb ? a.ipiv[(long)g * n + j0 + tid] - 1 - j0 : tid;
+    if (tid < NB * NB) {
+        const int r = tid % NB, k = tid / NB;
+        s_l11[tid] = (k < r && r < jb) ? lw[r + (long)k * lh] : cmake(0.0, 0.0);
+    }
+    __syncthreads();
+    if (tid < ncol)
+        for (int jj = 0; jj < jb; ++jj) {
+            const int pr = s_pr[jj];
+            if (pr != jj) { const c128 u = s_v[tid * lh + jj]; s_v[tid * lh + jj] = s_v[tid * lh + pr]; s_v[tid * lh + pr] = u; }
+        }
+    __syncthreads();
+    {
+        const int q = tid / NB, r = tid % NB;
+        for (int k = 0; k + 1 < jb; ++k) {
+            if (q < ncol && r > k && r < jb) cfms(s_v[q * lh + r], s_l11[r + k * NB], s_v[q * lh + k]);
+            __syncthreads();
+        }
+        if (q < ncol && r < jb && j0 + r >= lo(q)) col(q)[j0 + r] = s_v[q * lh + r];
+    }
+    for (int r = jb + tid; r < H; r += NT) {                            // rows below the block: jb = NB here
+        c128 l[NB];
+#pragma unroll
+        for (int k = 0; k < NB; ++k) l[k] = lw[r + (long)k * lh];
+        for (int q = 0; q < ncol; ++q) {
+            c128 acc = s_v[q * lh + r];
+#pragma unroll
+            for (int k = 0; k < NB; ++k) cfms(acc, l[k], s_v[q * lh + k]);
+            if (j0 + r >= lo(q)) col(q)[j0 + r] = acc;
+        }
+    }
+}
+
+// U x = y in blocks of BNB on matrix blockIdx.x, with the operations of band_back_kernel in its order; x[j] goes to
+// out[perm[j]].  flags |= 2 on a non-finite result.
+template <int NT>
+__global__ void __launch_bounds__(NT)
+band_back_blk_kernel(BandArgs a, c128* __restrict__ out, long ldo, const int* __restrict__ slots, const int* __restrict__ perm)
+{
+    __shared__ c128 s_u[BNB * BNB], s_y[BNB], s_x[BNB];
+    const int g = blockIdx.x, tid = threadIdx.x;
+    const int n = a.n, kv = a.kl + a.ku, ldab = a.ldab;
+    const c128* ab = a.ab + bix(a, g);
+    c128* x = a.x + (long)g * n;
+    c128* o = out + (slots ? (long)slots[g] : (long)g) * ldo;
+    bool bad = false;
+    for (int j0 = (n - 1) / BNB * BNB; j0 >= 0; j0 -= BNB) {
+        const int jb = min(BNB, n - j0);
+        if (tid < BNB * BNB) {
+            const int r = tid & (BNB - 1), k = tid / BNB;
+            s_u[tid] = (r <= k && k < jb && k - r <= kv) ? ab[kv + r - k + (long)(j0 + k) * ldab] : cmake(0.0, 0.0);
+        }
+        if (tid < jb) s_y[tid] = x[j0 + tid];
+        __syncthreads();
+        for (int k = jb - 1; k >= 0; --k) {
+            c128 xk = s_y[k];
+            const bool nz = xk.x != 0.0 || xk.y != 0.0;
+            if (nz) xk = cdiv(xk, s_u[k + k * BNB]);
+            if (nz && tid < k) cfms(s_y[tid], xk, s_u[tid + k * BNB]);
+            if (tid == k) s_x[k] = xk;
+            lds_barrier();
+        }
+        if (tid < jb) { const c128 xk = s_x[tid]; o[perm ? perm[j0 + tid] : j0 + tid] = xk; bad |= !cfinite(xk); }
+        for (int i = max(0, j0 - kv) + tid; i < j0; i += NT) {
+            c128 acc = x[i];
+            for (int k = jb - 1; k >= 0; --k) {
+                const c128 xk = s_x[k];
+                const int c = j0 + k;
+                if ((xk.x != 0.0 || xk.y != 0.0) && i >= c - kv) cfms(acc, xk, ab[kv + i - c + (long)c * ldab]);
+            }
+            x[i] = acc;
+        }
+        __syncthreads();
+    }
+    if (bad) atomicOr(&a.flags[g], 2);
+}
+
+// The whole blocked solve of G matrices on `st`: n / BNB block steps of two launches each, then the back substitution.  The
+// launch queue is bounded as maus_herm_tridiag bounds it: an event every 64 block steps, wait for the one before last.
+template <int NB>
+hipError_t launch_blocked_nb(const BandArgs& a, const BlkArgs& w, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)band_update_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+        attr_set = true;
+    }
+    const int kv = a.kl + a.ku, H = a.kl + NB, ntile = (kv + BTC - 1) / BTC;
+    const size_t lds = sizeof(c128) * (size_t)w.lh * BTC;
+    hipError_t err = hipMemsetAsync(w.ju, 0, sizeof(int) * G, st);
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    for (auto& e : ev) if (err == hipSuccess) err = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+    int step = 0;
+    for (int j0 = 0; j0 < a.n && err == hipSuccess; j0 += NB, ++step) {
+        if (step % 64 == 0 && step >= 128) err = hipEventSynchronize(ev[(step / 64) & 1]);
+        if (err != hipSuccess) break;
+        if (H <= 256) hipLaunchKernelGGL((band_panel_kernel<256, 1, NB>), dim3(G), dim3(256), 0, st, a, w, j0);
+        else if (H <= 512) hipLaunchKernelGGL((band_panel_kernel<512, 1, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
+        else if (H <= 1024) hipLaunchKernelGGL((band_panel_kernel<512, 2, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
+        else hipLaunchKernelGGL((band_panel_kernel<512, 3, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
+        hipLaunchKernelGGL(band_update_kernel<NB>, dim3(ntile + 1, G), dim3(256), lds, st, a, w, j0, ntile);
+        if (step % 64 == 63) { err = hipGetLastError(); if (err == hipSuccess) err = hipEventRecord(ev[(step / 64) & 1], st); }
+    }
+    if (err == hipSuccess) {
+        if (kv <= 256) hipLaunchKernelGGL((band_back_blk_kernel<256>), dim3(G), dim3(256), 0, st, a, out, ldo, slots, perm);
+        else hipLaunchKernelGGL((band_back_blk_kernel<1024>), dim3(G), dim3(1024), 0, st, a, out, ldo, slots, perm);
+        err = hipGetLastError();
+    }
+    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+    return err;
+}
+
+hipError_t launch_blocked(const BandArgs& a, const BlkArgs& w, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
+    return band_nb(a.kl, a.ku) == BNB ? launch_blocked_nb<BNB>(a, w, G, st, out, ldo, slots, perm)
+                                      : launch_blocked_nb<BNB_TALL>(a, w, G, st, out, ldo, slots, perm);
+}
+
 // workgroup size from (kl, ku) alone: one wave for narrow bands, where the barriers of every column dominate
 int band_threads(int kl, int ku) {
     const long w = (long)kl * (kl + ku);
@@ -214,11 +511,25 @@ void launch_back(const BandArgs& a, int G, hipStream_t st, c128* out, long ldo, 
 double band_flops(int n, int kl, int ku, int G) { return 8.0 * G * n * ((double)kl * (kl + ku) + 2.0 * kl + ku); }
 double band_bytes(int n, int ldab, int G) { return 32.0 * G * (double)ldab * n; }
 
-size_t band_per_solve(int n, int ldab) { return sizeof(c128) * ((size_t)ldab * n + n) + sizeof(int) * (size_t)n; }
+// the blocked method moves the band once per block step over the columns a pivot row can reach (kl + ku of them when every
+// step pivots from the bottom; ku when none does -- the reach is only known on the device, so this is the upper end), and
+// once more in the back substitution
+double band_blocked_bytes(int n, int kl, int ku, int G) {
+    const int nb = band_nb(kl, ku);
+    return 32.0 * G * ((double)(n + nb - 1) / nb) * (kl + nb) * (double)(nb + kl + ku) + 16.0 * G * (double)n * (kl + ku + 1);
+}
+
+// bytes of one solve in the workspace; the blocked method adds its panel of L and its reach
+size_t band_per_solve(int n, int kl, int ku, bool blocked) {
+    const size_t ldab = 2 * (size_t)kl + ku + 1;
+    return sizeof(c128) * (ldab * n + n) + sizeof(int) * (size_t)n
+         + (blocked ? sizeof(c128) * (size_t)(kl + BNB) * BNB + sizeof(int) : 0);
+}
 
 void band_ws_free(maus_ctx* c) {
-    void* ps[] = {c->band_ab, c->band_x, c->band_ipiv, c->band_info, c->band_flags};
+    void* ps[] = {c->band_ab, c->band_x, c->band_ipiv, c->band_info, c->band_flags, c->band_lw, c->band_ju};
     for (void* p : ps) if (p) (void)hipFree(p);
+    c->band_lw = nullptr; c->band_ju = nullptr;
     c->band_ab = nullptr; c->band_x = nullptr; c->band_ipiv = nullptr; c->band_info = nullptr; c->band_flags = nullptr;
     c->band_g = 0; c->band_at_limit = false; c->band_ws_key = 0;
 }
@@ -228,8 +539,9 @@ void band_ws_free(maus_ctx* c) {
 // memory) -- never shrunk; larger batches run in balanced chunks.
 int ensure_band_ws(maus_ctx* c, int want) {
     const int n = c->band_n, ldab = 2 * c->band_kl + c->band_ku + 1;
-    const size_t per = band_per_solve(n, ldab);
-    const unsigned long long key = ((unsigned long long)n << 32) | (unsigned)ldab;
+    const bool blocked = band_runs_blocked(c->band_method, c->band_kl, c->band_ku);
+    const size_t per = band_per_solve(n, c->band_kl, c->band_ku, blocked);
+    const unsigned long long key = ((unsigned long long)n << 32) | ((unsigned long long)blocked << 31) | (unsigned)ldab;
     const bool same = c->band_ab && c->band_ws_key == key;
     if (same && (c->band_g >= want || c->band_at_limit)) return 0;
     size_t fr = 0, tot = 0;
@@ -254,6 +566,10 @@ int ensure_band_ws(maus_ctx* c, int want) {
     HIPCHK(c, hipMalloc((void**)&c->band_ipiv, sizeof(int) * (size_t)n * G));
     HIPCHK(c, hipMalloc((void**)&c->band_info, sizeof(int) * G));
     HIPCHK(c, hipMalloc((void**)&c->band_flags, sizeof(int) * G));
+    if (blocked) {
+        HIPCHK(c, hipMalloc((void**)&c->band_lw, sizeof(c128) * (size_t)(c->band_kl + BNB) * BNB * G));
+        HIPCHK(c, hipMalloc((void**)&c->band_ju, sizeof(int) * G));
+    }
     c->band_g = G; c->band_ws_key = key; c->band_allocs++;
     c->band_at_limit = same || G < G_asked || G >= std::min(cap, gmax);
     return 0;
@@ -265,6 +581,8 @@ BandArgs band_args(maus_ctx* c) {
     a.n = c->band_n; a.kl = c->band_kl; a.ku = c->band_ku; a.ldab = 2 * a.kl + a.ku + 1;
     return a;
 }
+
+BlkArgs blk_args(maus_ctx* c) { BlkArgs w; w.lw = c->band_lw; w.ju = c->band_ju; w.lh = c->band_kl + band_nb(c->band_kl, c->band_ku); return w; }
 
 void band_status(int G, const int* info, const int* flags, int32_t* status) {
     for (int g = 0; g < G; ++g) {
@@ -349,20 +667,26 @@ int maus_band_solve(maus_ctx* c, const int* slots, int count, const double* shif
     const int Gmax = (count + nchunks - 1) / nchunks;
     std::vector<int> h_info(Gmax), h_flags(Gmax);
     const BandArgs a = band_args(c);
+    const bool blocked = band_runs_blocked(c->band_method, a.kl, a.ku);
+    const BlkArgs w = blk_args(c);
     for (int off = 0; off < count; off += Gmax) {
         const int G = std::min(Gmax, count - off);
         if (maus_h2d(c, c->d_slots, slots + off, sizeof(int) * G, c->st)) return -1;
         if (maus_h2d(c, c->d_c1, shift + 2 * (size_t)off, sizeof(c128) * G, c->st)) return -1;
         if (maus_h2d(c, c->d_r1, psi + off, sizeof(double) * G, c->st)) return -1;
         {
-            ProfScope ps(c, KC_BAND, band_flops(a.n, a.kl, a.ku, G), band_bytes(a.n, a.ldab, G));
+            ProfScope ps(c, blocked ? KC_BAND_BLOCKED : KC_BAND, band_flops(a.n, a.kl, a.ku, G),
+                         blocked ? band_blocked_bytes(a.n, a.kl, a.ku, G) : band_bytes(a.n, a.ldab, G));
             HIPCHK(c, hipMemsetAsync(a.info, 0, sizeof(int) * G, c->st));
             HIPCHK(c, hipMemsetAsync(a.flags, 0, sizeof(int) * G, c->st));
             HIPCHK(c, hipMemsetAsync(a.ab, 0, sizeof(c128) * (size_t)a.ldab * a.n * G, c->st));
             hipLaunchKernelGGL(band_build_csr_kernel, dim3((a.n + 255) / 256, G), dim3(256), 0, c->st, a, c->Acsr.ptr, c->Acsr.idx,
                                c->Acsr.val, c->band_perm, c->band_iperm, c->d_c1, c->d_r1, rhs_mode, c->X, c->ldp, c->d_slots, c->b);
-            launch_factor(a, G, c->st);
-            launch_back(a, G, c->st, c->W, c->ldp, c->d_slots, c->band_perm);
+            if (blocked) HIPCHK(c, launch_blocked(a, w, G, c->st, c->W, c->ldp, c->d_slots, c->band_perm));
+            else {
+                launch_factor(a, G, c->st);
+                launch_back(a, G, c->st, c->W, c->ldp, c->d_slots, c->band_perm);
+            }
         }
         if (maus_d2h(c, h_info.data(), a.info, sizeof(int) * G, c->st)) return -1;
         if (maus_d2h(c, h_flags.data(), a.flags, sizeof(int) * G, c->st)) return -1;
@@ -374,6 +698,23 @@ int maus_band_solve(maus_ctx* c, const int* slots, int count, const double* shif
 }
 
 int maus_band_workspace_allocs(maus_ctx* c) { return c ? c->band_allocs : -1; }
+
+int maus_band_set_method(maus_ctx* c, int method) {
+    if (!c) return -1;
+    if (method != 0 && method != 1) FAIL(c, "maus_band_set_method: method must be 0 (column) or 1 (blocked)");
+    c->band_method = method;                                            // the workspace follows at its next use (ensure_band_ws)
+    return 0;
+}
+
+int maus_band_get_method(maus_ctx* c) { return c ? c->band_method : -1; }
+
+int maus_band_kernel_for(maus_ctx* c, int n, int kl, int ku, int* nb_out) {
+    if (!c) return -1;
+    if (n <= 0 || kl < 0 || ku < 0) FAIL(c, "maus_band_kernel_for: bad sizes");
+    const bool blocked = band_runs_blocked(c->band_method, kl, ku);
+    if (nb_out) *nb_out = blocked ? band_nb(kl, ku) : 1;
+    return blocked ? 1 : 0;
+}
 
 int maus_band_lu_host(maus_ctx* c, int count, int n, int kl, int ku, const double* ab, const double* b, double* x_out,
                       int32_t* ipiv_out, int32_t* info_out) {
@@ -387,19 +728,29 @@ int maus_band_lu_host(maus_ctx* c, int count, int n, int kl, int ku, const doubl
     auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
     const size_t o_ab = take(abb * count), o_x = take(xb * count), o_o = take(xb * count), o_p = take(ib * count),
                  o_i = take(sizeof(int) * count), o_f = take(sizeof(int) * count);
+    const bool blocked = band_runs_blocked(c->band_method, kl, ku);
+    BlkArgs w; w.lw = nullptr; w.ju = nullptr; w.lh = kl + band_nb(kl, ku);
+    const size_t o_l = take(blocked ? sizeof(c128) * (size_t)(kl + BNB) * BNB * count : 0), o_j = take(blocked ? sizeof(int) * count : 0);
     if (ensure_scratch(c, off)) return -1;
     char* base = (char*)c->scratch;
     a.ab = (c128*)(base + o_ab); a.x = (c128*)(base + o_x); a.ipiv = (int*)(base + o_p); a.info = (int*)(base + o_i); a.flags = (int*)(base + o_f);
     c128* out = (c128*)(base + o_o);
+    if (blocked) { w.lw = (c128*)(base + o_l); w.ju = (int*)(base + o_j); }
     if (maus_stage_h2d(c, a.ab, ab, abb * count, c->st)) return -1;
     if (maus_stage_h2d(c, a.x, b, xb * count, c->st)) return -1;
     HIPCHK(c, hipMemsetAsync(a.info, 0, sizeof(int) * count, c->st));
     HIPCHK(c, hipMemsetAsync(a.flags, 0, sizeof(int) * count, c->st));
     {
-        ProfScope ps(c, KC_BAND, band_flops(n, kl, ku, count), band_bytes(n, a.ldab, count));
+        ProfScope ps(c, blocked ? KC_BAND_BLOCKED : KC_BAND, band_flops(n, kl, ku, count),
+                     blocked ? band_blocked_bytes(n, kl, ku, count) : band_bytes(n, a.ldab, count));
         hipLaunchKernelGGL(band_scan_kernel, dim3(64, count), dim3(256), 0, c->st, a);
-        launch_factor(a, count, c->st);
-        launch_back(a, count, c->st, out, n, nullptr, nullptr);
+        if (blocked) {
+            hipLaunchKernelGGL(band_zero_fill_kernel, dim3(64, count), dim3(256), 0, c->st, a);
+            HIPCHK(c, launch_blocked(a, w, count, c->st, out, n, nullptr, nullptr));
+        } else {
+            launch_factor(a, count, c->st);
+            launch_back(a, count, c->st, out, n, nullptr, nullptr);
+        }
     }
     std::vector<int> h_info(count), h_flags(count);
     if (maus_stage_d2h(c, x_out, out, xb * count, c->st)) return -1;

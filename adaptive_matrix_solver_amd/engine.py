@@ -237,7 +237,7 @@ def tridiagonal_eigenvalues(ctx, d, e):
     return np.sort(sla.eigvalsh_tridiagonal(d, e))
 
 
-SPARSE_DIRECT_MODES = ("auto", "dense", "band")
+SPARSE_DIRECT_MODES = ("auto", "dense", "band", "blocked")
 
 
 def sparse_direct_mode(mode):
@@ -362,7 +362,8 @@ class DeviceEngine:
         self._sparse = False                    # the bound matrix is sparse (CSR on the device)
         # direct solves of a sparse matrix: 'dense' densifies H_k into the LU workspace (n <= maus_lu_max_n()),
         # 'band' runs the band LU in the ordering of band.band_order, 'auto' the first up to maus_lu_max_n() and the second
-        # above.  MAUS_SPARSE_DIRECT sets the default.  Chosen once per bound matrix (_band).
+        # above; 'blocked' is 'band' with the blocked kernels (zgbtrf's schedule, every step a launch over the whole device;
+        # opt-in, 'auto' never picks it).  MAUS_SPARSE_DIRECT sets the default.  Chosen once per bound matrix (_band).
         self.sparse_direct = sparse_direct_mode(sparse_direct)
         # sparse Hermitian shortcut (AMS:186-216): 'dense' = one scipy.linalg.eigh of A.toarray() per matrix, 'lanczos' =
         # thick-restart Lanczos on the CSR matrix on the device, 'auto' the first up to maus_lu_max_n() and the second above.
@@ -451,7 +452,7 @@ class DeviceEngine:
 
     def uses_band(self, n: int) -> bool:
         """Whether a sparse n x n matrix takes the band solve (sparse_direct; 'auto': above maus_lu_max_n())."""
-        if self.sparse_direct == "band":
+        if self.sparse_direct in ("band", "blocked"):
             return True
         if self.sparse_direct == "dense":
             return False
@@ -473,6 +474,8 @@ class DeviceEngine:
         pay neither the ordering nor the host copy of the pattern."""
         if not self._band_ready:
             perm, kl, ku = self.band_shape(self._bound)
+            if self.sparse_direct == "blocked":  # the only mode that touches the method: contexts without it keep working
+                self.ctx.band_set_method(1)
             self.ctx.band_prepare(perm)
             self._band_ready = True
 

@@ -113,7 +113,14 @@ int maus_matrix_is_sparse(maus_ctx* ctx);
  *   ldab = 2 kl + ku + 1 entries, A(i, j) at row kl + ku + i - j; the first kl rows are workspace), and b[count][n]:
  *   x_out[count][n], ipiv_out[count][n] (may be NULL; LAPACK's 1-based rows) and info_out[count] with the status values
  *   above.  Test entry point.
- * maus_band_workspace_allocs: (re-)allocations of the band workspace on this context. */
+ * maus_band_workspace_allocs: (re-)allocations of the band workspace on this context.
+ * maus_band_set_method: which kernels maus_band_solve, maus_band_reserve and maus_band_lu_host run on this context --
+ *   0 the column kernel (one workgroup per matrix walks the columns; the default), 1 the blocked method (zgbtrf's
+ *   schedule in blocks of 16 columns, every step a launch over (matrix, tile)).  Under method 1 a band with kl < 16 or
+ *   kl > 1024 still runs the column kernel.  The method outlives the bound matrix; same status contract either way.
+ * maus_band_get_method: the current method.
+ * maus_band_kernel_for: what (n, kl, ku) runs under the current method: returns 0 (column kernel) or 1 (blocked);
+ *   nb_out (may be NULL): the block width, 1 for the column kernel. */
 int maus_sparse_max_n(void);
 int maus_band_prepare(maus_ctx* ctx, const int32_t* perm, int n, int* kl_out, int* ku_out);
 int maus_band_reserve(maus_ctx* ctx, int count, int* capacity_out);
@@ -122,6 +129,9 @@ int maus_band_solve(maus_ctx* ctx, const int* slots, int count, const double* sh
 int maus_band_lu_host(maus_ctx* ctx, int count, int n, int kl, int ku, const double* ab_c128, const double* b_c128,
                       double* x_out_c128, int32_t* ipiv_out, int32_t* info_out);
 int maus_band_workspace_allocs(maus_ctx* ctx);
+int maus_band_set_method(maus_ctx* ctx, int method);
+int maus_band_get_method(maus_ctx* ctx);
+int maus_band_kernel_for(maus_ctx* ctx, int n, int kl, int ku, int* nb_out);
 
 /* Upload b (AMS:146, 275). */
 int maus_set_rhs(maus_ctx* ctx, const double* b_c128, int n);
@@ -373,7 +383,8 @@ int maus_timer_stop(maus_ctx* ctx, float* ms_out);
 /* Per-kernel-class accounting (event pairs around each launch of the class while enabled).
  * classes: 0 zgemm (LU trailing update with K>=256 / A@X), 1 lu_panel, 2 trsm, 3 (unused since round 2: row-swap sweeps), 4 build_H, 5 backsolve,
  * 6 vector ops, 7..10 zgemm inside the LU recursion with K = 128 / 64 / 32 / 16, 11 CSR products, 12 band solves,
- * 13 lanczos (reorthogonalisation, restart, match of the sparse Hermitian shortcut) */
+ * 13 lanczos (reorthogonalisation, restart, match of the sparse Hermitian shortcut), 14 band solves by the blocked method
+ * (maus_band_set_method; bytes: the band moved once per block step over the full reach kl + ku, not an MFMA class) */
 /* on = 1: event pairs around every launch of every class; on = 2: around the K>=256 zgemm launches only (class 0;
  * long kernels, so cheap enough for a timed region -- full bracketing costs 3-5 % of throughput; MAUS_PROF_STRIDE
  * can thin them out, each sample then stands for `stride` launches); 0: off */

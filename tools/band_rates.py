@@ -1,13 +1,17 @@
-"""Band solve rates (csrc/band.hip) -> profiles/band_rates.txt.
+"""Band solve rates (csrc/band.hip), the column kernel and the blocked method side by side in one process
+-> profiles/band_blocked_rates.txt (profiles/band_rates.txt is the column kernel's record from before the blocked method).
 
 The 2-D 5-point operator (complex values, shuffled, then reordered by band.band_order) at n = 16384, 65536 and 262144: a lone
-shifted solve and a batch, timed by the library's HIP-event profile of the "band" class (build + factorisation + solve).
-Flops 8 n kl (kl + ku) + 8 n (2 kl + ku), bytes = the band storage read and written once; the bound is the larger of the
-fp64 peak (MI355X: 78.6 TFLOP/s, no MFMA in this kernel) and HBM (8 TB/s).  Then band against the densified dense LU at
-n = 16384 for the same 64 shifted systems, both paths in one process, and MAUS_Solver linear loop bodies at n = 65536, P = 64
-(5-point operator + 2 I) on the direct path (gmres_compat='scipy-legacy': every solve a band solve) and on the GMRES path.
+shifted solve and a batch, timed by the library's HIP-event profile of the "band" / "band_blocked" class (build +
+factorisation + solve), first with the column kernel, then with the blocked method, same systems, same context.
+Flops 8 n kl (kl + ku) + 8 n (2 kl + ku); bytes = the band storage read and written once (column kernel) or once per block
+step over the full reach kl + ku (blocked: an upper end, a matrix that pivots little moves less); the bound is the larger
+of the fp64 peak (MI355X: 78.6 TFLOP/s, no MFMA in these kernels) and HBM (8 TB/s).  Then both against the densified dense
+LU at n = 16384 for the same 64 shifted systems, and MAUS_Solver linear loop bodies at n = 65536, P = 64 (5-point operator
++ 2 I) on the direct path (gmres_compat='scipy-legacy': every solve a band solve) with sparse_direct 'band' and 'blocked',
+and on the GMRES path.
 
-    python tools/band_rates.py [--out profiles/band_rates.txt]
+    python tools/band_rates.py [--out profiles/band_blocked_rates.txt]
 """
 import argparse
 import os
@@ -45,7 +49,7 @@ def bind(ctx, A, P):
     return kl, ku
 
 
-def timed_band(ctx, count, reps=2):
+def timed_band(ctx, count, klass="band", reps=2):
     rng = np.random.default_rng(2)
     shift = rng.standard_normal(count) + 1j * rng.standard_normal(count)
     psi = np.full(count, 1e-3)
@@ -59,7 +63,7 @@ def timed_band(ctx, count, reps=2):
         t0 = time.perf_counter()
         st = ctx.band_solve(slots, shift, psi, 0)
         wall = time.perf_counter() - t0
-        pr = ctx.profile_read()["band"]
+        pr = ctx.profile_read()[klass]
         assert (st == 0).all(), st
         if best is None or pr["ms"] < best[0]["ms"]:
             best = (pr, wall)
@@ -67,7 +71,7 @@ def timed_band(ctx, count, reps=2):
     return best
 
 
-def loop_rate(compat, bodies=3):
+def loop_rate(compat, direct="auto", bodies=3):
     import random
     from adaptive_matrix_solver_amd.solver import MAUS_Solver, ProblemType, SolutionCandidate
     A = (five_point(256, 7) + 2.0 * sp.identity(65536)).tocsr()
@@ -77,7 +81,7 @@ def loop_rate(compat, bodies=3):
     diag = {"is_sparse_init": True, "condition_number": 1e7, "is_singular": False, "is_hermitian": False,
             "is_complex_symmetric": False}
     s = MAUS_Solver(A, ProblemType.SOLVE_LINEAR_SYSTEM, b_vector=b, initial_num_candidates=64, quiet=True, sparse_mode="device",
-                    gmres_compat=compat, diag_info=diag)
+                    gmres_compat=compat, sparse_direct=direct, diag_info=diag)
     s.loop_body(1)
     ctx = s.engine.ctx
     ctx.profile_enable(False)
@@ -90,20 +94,22 @@ def loop_rate(compat, bodies=3):
     wall = time.perf_counter() - t0
     pr = ctx.profile_read()
     ctx.profile_enable(False)
-    return steps / wall, pr["band"]["ms"] / bodies, pr["spmm"]["ms"] / bodies
+    return steps / wall, (pr["band"]["ms"] + pr["band_blocked"]["ms"]) / bodies, pr["spmm"]["ms"] / bodies
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/band_rates.txt")
+    ap.add_argument("--out", default="profiles/band_blocked_rates.txt")
     ap.add_argument("--sizes", default="128:1,128:64,256:1,256:64,512:1,512:8")
     args = ap.parse_args()
     ctx = _cabi.Context(0)
     info = ctx.device_info()
-    lines = [f"# band solves, csrc/band.hip -- {info['name']}, {info['cus']} CUs",
-             "# ms / solve from the 'band' profile class (HIP events around build + factor + solve of one batch);",
-             "# bound = max(flops / 78.6 TFLOP/s fp64, bytes / 8 TB/s); share = bound time / measured time",
-             f"{'n':>7} {'kl':>4} {'ku':>4} {'batch':>5} {'ms/solve':>9} {'TFLOP/s':>8} {'TB/s':>6} {'bound':>5} {'share':>7}"]
+    lines = [f"# band solves, csrc/band.hip, column kernel and blocked method in one process -- {info['name']}, {info['cus']} CUs",
+             "# ms / solve from the 'band' / 'band_blocked' profile class (HIP events around build + factor + solve of one batch),",
+             "# the better of two timed calls after one warm-up call; bound = max(flops / 78.6 TFLOP/s fp64, bytes / 8 TB/s);",
+             "# share = bound time / measured time; speed-up = column ms / blocked ms",
+             f"{'n':>7} {'kl':>4} {'ku':>4} {'batch':>5} {'method':>8} {'nb':>3} {'ms/solve':>9} {'TFLOP/s':>8} {'TB/s':>6} {'bound':>5} "
+             f"{'share':>7} {'speed-up':>8}"]
     cache = {}
     for item in args.sizes.split(","):
         m, P = (int(v) for v in item.split(":"))
@@ -113,13 +119,20 @@ def main():
             cache.clear()
             cache[m] = (A, bind(ctx, A, 64))
         A, (kl, ku) = cache[m]
-        pr, wall = timed_band(ctx, P)
-        s = pr["ms"] / 1e3
-        tf, tb = pr["flops"] / s / 1e12, pr["bytes"] / s / 1e12
-        tc, tm = pr["flops"] / PEAK_F64, pr["bytes"] / HBM
-        bound = "fp64" if tc >= tm else "HBM"
-        lines.append(f"{n:>7} {kl:>4} {ku:>4} {P:>5} {pr['ms'] / P:>9.3f} {tf:>8.3f} {tb:>6.2f} {bound:>5} {max(tc, tm) / s:>7.2%}")
-        print(lines[-1], flush=True)
+        col_ms = None
+        for method, name in ((_cabi.BAND_COLUMN, "column"), (_cabi.BAND_BLOCKED, "blocked")):
+            ctx.band_set_method(method)
+            kern, nb = ctx.band_kernel_for(n, kl, ku)
+            pr, wall = timed_band(ctx, P, "band_blocked" if kern == _cabi.BAND_BLOCKED else "band")
+            s = pr["ms"] / 1e3
+            tf, tb = pr["flops"] / s / 1e12, pr["bytes"] / s / 1e12
+            tc, tm = pr["flops"] / PEAK_F64, pr["bytes"] / HBM
+            bound = "fp64" if tc >= tm else "HBM"
+            up = "" if col_ms is None else f"{col_ms / pr['ms']:.2f}x"
+            col_ms = pr["ms"] if col_ms is None else col_ms
+            lines.append(f"{n:>7} {kl:>4} {ku:>4} {P:>5} {name:>8} {nb:>3} {pr['ms'] / P:>9.3f} {tf:>8.3f} {tb:>6.2f} {bound:>5} "
+                         f"{max(tc, tm) / s:>7.2%} {up:>8}")
+            print(lines[-1], flush=True)
     # band against dense at n = 16384: the same 64 shifted systems
     m, P = 128, 64
     A = five_point(m, 3)
@@ -129,24 +142,30 @@ def main():
     shift = rng.standard_normal(P) + 1j * rng.standard_normal(P)
     psi = np.full(P, 1e-3)
     slots = np.arange(P)
-    ctx.band_reserve(P)
-    ctx.band_solve(slots, shift, psi, 0)
-    t0 = time.perf_counter(); ctx.band_solve(slots, shift, psi, 0); tb = time.perf_counter() - t0
-    Wb = ctx.pop_get(_cabi.POP_W, slots, n)
+    tb, Wb = {}, {}
+    for method, name in ((_cabi.BAND_COLUMN, "column"), (_cabi.BAND_BLOCKED, "blocked")):
+        ctx.band_set_method(method)
+        ctx.band_reserve(P)
+        ctx.band_solve(slots, shift, psi, 0)
+        t0 = time.perf_counter(); ctx.band_solve(slots, shift, psi, 0); tb[name] = time.perf_counter() - t0
+        Wb[name] = ctx.pop_get(_cabi.POP_W, slots, n)
     ctx.lu_reserve(n, P)
     t0 = time.perf_counter(); ctx.shifted_lu_solve(slots, shift, psi, 0); td = time.perf_counter() - t0
     Wd = ctx.pop_get(_cabi.POP_W, slots, n)
-    rel = max(np.linalg.norm(Wb[k] - Wd[k]) / np.linalg.norm(Wd[k]) for k in range(P))
-    lines += ["", "# band vs dense (densified H_k, maus_shifted_lu_solve) at n = 16384, 64 shifted 5-point systems, wall clock per call",
-              f"band  {tb * 1e3 / P:9.3f} ms/solve", f"dense {td * 1e3 / P:9.3f} ms/solve",
-              f"speed-up {td / tb:.1f}x, largest relative difference of the solutions {rel:.2e}"]
+    lines += ["", "# band vs dense (densified H_k, maus_shifted_lu_solve) at n = 16384, 64 shifted 5-point systems, wall clock per call"]
+    for name in ("column", "blocked"):
+        rel = max(np.linalg.norm(Wb[name][k] - Wd[k]) / np.linalg.norm(Wd[k]) for k in range(P))
+        lines.append(f"band {name:<8} {tb[name] * 1e3 / P:9.3f} ms/solve, {td / tb[name]:6.1f}x the dense path, largest relative difference "
+                     f"of the solutions {rel:.2e}")
+    lines.append(f"dense         {td * 1e3 / P:9.3f} ms/solve")
     print("\n".join(lines[-4:]), flush=True)
     ctx.close()                                                # its workspaces would crowd out the solver's own context
     lines += ["", "# MAUS_Solver linear loop bodies at n = 65536, P = 64 (5-point + 2 I, GMRES preferred): 1 untimed + 3 timed bodies;",
               "# candidate-steps = candidates in the population at the start of each timed body"]
-    for compat, path in (("scipy-legacy", "direct (band)"), ("rtol", "GMRES")):
-        rate, band_ms, spmm_ms = loop_rate(compat)
-        lines.append(f"{path:<14} {rate:9.1f} candidate-steps/s   (band class {band_ms:8.1f} ms, spmm class {spmm_ms:8.1f} ms per body)")
+    for compat, direct, path in (("scipy-legacy", "band", "direct (column)"), ("scipy-legacy", "blocked", "direct (blocked)"),
+                                 ("rtol", "auto", "GMRES")):
+        rate, band_ms, spmm_ms = loop_rate(compat, direct)
+        lines.append(f"{path:<16} {rate:9.1f} candidate-steps/s   (band classes {band_ms:8.1f} ms, spmm class {spmm_ms:8.1f} ms per body)")
         print(lines[-1], flush=True)
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")
