@@ -34,8 +34,8 @@ POP_X, POP_U, POP_W, POP_Y = 0, 1, 2, 3
 KIND_EIG, KIND_LINEAR, KIND_SVD = 1, 2, 3
 PERT_NONE, PERT_UNIFORM, PERT_MT19937 = 0, 1, 2
 KC_NAMES = ["zgemm", "lu_panel", "trsm", "laswp", "build_h", "backsolve", "vector",
-            "zgemm_k128", "zgemm_k64", "zgemm_k32", "zgemm_k16", "spmm", "band", "lanczos", "band_blocked"]
-BAND_COLUMN, BAND_BLOCKED = 0, 1                     # maus_band_set_method
+            "zgemm_k128", "zgemm_k64", "zgemm_k32", "zgemm_k16", "spmm", "band", "lanczos", "band_blocked", "band_tiled"]
+BAND_COLUMN, BAND_BLOCKED, BAND_TILED = 0, 1, 2      # maus_band_set_method
 SPMM_SCHEDULES = {0: None, 1: "rows", 2: "wave"}     # maus_matrix_is_sparse: dense / lane per row / wave per row
 
 
@@ -624,14 +624,15 @@ class Context:
         return int(self.lib.maus_band_workspace_allocs(self.h))
 
     def band_set_method(self, method):
-        """The kernels of the band entry points: BAND_COLUMN (the default) or BAND_BLOCKED; kept across matrices."""
+        """The kernels of the band entry points: BAND_COLUMN (the default), BAND_BLOCKED or BAND_TILED; kept across matrices."""
         self._ck(self.lib.maus_band_set_method(self.h, int(method)), "maus_band_set_method")
 
     def band_method(self) -> int:
         return int(self.lib.maus_band_get_method(self.h))
 
     def band_kernel_for(self, n, kl, ku):
-        """(kernel, nb) that an (n, kl, ku) band runs under the current method: (BAND_COLUMN, 1) or (BAND_BLOCKED, nb)."""
+        """(kernel, nb) that an (n, kl, ku) band runs under the current method: (BAND_COLUMN, 1), (BAND_BLOCKED, nb) or
+        (BAND_TILED, nb)."""
         nb = C.c_int()
         k = self.lib.maus_band_kernel_for(self.h, int(n), int(kl), int(ku), C.byref(nb))
         self._ck(min(k, 0), "maus_band_kernel_for")

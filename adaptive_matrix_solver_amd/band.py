@@ -52,10 +52,19 @@ def runs_blocked(kl: int, ku: int) -> bool:
     return BLOCKED_MIN_KL <= kl <= BLOCKED_MAX_KL
 
 
-def band_bytes_per_solve(n: int, kl: int, ku: int, blocked: bool = False) -> int:
+TILED_MIN_KL = 16               # the tiled method's range under sparse_direct='tiled': the column kernel outside it ...
+TILED_MAX_KL = 4096             # ... which is where its register panel ends (above kl = 1024: nb = 16 to 1520, 8 to 3064, then 4)
+
+
+def runs_tiled(kl: int, ku: int) -> bool:
+    """Whether the tiled method takes a (kl, ku) band when it is selected (band_runs_tiled in csrc/band.hip)."""
+    return TILED_MIN_KL <= kl <= TILED_MAX_KL
+
+
+def band_bytes_per_solve(n: int, kl: int, ku: int, blocked: bool = False, tiled: bool = False) -> int:
     """Device memory of one band solve: the band storage, the right-hand side and the pivots (csrc/band.hip); with
-    `blocked`, and a band the blocked method takes, its panel of L and its reach as well."""
+    `blocked` (`tiled`), and a band the blocked (tiled) method takes, its panel of L and its reach as well."""
     per = 16 * ((2 * kl + ku + 1) * n + n) + 4 * n
-    if blocked and runs_blocked(kl, ku):
+    if (blocked and runs_blocked(kl, ku)) or (tiled and runs_tiled(kl, ku)):
         per += 16 * (kl + BLOCKED_NB) * BLOCKED_NB + 4
     return per

@@ -18,7 +18,8 @@
 //
 // That is the column kernel, the default.  maus_band_set_method(ctx, 1) selects the blocked method further down (zgbtrf's
 // schedule, every step a launch over (matrix, tile)) for bands with BLK_MIN_KL <= kl <= BLK_MAX_KL; same storage, build kernel,
-// pivot rule and status contract.
+// pivot rule and status contract.  maus_band_set_method(ctx, 2) selects the tiled method after it (the blocked schedule with the
+// block row and the trailing update as launches of their own over (column tile, row tile)) for kl up to TIL_MAX_KL.
 #include "ctx.h"
 #include <climits>
 #include <utility>
@@ -484,6 +485,212 @@ hipError_t launch_blocked(const BandArgs& a, const BlkArgs& w, int G, hipStream_
                                       : launch_blocked_nb<BNB_TALL>(a, w, G, st, out, ldo, slots, perm);
 }
 
+// ---- the tiled method (maus_band_set_method(ctx, 2)) --------------------------------------------------------
+// The blocked method's schedule, storage, panel, pivot rule, status contract and back substitution, with the update split so
+// that nothing of height kl goes through LDS and the panel is the only kernel whose reach is bounded (kl <= TIL_MAX_KL):
+//   panel      band_panel_kernel with up to 9 rows per thread; above kl = 1024 the block width shrinks with the height of the
+//              slice (band_tiled_nb) so that every instantiation stays in registers.
+//   block row  one workgroup per 256 / nb columns right of the panel (plus the right-hand side): the interchanges and
+//              U12 = L11^-1 A12 on the 2 nb elements of a column that they touch -- its top nb rows and its pivot rows.
+//   trailing   one workgroup per (TCT columns, TRT rows) of A22 (plus the right-hand side): a thread keeps its row of L21 in
+//              registers, U12 of the tile sits in LDS, every element is read once and written once.
+// Every element is owned by one thread in each launch and its nb multiply-subtracts run in column order on the values the
+// blocked update uses, so for a band that both methods take the results are the same bits.
+constexpr int TIL_MIN_KL = BLK_MIN_KL;
+constexpr int TIL_MAX_KL = 4096;                        // the register panel ends at 4608 rows (512 threads x 9 rows, nb = 4)
+constexpr int TIL_NB16_H = 1536;                        // above kl = 1024: nb = 16 while kl + 16 rows fit three per thread ...
+constexpr int TNB_MID = 8;                              // ... 8 while kl + 8 <= 3072 (six per thread) ...
+constexpr int TNB_TALL = 4;                             // ... and 4 up to TIL_MAX_KL
+constexpr int TCT = 16;                                 // columns per tile of the trailing update
+constexpr int TRT = 256;                                // rows per tile of the trailing update: one per thread
+
+bool band_runs_tiled(int method, int kl, int ku) { (void)ku; return method == 2 && kl >= TIL_MIN_KL && kl <= TIL_MAX_KL; }
+// up to BLK_MAX_KL the blocked method's width, so that both methods do the same arithmetic there; above it the widest block
+// whose panel stays in registers (measured: DESIGN §11)
+int band_tiled_nb(int kl, int ku) {
+    if (kl <= BLK_MAX_KL) return band_nb(kl, ku);
+    return kl + BNB <= TIL_NB16_H ? BNB : (kl + TNB_MID <= 3072 ? TNB_MID : TNB_TALL);
+}
+
+// 0: the column kernel, 1: blocked, 2: tiled -- what a (kl, ku) band runs under `method`; the block width with it
+int band_kind(int method, int kl, int ku) { return band_runs_blocked(method, kl, ku) ? 1 : (band_runs_tiled(method, kl, ku) ? 2 : 0); }
+int band_kind_nb(int kind, int kl, int ku) { return kind == 1 ? band_nb(kl, ku) : (kind == 2 ? band_tiled_nb(kl, ku) : 1); }
+
+// Block row of block step j0: workgroup (t, g) takes the 256 / NB columns from c0 right of the panel of matrix g, workgroup
+// (ntile, g) its right-hand side.  A column keeps 2 NB elements in LDS: slots 0 .. NB - 1 its rows j0 .. j0 + NB - 1, slot
+// NB + jj the pivot row of column jj where that row lies below the block (pivot rows that coincide share the first slot).
+// Rows above a column's first stored row are read as zero and not written, as band_update_kernel.
+template <int NB>
+__global__ void __launch_bounds__(256)
+band_row_kernel(BandArgs a, BlkArgs w, int j0, int ntile)
+{
+    constexpr int NT = 256, RC = NT / NB, SL = 2 * NB;
+    __shared__ c128 s_v[RC * SL];
+    __shared__ c128 s_l11[NB * NB];
+    __shared__ int s_pr[NB], s_sl[NB];
+    const int t = blockIdx.x, g = blockIdx.y, tid = threadIdx.x;
+    const int n = a.n, kl = a.kl, kv = kl + a.ku, ldab = a.ldab, lh = w.lh;
+    const int jb = min(NB, n - j0), H = min(kl + jb, n - j0);
+    const bool rhs = t == ntile;
+    const int c0 = j0 + jb + t * RC;
+    int ncol = 1;
+    if (!rhs) {
+        const int ju = w.ju[g];
+        if (c0 > ju) return;
+        ncol = min(RC, ju - c0 + 1);
+    }
+    c128* ab = a.ab + bix(a, g);
+    const c128* lw = w.lw + (long)g * lh * NB;
+    auto col = [&](int q) -> c128* { return rhs ? a.x + (long)g * n : ab + (long)(c0 + q) * ldab + kv - (c0 + q); };
+    auto lo = [&](int q) { return rhs ? 0 : c0 + q - kv; };
+    if (tid < NB) {
+        const int* ip = a.ipiv + (long)g * n + j0;
+        int pr = tid, sl = tid;
+        if (tid < jb) {
+            pr = ip[tid] - 1 - j0;
+            sl = pr;
+            if (pr >= jb) {
+                sl = NB + tid;
+                for (int k = tid - 1; k >= 0; --k) if (ip[k] - 1 - j0 == pr) sl = NB + k;
+            }
+        }
+        s_pr[tid] = pr; s_sl[tid] = sl;
+    }
+    if (tid < NB * NB) {
+        const int r = tid % NB, k = tid / NB;
+        s_l11[tid] = (k < r && r < jb) ? lw[r + (long)k * lh] : cmake(0.0, 0.0);
+    }
+    __syncthreads();
+    for (int e = tid; e < ncol * SL; e += NT) {
+        const int q = e / SL, s = e % SL;
+        const int r = s < NB ? s : s_pr[s - NB];
+        const bool used = (s < NB ? s : s - NB) < jb && r < H;
+        s_v[e] = (used && j0 + r >= lo(q)) ? col(q)[j0 + r] : cmake(0.0, 0.0);
+    }
+    __syncthreads();
+    if (tid < ncol)
+        for (int jj = 0; jj < jb; ++jj) {
+            const int sl = s_sl[jj];
+            if (sl != jj) { const c128 u = s_v[tid * SL + jj]; s_v[tid * SL + jj] = s_v[tid * SL + sl]; s_v[tid * SL + sl] = u; }
+        }
+    __syncthreads();
+    const int q = tid / NB, r = tid % NB;
+    for (int k = 0; k + 1 < jb; ++k) {
+        if (q < ncol && r > k && r < jb) cfms(s_v[q * SL + r], s_l11[r + k * NB], s_v[q * SL + k]);
+        __syncthreads();
+    }
+    if (q < ncol && r < jb) {
+        if (j0 + r >= lo(q)) col(q)[j0 + r] = s_v[q * SL + r];
+        const int pr = s_pr[r];
+        if (s_sl[r] == NB + r && pr < H && j0 + pr >= lo(q)) col(q)[j0 + pr] = s_v[q * SL + NB + r];
+    }
+}
+
+// Trailing update of block step j0 (a full block: jb = NB): workgroup (ct * nrt + rt, g) takes rows NB + rt TRT .. of the
+// slice in the TCT columns from c0 right of the panel of matrix g, column tile ct = nct its right-hand side.  Along a column
+// the band storage is contiguous in the row, so the loads and stores of a wave coalesce.
+template <int NB>
+__global__ void __launch_bounds__(TRT)
+band_trail_kernel(BandArgs a, BlkArgs w, int j0, int nct, int nrt)
+{
+    __shared__ c128 s_u[TCT * NB];
+    const int ct = blockIdx.x / nrt, rt = blockIdx.x % nrt, g = blockIdx.y, tid = threadIdx.x;
+    const int n = a.n, kl = a.kl, kv = kl + a.ku, ldab = a.ldab, lh = w.lh;
+    const int H = min(kl + NB, n - j0);
+    const bool rhs = ct == nct;
+    const int c0 = j0 + NB + ct * TCT;
+    int ncol = 1;
+    if (!rhs) {
+        const int ju = w.ju[g];
+        if (c0 > ju) return;
+        ncol = min(TCT, ju - c0 + 1);
+    }
+    c128* ab = a.ab + bix(a, g);
+    const c128* lw = w.lw + (long)g * lh * NB;
+    auto col = [&](int q) -> c128* { return rhs ? a.x + (long)g * n : ab + (long)(c0 + q) * ldab + kv - (c0 + q); };
+    auto lo = [&](int q) { return rhs ? 0 : c0 + q - kv; };
+    for (int e = tid; e < ncol * NB; e += TRT) {
+        const int q = e / NB, k = e % NB;
+        s_u[e] = (j0 + k >= lo(q)) ? col(q)[j0 + k] : cmake(0.0, 0.0);
+    }
+    __syncthreads();
+    const int r = NB + rt * TRT + tid;
+    if (r >= H) return;
+    c128 l[NB];
+#pragma unroll
+    for (int k = 0; k < NB; ++k) l[k] = lw[r + (long)k * lh];
+#pragma unroll 4
+    for (int q = 0; q < ncol; ++q) {
+        const bool in = j0 + r >= lo(q);
+        c128* p = col(q) + j0 + r;
+        c128 acc = in ? *p : cmake(0.0, 0.0);
+#pragma unroll
+        for (int k = 0; k < NB; ++k) cfms(acc, l[k], s_u[q * NB + k]);
+        if (in) *p = acc;
+    }
+}
+
+template <int NB>
+void launch_tiled_panel(const BandArgs& a, const BlkArgs& w, int G, hipStream_t st, int j0) {
+    const int H = a.kl + NB;
+    if constexpr (NB == BNB) {                                          // kl <= 1008 (the blocked method's panels), 1025 <= kl <= 1520
+        if (H <= 256) hipLaunchKernelGGL((band_panel_kernel<256, 1, NB>), dim3(G), dim3(256), 0, st, a, w, j0);
+        else if (H <= 512) hipLaunchKernelGGL((band_panel_kernel<512, 1, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
+        else if (H <= 1024) hipLaunchKernelGGL((band_panel_kernel<512, 2, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
+        else hipLaunchKernelGGL((band_panel_kernel<512, 3, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
+    } else if constexpr (NB == TNB_MID) {                               // 1009 <= kl <= 1024, 1521 <= kl <= 3064
+        if (H <= 1536) hipLaunchKernelGGL((band_panel_kernel<512, 3, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
+        else if (H <= 2048) hipLaunchKernelGGL((band_panel_kernel<512, 4, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
+        else if (H <= 2560) hipLaunchKernelGGL((band_panel_kernel<512, 5, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
+        else hipLaunchKernelGGL((band_panel_kernel<512, 6, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
+    } else {                                                            // 3065 <= kl <= 4096
+        if (H <= 4096) hipLaunchKernelGGL((band_panel_kernel<512, 8, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
+        else hipLaunchKernelGGL((band_panel_kernel<512, 9, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
+    }
+}
+
+// The whole tiled solve of G matrices on `st`: three launches per block step (the trailing update only where rows lie below
+// the block), then the blocked back substitution; the launch queue is bounded as in launch_blocked_nb.
+template <int NB>
+hipError_t launch_tiled_nb(const BandArgs& a, const BlkArgs& w, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
+    const int kv = a.kl + a.ku, RC = 256 / NB, ntile = (kv + RC - 1) / RC, nct = (kv + TCT - 1) / TCT;
+    hipError_t err = hipMemsetAsync(w.ju, 0, sizeof(int) * G, st);
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    for (auto& e : ev) if (err == hipSuccess) err = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+    int step = 0;
+    for (int j0 = 0; j0 < a.n && err == hipSuccess; j0 += NB, ++step) {
+        if (step % 64 == 0 && step >= 128) err = hipEventSynchronize(ev[(step / 64) & 1]);
+        if (err != hipSuccess) break;
+        launch_tiled_panel<NB>(a, w, G, st, j0);
+        hipLaunchKernelGGL(band_row_kernel<NB>, dim3(ntile + 1, G), dim3(256), 0, st, a, w, j0, ntile);
+        const int below = std::min(a.kl + NB, a.n - j0) - NB;           // rows of L21; none in a last, short block
+        if (below > 0) {
+            const int nrt = (below + TRT - 1) / TRT;
+            hipLaunchKernelGGL(band_trail_kernel<NB>, dim3((nct + 1) * nrt, G), dim3(TRT), 0, st, a, w, j0, nct, nrt);
+        }
+        if (step % 64 == 63) { err = hipGetLastError(); if (err == hipSuccess) err = hipEventRecord(ev[(step / 64) & 1], st); }
+    }
+    if (err == hipSuccess) {
+        if (kv <= 256) hipLaunchKernelGGL((band_back_blk_kernel<256>), dim3(G), dim3(256), 0, st, a, out, ldo, slots, perm);
+        else hipLaunchKernelGGL((band_back_blk_kernel<1024>), dim3(G), dim3(1024), 0, st, a, out, ldo, slots, perm);
+        err = hipGetLastError();
+    }
+    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+    return err;
+}
+
+hipError_t launch_tiled(const BandArgs& a, const BlkArgs& w, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
+    switch (band_tiled_nb(a.kl, a.ku)) {
+    case BNB: return launch_tiled_nb<BNB>(a, w, G, st, out, ldo, slots, perm);
+    case TNB_MID: return launch_tiled_nb<TNB_MID>(a, w, G, st, out, ldo, slots, perm);
+    default: return launch_tiled_nb<TNB_TALL>(a, w, G, st, out, ldo, slots, perm);
+    }
+}
+
+hipError_t launch_kind(int kind, const BandArgs& a, const BlkArgs& w, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
+    return kind == 1 ? launch_blocked(a, w, G, st, out, ldo, slots, perm) : launch_tiled(a, w, G, st, out, ldo, slots, perm);
+}
+
 // workgroup size from (kl, ku) alone: one wave for narrow bands, where the barriers of every column dominate
 int band_threads(int kl, int ku) {
     const long w = (long)kl * (kl + ku);
@@ -519,7 +726,20 @@ double band_blocked_bytes(int n, int kl, int ku, int G) {
     return 32.0 * G * ((double)(n + nb - 1) / nb) * (kl + nb) * (double)(nb + kl + ku) + 16.0 * G * (double)n * (kl + ku + 1);
 }
 
-// bytes of one solve in the workspace; the blocked method adds its panel of L and its reach
+// the tiled method moves the same upper end of the band per block step, and L21 once per column tile of the trailing update
+double band_tiled_bytes(int n, int kl, int ku, int G) {
+    const int nb = band_tiled_nb(kl, ku);
+    const double steps = (double)(n + nb - 1) / nb, nct = (double)((kl + ku + TCT - 1) / TCT + 1);
+    return G * steps * (32.0 * (kl + nb) * (double)(nb + kl + ku) + 16.0 * (kl + nb) * (double)nb * nct) + 16.0 * G * (double)n * (kl + ku + 1);
+}
+
+int band_class(int kind) { return kind == 1 ? KC_BAND_BLOCKED : (kind == 2 ? KC_BAND_TILED : KC_BAND); }
+double band_kind_bytes(int kind, int n, int kl, int ku, int G) {
+    return kind == 1 ? band_blocked_bytes(n, kl, ku, G) : (kind == 2 ? band_tiled_bytes(n, kl, ku, G) : band_bytes(n, 2 * kl + ku + 1, G));
+}
+
+// bytes of one solve in the workspace; the blocked and the tiled method add their panel of L ((kl + nb) x nb, nb <= BNB) and
+// their reach
 size_t band_per_solve(int n, int kl, int ku, bool blocked) {
     const size_t ldab = 2 * (size_t)kl + ku + 1;
     return sizeof(c128) * (ldab * n + n) + sizeof(int) * (size_t)n
@@ -539,7 +759,7 @@ void band_ws_free(maus_ctx* c) {
 // memory) -- never shrunk; larger batches run in balanced chunks.
 int ensure_band_ws(maus_ctx* c, int want) {
     const int n = c->band_n, ldab = 2 * c->band_kl + c->band_ku + 1;
-    const bool blocked = band_runs_blocked(c->band_method, c->band_kl, c->band_ku);
+    const bool blocked = band_kind(c->band_method, c->band_kl, c->band_ku) != 0;      // the methods that allocate lw and ju
     const size_t per = band_per_solve(n, c->band_kl, c->band_ku, blocked);
     const unsigned long long key = ((unsigned long long)n << 32) | ((unsigned long long)blocked << 31) | (unsigned)ldab;
     const bool same = c->band_ab && c->band_ws_key == key;
@@ -582,7 +802,11 @@ BandArgs band_args(maus_ctx* c) {
     return a;
 }
 
-BlkArgs blk_args(maus_ctx* c) { BlkArgs w; w.lw = c->band_lw; w.ju = c->band_ju; w.lh = c->band_kl + band_nb(c->band_kl, c->band_ku); return w; }
+BlkArgs blk_args(maus_ctx* c) {
+    BlkArgs w; w.lw = c->band_lw; w.ju = c->band_ju;
+    w.lh = c->band_kl + band_kind_nb(band_kind(c->band_method, c->band_kl, c->band_ku), c->band_kl, c->band_ku);
+    return w;
+}
 
 void band_status(int G, const int* info, const int* flags, int32_t* status) {
     for (int g = 0; g < G; ++g) {
@@ -667,7 +891,7 @@ int maus_band_solve(maus_ctx* c, const int* slots, int count, const double* shif
     const int Gmax = (count + nchunks - 1) / nchunks;
     std::vector<int> h_info(Gmax), h_flags(Gmax);
     const BandArgs a = band_args(c);
-    const bool blocked = band_runs_blocked(c->band_method, a.kl, a.ku);
+    const int kind = band_kind(c->band_method, a.kl, a.ku);
     const BlkArgs w = blk_args(c);
     for (int off = 0; off < count; off += Gmax) {
         const int G = std::min(Gmax, count - off);
@@ -675,14 +899,13 @@ int maus_band_solve(maus_ctx* c, const int* slots, int count, const double* shif
         if (maus_h2d(c, c->d_c1, shift + 2 * (size_t)off, sizeof(c128) * G, c->st)) return -1;
         if (maus_h2d(c, c->d_r1, psi + off, sizeof(double) * G, c->st)) return -1;
         {
-            ProfScope ps(c, blocked ? KC_BAND_BLOCKED : KC_BAND, band_flops(a.n, a.kl, a.ku, G),
-                         blocked ? band_blocked_bytes(a.n, a.kl, a.ku, G) : band_bytes(a.n, a.ldab, G));
+            ProfScope ps(c, band_class(kind), band_flops(a.n, a.kl, a.ku, G), band_kind_bytes(kind, a.n, a.kl, a.ku, G));
             HIPCHK(c, hipMemsetAsync(a.info, 0, sizeof(int) * G, c->st));
             HIPCHK(c, hipMemsetAsync(a.flags, 0, sizeof(int) * G, c->st));
             HIPCHK(c, hipMemsetAsync(a.ab, 0, sizeof(c128) * (size_t)a.ldab * a.n * G, c->st));
             hipLaunchKernelGGL(band_build_csr_kernel, dim3((a.n + 255) / 256, G), dim3(256), 0, c->st, a, c->Acsr.ptr, c->Acsr.idx,
                                c->Acsr.val, c->band_perm, c->band_iperm, c->d_c1, c->d_r1, rhs_mode, c->X, c->ldp, c->d_slots, c->b);
-            if (blocked) HIPCHK(c, launch_blocked(a, w, G, c->st, c->W, c->ldp, c->d_slots, c->band_perm));
+            if (kind) HIPCHK(c, launch_kind(kind, a, w, G, c->st, c->W, c->ldp, c->d_slots, c->band_perm));
             else {
                 launch_factor(a, G, c->st);
                 launch_back(a, G, c->st, c->W, c->ldp, c->d_slots, c->band_perm);
@@ -701,7 +924,7 @@ int maus_band_workspace_allocs(maus_ctx* c) { return c ? c->band_allocs : -1; }
 
 int maus_band_set_method(maus_ctx* c, int method) {
     if (!c) return -1;
-    if (method != 0 && method != 1) FAIL(c, "maus_band_set_method: method must be 0 (column) or 1 (blocked)");
+    if (method < 0 || method > 2) FAIL(c, "maus_band_set_method: method must be 0 (column), 1 (blocked) or 2 (tiled)");
     c->band_method = method;                                            // the workspace follows at its next use (ensure_band_ws)
     return 0;
 }
@@ -711,9 +934,9 @@ int maus_band_get_method(maus_ctx* c) { return c ? c->band_method : -1; }
 int maus_band_kernel_for(maus_ctx* c, int n, int kl, int ku, int* nb_out) {
     if (!c) return -1;
     if (n <= 0 || kl < 0 || ku < 0) FAIL(c, "maus_band_kernel_for: bad sizes");
-    const bool blocked = band_runs_blocked(c->band_method, kl, ku);
-    if (nb_out) *nb_out = blocked ? band_nb(kl, ku) : 1;
-    return blocked ? 1 : 0;
+    const int kind = band_kind(c->band_method, kl, ku);
+    if (nb_out) *nb_out = band_kind_nb(kind, kl, ku);
+    return kind;
 }
 
 int maus_band_lu_host(maus_ctx* c, int count, int n, int kl, int ku, const double* ab, const double* b, double* x_out,
@@ -728,8 +951,9 @@ int maus_band_lu_host(maus_ctx* c, int count, int n, int kl, int ku, const doubl
     auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
     const size_t o_ab = take(abb * count), o_x = take(xb * count), o_o = take(xb * count), o_p = take(ib * count),
                  o_i = take(sizeof(int) * count), o_f = take(sizeof(int) * count);
-    const bool blocked = band_runs_blocked(c->band_method, kl, ku);
-    BlkArgs w; w.lw = nullptr; w.ju = nullptr; w.lh = kl + band_nb(kl, ku);
+    const int kind = band_kind(c->band_method, kl, ku);
+    const bool blocked = kind != 0;
+    BlkArgs w; w.lw = nullptr; w.ju = nullptr; w.lh = kl + band_kind_nb(kind, kl, ku);
     const size_t o_l = take(blocked ? sizeof(c128) * (size_t)(kl + BNB) * BNB * count : 0), o_j = take(blocked ? sizeof(int) * count : 0);
     if (ensure_scratch(c, off)) return -1;
     char* base = (char*)c->scratch;
@@ -741,12 +965,11 @@ int maus_band_lu_host(maus_ctx* c, int count, int n, int kl, int ku, const doubl
     HIPCHK(c, hipMemsetAsync(a.info, 0, sizeof(int) * count, c->st));
     HIPCHK(c, hipMemsetAsync(a.flags, 0, sizeof(int) * count, c->st));
     {
-        ProfScope ps(c, blocked ? KC_BAND_BLOCKED : KC_BAND, band_flops(n, kl, ku, count),
-                     blocked ? band_blocked_bytes(n, kl, ku, count) : band_bytes(n, a.ldab, count));
+        ProfScope ps(c, band_class(kind), band_flops(n, kl, ku, count), band_kind_bytes(kind, n, kl, ku, count));
         hipLaunchKernelGGL(band_scan_kernel, dim3(64, count), dim3(256), 0, c->st, a);
         if (blocked) {
             hipLaunchKernelGGL(band_zero_fill_kernel, dim3(64, count), dim3(256), 0, c->st, a);
-            HIPCHK(c, launch_blocked(a, w, count, c->st, out, n, nullptr, nullptr));
+            HIPCHK(c, launch_kind(kind, a, w, count, c->st, out, n, nullptr, nullptr));
         } else {
             launch_factor(a, count, c->st);
             launch_back(a, count, c->st, out, n, nullptr, nullptr);

@@ -237,7 +237,7 @@ def tridiagonal_eigenvalues(ctx, d, e):
     return np.sort(sla.eigvalsh_tridiagonal(d, e))
 
 
-SPARSE_DIRECT_MODES = ("auto", "dense", "band", "blocked")
+SPARSE_DIRECT_MODES = ("auto", "dense", "band", "blocked", "tiled")
 
 
 def sparse_direct_mode(mode):
@@ -363,7 +363,8 @@ class DeviceEngine:
         # direct solves of a sparse matrix: 'dense' densifies H_k into the LU workspace (n <= maus_lu_max_n()),
         # 'band' runs the band LU in the ordering of band.band_order, 'auto' the first up to maus_lu_max_n() and the second
         # above; 'blocked' is 'band' with the blocked kernels (zgbtrf's schedule, every step a launch over the whole device;
-        # opt-in, 'auto' never picks it).  MAUS_SPARSE_DIRECT sets the default.  Chosen once per bound matrix (_band).
+        # opt-in, 'auto' never picks it); 'tiled' is 'blocked' with the update tiled over rows as well, for bands up to
+        # kl = 4096 (opt-in too).  MAUS_SPARSE_DIRECT sets the default.  Chosen once per bound matrix (_band).
         self.sparse_direct = sparse_direct_mode(sparse_direct)
         # sparse Hermitian shortcut (AMS:186-216): 'dense' = one scipy.linalg.eigh of A.toarray() per matrix, 'lanczos' =
         # thick-restart Lanczos on the CSR matrix on the device, 'auto' the first up to maus_lu_max_n() and the second above.
@@ -452,7 +453,7 @@ class DeviceEngine:
 
     def uses_band(self, n: int) -> bool:
         """Whether a sparse n x n matrix takes the band solve (sparse_direct; 'auto': above maus_lu_max_n())."""
-        if self.sparse_direct in ("band", "blocked"):
+        if self.sparse_direct in ("band", "blocked", "tiled"):
             return True
         if self.sparse_direct == "dense":
             return False
@@ -474,8 +475,10 @@ class DeviceEngine:
         pay neither the ordering nor the host copy of the pattern."""
         if not self._band_ready:
             perm, kl, ku = self.band_shape(self._bound)
-            if self.sparse_direct == "blocked":  # the only mode that touches the method: contexts without it keep working
+            if self.sparse_direct == "blocked":  # the only modes that touch the method: contexts without it keep working
                 self.ctx.band_set_method(1)
+            elif self.sparse_direct == "tiled":
+                self.ctx.band_set_method(2)
             self.ctx.band_prepare(perm)
             self._band_ready = True
 

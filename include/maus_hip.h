@@ -116,10 +116,13 @@ int maus_matrix_is_sparse(maus_ctx* ctx);
  * maus_band_workspace_allocs: (re-)allocations of the band workspace on this context.
  * maus_band_set_method: which kernels maus_band_solve, maus_band_reserve and maus_band_lu_host run on this context --
  *   0 the column kernel (one workgroup per matrix walks the columns; the default), 1 the blocked method (zgbtrf's
- *   schedule in blocks of 16 columns, every step a launch over (matrix, tile)).  Under method 1 a band with kl < 16 or
- *   kl > 1024 still runs the column kernel.  The method outlives the bound matrix; same status contract either way.
+ *   schedule in blocks of 16 columns, every step a launch over (matrix, tile)), 2 the tiled method (the blocked
+ *   schedule with the block row and the trailing update as launches of their own over (column tile, row tile); blocks of
+ *   16, 8 or 4 columns by kl).  Under method 1 a band with kl < 16 or kl > 1024 still runs the column kernel, under
+ *   method 2 one with kl < 16 or kl > 4096.  For a band that both take, methods 1 and 2 give the same bits.  The method
+ *   outlives the bound matrix; same status contract in every method.
  * maus_band_get_method: the current method.
- * maus_band_kernel_for: what (n, kl, ku) runs under the current method: returns 0 (column kernel) or 1 (blocked);
+ * maus_band_kernel_for: what (n, kl, ku) runs under the current method: returns 0 (column kernel), 1 (blocked) or 2 (tiled);
  *   nb_out (may be NULL): the block width, 1 for the column kernel. */
 int maus_sparse_max_n(void);
 int maus_band_prepare(maus_ctx* ctx, const int32_t* perm, int n, int* kl_out, int* ku_out);
@@ -384,7 +387,8 @@ int maus_timer_stop(maus_ctx* ctx, float* ms_out);
  * classes: 0 zgemm (LU trailing update with K>=256 / A@X), 1 lu_panel, 2 trsm, 3 (unused since round 2: row-swap sweeps), 4 build_H, 5 backsolve,
  * 6 vector ops, 7..10 zgemm inside the LU recursion with K = 128 / 64 / 32 / 16, 11 CSR products, 12 band solves,
  * 13 lanczos (reorthogonalisation, restart, match of the sparse Hermitian shortcut), 14 band solves by the blocked method
- * (maus_band_set_method; bytes: the band moved once per block step over the full reach kl + ku, not an MFMA class) */
+ * (maus_band_set_method; bytes: the band moved once per block step over the full reach kl + ku, not an MFMA class),
+ * 15 band solves by the tiled method (bytes: as 14 plus L21 once per column tile of the trailing update) */
 /* on = 1: event pairs around every launch of every class; on = 2: around the K>=256 zgemm launches only (class 0;
  * long kernels, so cheap enough for a timed region -- full bracketing costs 3-5 % of throughput; MAUS_PROF_STRIDE
  * can thin them out, each sample then stands for `stride` launches); 0: off */

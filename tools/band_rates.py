@@ -12,6 +12,15 @@ LU at n = 16384 for the same 64 shifted systems, and MAUS_Solver linear loop bod
 and on the GMRES path.
 
     python tools/band_rates.py [--out profiles/band_blocked_rates.txt]
+
+With --table tiled: the tiled method (maus_band_set_method(ctx, 2)) beside the other two -> profiles/band_tiled_rates.txt.
+First the bands only it takes, against the column kernel that runs there otherwise: the 3-D 7-point operator on 40^3
+(complex values, shuffled, reordered) alone and in a batch of 8, and a five-diagonal band (offsets 0, +-1, +-k with random
+complex values of one size, so that the factorisation pivots and fills the whole band) at n = 32768 with kl = ku = 2048 and
+4096 in the identity ordering.  The column kernel takes minutes there: it is timed alone only, one call, no warm-up call.
+Then the six rows of the blocked table, tiled beside blocked, same systems.
+
+    python tools/band_rates.py --table tiled [--out profiles/band_tiled_rates.txt]
 """
 import argparse
 import os
@@ -38,10 +47,32 @@ def five_point(m, seed=0):
     return L[p][:, p].tocsr()
 
 
-def bind(ctx, A, P):
+def seven_point(m, seed=0):
+    rng = np.random.default_rng(seed)
+    I = sp.identity(m)
+    T = sp.diags([-1.0, 6.0, -1.0], [-1, 0, 1], shape=(m, m))
+    O = sp.diags([-1.0, -1.0], [-1, 1], shape=(m, m))
+    L = (sp.kron(I, sp.kron(I, T)) + sp.kron(I, sp.kron(O, I)) + sp.kron(O, sp.kron(I, I))).tocsr().astype(np.complex128)
+    L.data = L.data * (1.0 + 0.3j * rng.standard_normal(L.nnz))
+    p = rng.permutation(m ** 3)
+    return L[p][:, p].tocsr()
+
+
+def five_diagonals(n, k, seed=0):
+    """Offsets 0, +-1, +-k, complex normal values: kl = ku = k in the identity ordering, and partial pivoting fills the band."""
+    rng = np.random.default_rng(seed)
+    offs = [-k, -1, 0, 1, k]
+    return sp.diags([rng.standard_normal(n - abs(o)) + 1j * rng.standard_normal(n - abs(o)) for o in offs], offs, format="csr")
+
+
+def bind(ctx, A, P, identity=False):
     ctx.set_matrix_csr(A)
     perm, kl, ku = band_order(A)
-    ctx.band_prepare(perm)
+    if identity:
+        perm = np.arange(A.shape[0])
+        kl, ku = ctx.band_prepare(perm)
+    else:
+        ctx.band_prepare(perm)
     ctx.pop_reserve(P)
     rng = np.random.default_rng(1)
     n = A.shape[0]
@@ -49,13 +80,14 @@ def bind(ctx, A, P):
     return kl, ku
 
 
-def timed_band(ctx, count, klass="band", reps=2):
+def timed_band(ctx, count, klass="band", reps=2, warm=True):
     rng = np.random.default_rng(2)
     shift = rng.standard_normal(count) + 1j * rng.standard_normal(count)
     psi = np.full(count, 1e-3)
     slots = np.arange(count)
     ctx.band_reserve(count)
-    ctx.band_solve(slots, shift, psi, 0)                       # warm-up
+    if warm:
+        ctx.band_solve(slots, shift, psi, 0)                   # warm-up
     best = None
     for _ in range(reps):
         ctx.profile_enable(False)
@@ -97,11 +129,87 @@ def loop_rate(compat, direct="auto", bodies=3):
     return steps / wall, (pr["band"]["ms"] + pr["band_blocked"]["ms"]) / bodies, pr["spmm"]["ms"] / bodies
 
 
+KCLASS = {_cabi.BAND_COLUMN: "band", _cabi.BAND_BLOCKED: "band_blocked", _cabi.BAND_TILED: "band_tiled"}
+
+
+def table_row(ctx, n, kl, ku, P, method, name, base_ms=None, **timing):
+    """One timed row of `method` on the bound system; returns (line, ms of the batch)."""
+    ctx.band_set_method(method)
+    kern, nb = ctx.band_kernel_for(n, kl, ku)
+    pr, wall = timed_band(ctx, P, KCLASS[kern], **timing)
+    s = pr["ms"] / 1e3
+    tf, tb = pr["flops"] / s / 1e12, pr["bytes"] / s / 1e12
+    tc, tm = pr["flops"] / PEAK_F64, pr["bytes"] / HBM
+    bound = "fp64" if tc >= tm else "HBM"
+    up = "" if base_ms is None else f"{base_ms / (pr['ms'] / P):.2f}x"
+    line = (f"{n:>7} {kl:>4} {ku:>4} {P:>5} {name:>8} {nb:>3} {pr['ms'] / P:>9.3f} {tf:>8.3f} {tb:>6.2f} {bound:>5} "
+            f"{max(tc, tm) / s:>7.2%} {up:>8}")
+    print(line, flush=True)
+    return line, pr["ms"]
+
+
+def main_tiled(args):
+    ctx = _cabi.Context(0)
+    info = ctx.device_info()
+    head = (f"{'n':>7} {'kl':>4} {'ku':>4} {'batch':>5} {'method':>8} {'nb':>3} {'ms/solve':>9} {'TFLOP/s':>8} {'TB/s':>6} {'bound':>5} "
+            f"{'share':>7} {'speed-up':>8}")
+    lines = [f"# band solves, csrc/band.hip, the tiled method beside the column kernel and the blocked method in one process -- "
+             f"{info['name']}, {info['cus']} CUs",
+             "# ms / solve from the 'band' / 'band_blocked' / 'band_tiled' profile class (HIP events around build + factor + solve of",
+             "# one batch); bound = max(flops / 78.6 TFLOP/s fp64, bytes / 8 TB/s), bytes an upper end for blocked and tiled;",
+             "# share = bound time / measured time",
+             "",
+             "# bands above kl = 1024: tiled (the better of two timed calls after one warm-up call) against the column kernel, which",
+             "# runs there in every other mode (one timed call of a lone solve, no warm-up call: it takes minutes);",
+             "# speed-up = column ms per solve (alone) / tiled ms per solve",
+             head]
+    wide = [("7-point 40^3", lambda: seven_point(40, 40), False, (1, 8))]
+    wide += [(f"five diagonals k = {k}", (lambda k=k: five_diagonals(32768, k, k)), True, (1,)) for k in (2048, 4096)]
+    for label, make, identity, batches in wide:
+        if args.only and not any(o in label for o in args.only.split(",")):
+            continue
+        A = make()
+        n = A.shape[0]
+        kl, ku = bind(ctx, A, max(batches), identity=identity)
+        lines.append(f"# {label}")
+        col = None
+        if not args.no_column:
+            line, col = table_row(ctx, n, kl, ku, 1, _cabi.BAND_COLUMN, "column", reps=1, warm=False)
+            lines.append(line)
+        for P in batches:
+            line, _ = table_row(ctx, n, kl, ku, P, _cabi.BAND_TILED, "tiled", base_ms=col)
+            lines.append(line)
+    lines += ["", "# the six rows of profiles/band_blocked_rates.txt (2-D 5-point operator), tiled beside blocked, the better of two timed",
+              "# calls after one warm-up call each; speed-up = blocked ms / tiled ms (no bar: neither is a default)", head]
+    cache = {}
+    for item in ([] if args.only else args.sizes.split(",")):
+        m, P = (int(v) for v in item.split(":"))
+        n = m * m
+        if m not in cache:
+            A = five_point(m, m)
+            cache.clear()
+            cache[m] = (A, bind(ctx, A, 64))
+        A, (kl, ku) = cache[m]
+        line, blk = table_row(ctx, n, kl, ku, P, _cabi.BAND_BLOCKED, "blocked")
+        lines.append(line)
+        line, _ = table_row(ctx, n, kl, ku, P, _cabi.BAND_TILED, "tiled", base_ms=blk / P)
+        lines.append(line)
+    ctx.close()
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/band_blocked_rates.txt")
+    ap.add_argument("--table", choices=("blocked", "tiled"), default="blocked")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--sizes", default="128:1,128:64,256:1,256:64,512:1,512:8")
+    ap.add_argument("--only", default=None, help="--table tiled: the wide rows whose label contains one of these, nothing else")
+    ap.add_argument("--no-column", action="store_true", help="--table tiled: leave the column kernel's minutes out")
     args = ap.parse_args()
+    args.out = args.out or f"profiles/band_{args.table}_rates.txt"
+    if args.table == "tiled":
+        return main_tiled(args)
     ctx = _cabi.Context(0)
     info = ctx.device_info()
     lines = [f"# band solves, csrc/band.hip, column kernel and blocked method in one process -- {info['name']}, {info['cus']} CUs",
