@@ -23,7 +23,7 @@ SYMBOLS = [
     "maus_profile_enable", "maus_profile_read", "maus_sync", "maus_mt19937_jump",
     "maus_lanczos_begin", "maus_lanczos_inject", "maus_lanczos_extend", "maus_lanczos_restart", "maus_lanczos_finish", "maus_herm_match_rows", "maus_get_ritz_rows",
     "maus_sparse_max_n", "maus_band_prepare", "maus_band_reserve", "maus_band_solve", "maus_band_lu_host", "maus_band_workspace_allocs",
-    "maus_band_set_method", "maus_band_get_method", "maus_band_kernel_for",
+    "maus_band_set_method", "maus_band_get_method", "maus_band_kernel_for", "maus_band_outer_nb",
     "maus_device_count", "maus_comm_unique_id", "maus_comm_init", "maus_comm_destroy", "maus_comm_info",
     "maus_comm_allgather_records", "maus_comm_allgather_rows", "maus_comm_bcast", "maus_comm_bcast_eigvecs", "maus_comm_set_matrix", "maus_comm_stats",
 ]
@@ -34,8 +34,9 @@ POP_X, POP_U, POP_W, POP_Y = 0, 1, 2, 3
 KIND_EIG, KIND_LINEAR, KIND_SVD = 1, 2, 3
 PERT_NONE, PERT_UNIFORM, PERT_MT19937 = 0, 1, 2
 KC_NAMES = ["zgemm", "lu_panel", "trsm", "laswp", "build_h", "backsolve", "vector",
-            "zgemm_k128", "zgemm_k64", "zgemm_k32", "zgemm_k16", "spmm", "band", "lanczos", "band_blocked", "band_tiled"]
+            "zgemm_k128", "zgemm_k64", "zgemm_k32", "zgemm_k16", "spmm", "band", "lanczos", "band_blocked", "band_tiled", "band_wide"]
 BAND_COLUMN, BAND_BLOCKED, BAND_TILED = 0, 1, 2      # maus_band_set_method
+BAND_WIDE = 4                                        # (there is no method 3)
 SPMM_SCHEDULES = {0: None, 1: "rows", 2: "wave"}     # maus_matrix_is_sparse: dense / lane per row / wave per row
 
 
@@ -134,6 +135,7 @@ def load_library():
         "maus_band_set_method": ([vp, C.c_int], C.c_int),
         "maus_band_get_method": ([vp], C.c_int),
         "maus_band_kernel_for": ([vp, C.c_int, C.c_int, C.c_int, ip], C.c_int),
+        "maus_band_outer_nb": ([vp, C.c_int, C.c_int, C.c_int], C.c_int),
         "maus_device_count": ([], C.c_int),
         "maus_comm_unique_id": ([C.c_char_p], C.c_int),
         "maus_comm_init": ([vp, C.c_int, C.c_int, C.c_char_p], C.c_int),
@@ -624,19 +626,26 @@ class Context:
         return int(self.lib.maus_band_workspace_allocs(self.h))
 
     def band_set_method(self, method):
-        """The kernels of the band entry points: BAND_COLUMN (the default), BAND_BLOCKED or BAND_TILED; kept across matrices."""
+        """The kernels of the band entry points: BAND_COLUMN (the default), BAND_BLOCKED, BAND_TILED or BAND_WIDE; kept across
+        matrices."""
         self._ck(self.lib.maus_band_set_method(self.h, int(method)), "maus_band_set_method")
 
     def band_method(self) -> int:
         return int(self.lib.maus_band_get_method(self.h))
 
     def band_kernel_for(self, n, kl, ku):
-        """(kernel, nb) that an (n, kl, ku) band runs under the current method: (BAND_COLUMN, 1), (BAND_BLOCKED, nb) or
-        (BAND_TILED, nb)."""
+        """(kernel, nb) that an (n, kl, ku) band runs under the current method: (BAND_COLUMN, 1), (BAND_BLOCKED, nb),
+        (BAND_TILED, nb) or (BAND_WIDE, nb of the inner steps)."""
         nb = C.c_int()
         k = self.lib.maus_band_kernel_for(self.h, int(n), int(kl), int(ku), C.byref(nb))
         self._ck(min(k, 0), "maus_band_kernel_for")
         return int(k), int(nb.value)
+
+    def band_outer_nb(self, n, kl, ku) -> int:
+        """Width of the outer block (64) where an (n, kl, ku) band runs the wide method under the current method, else 0."""
+        k = self.lib.maus_band_outer_nb(self.h, int(n), int(kl), int(ku))
+        self._ck(min(k, 0), "maus_band_outer_nb")
+        return int(k)
 
     def band_lu(self, ab, b, kl, ku, method=None):
         """zgbtrf + zgbtrs on the device: ab[count, 2kl+ku+1, n] in LAPACK's band layout (SciPy's `ab`), b[count, n] ->

@@ -61,10 +61,23 @@ def runs_tiled(kl: int, ku: int) -> bool:
     return TILED_MIN_KL <= kl <= TILED_MAX_KL
 
 
-def band_bytes_per_solve(n: int, kl: int, ku: int, blocked: bool = False, tiled: bool = False) -> int:
+WIDE_MIN_KL = 64                # the wide method's range under sparse_direct='wide': below it the outer block is wider than
+WIDE_MAX_KL = 4096              # the band's reach (the tiled method runs from kl = 16), above it the inner panel ends
+WIDE_NBO = 64                   # columns of the outer block, csrc/band.hip
+
+
+def runs_wide(kl: int, ku: int) -> bool:
+    """Whether the wide method takes a (kl, ku) band when it is selected (band_runs_wide in csrc/band.hip)."""
+    return WIDE_MIN_KL <= kl <= WIDE_MAX_KL
+
+
+def band_bytes_per_solve(n: int, kl: int, ku: int, blocked: bool = False, tiled: bool = False, wide: bool = False) -> int:
     """Device memory of one band solve: the band storage, the right-hand side and the pivots (csrc/band.hip); with
-    `blocked` (`tiled`), and a band the blocked (tiled) method takes, its panel of L and its reach as well."""
+    `blocked` (`tiled`), and a band the blocked (tiled) method takes, its panel of L and its reach as well; with `wide` the
+    tiled method's where that runs, and the L of the outer block ((kl + 64) x 64) where the wide method does."""
     per = 16 * ((2 * kl + ku + 1) * n + n) + 4 * n
-    if (blocked and runs_blocked(kl, ku)) or (tiled and runs_tiled(kl, ku)):
+    if (blocked and runs_blocked(kl, ku)) or ((tiled or wide) and runs_tiled(kl, ku)):
         per += 16 * (kl + BLOCKED_NB) * BLOCKED_NB + 4
+    if wide and runs_wide(kl, ku):
+        per += 16 * (kl + WIDE_NBO) * WIDE_NBO
     return per

@@ -20,6 +20,8 @@
 // schedule, every step a launch over (matrix, tile)) for bands with BLK_MIN_KL <= kl <= BLK_MAX_KL; same storage, build kernel,
 // pivot rule and status contract.  maus_band_set_method(ctx, 2) selects the tiled method after it (the blocked schedule with the
 // block row and the trailing update as launches of their own over (column tile, row tile)) for kl up to TIL_MAX_KL.
+// maus_band_set_method(ctx, 4) selects the wide method at the end (zgbtrf's two levels: outer blocks of 64 columns factored by
+// the tiled steps, then one rank-64 update on the MFMA pipe) for WID_MIN_KL <= kl <= WID_MAX_KL.
 #include "ctx.h"
 #include <climits>
 #include <utility>
@@ -213,7 +215,9 @@ constexpr int BTC = 4;                                  // columns per update ti
 constexpr int BLK_MIN_KL = 16;                          // narrower bands run the column kernel ...
 constexpr int BLK_MAX_KL = 1024;                        // ... and so do bands too tall for the one-workgroup panel
 
-struct BlkArgs { c128* lw; int* ju; int lh; };          // lw: (lh x nb) column-major per matrix, lh = kl + nb; ju: reach so far
+// lw: the L of a block step, column-major with leading dimension lh, matrix g at lw + g * ls (blocked and tiled: lh = kl + nb,
+// ls = lh * nb); ju: reach so far
+struct BlkArgs { c128* lw; int* ju; int lh; long ls; };
 
 bool band_runs_blocked(int method, int kl, int ku) { (void)ku; return method == 1 && kl >= BLK_MIN_KL && kl <= BLK_MAX_KL; }
 int band_nb(int kl, int ku) { (void)ku; return kl + BNB <= 1024 ? BNB : BNB_TALL; }
@@ -247,7 +251,7 @@ band_panel_kernel(BandArgs a, BlkArgs w, int j0)
     const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = a.n, kl = a.kl, ku = a.ku, kv = kl + ku, ldab = a.ldab;
     c128* ab = a.ab + bix(a, g);
-    c128* lw = w.lw + (long)g * w.lh * NB;
+    c128* lw = w.lw + (long)g * w.ls;
     int* ipiv = a.ipiv + (long)g * n;
     const int jb = min(NB, n - j0), H = min(kl + jb, n - j0);
     auto at = [&](int r, int j) -> c128& { return ab[r + (long)j * ldab]; };
@@ -360,7 +364,7 @@ band_update_kernel(BandArgs a, BlkArgs w, int j0, int ntile)
         ncol = min(BTC, ju - c0 + 1);
     }
     c128* ab = a.ab + bix(a, g);
-    const c128* lw = w.lw + (long)g * lh * NB;
+    const c128* lw = w.lw + (long)g * w.ls;
     // element i of column q at col(q)[i], stored from row lo(q) on
     auto col = [&](int q) -> c128* { return rhs ? a.x + (long)g * n : ab + (long)(c0 + q) * ldab + kv - (c0 + q); };
     auto lo = [&](int q) { return rhs ? 0 : c0 + q - kv; };
@@ -512,9 +516,24 @@ int band_tiled_nb(int kl, int ku) {
     return kl + BNB <= TIL_NB16_H ? BNB : (kl + TNB_MID <= 3072 ? TNB_MID : TNB_TALL);
 }
 
-// 0: the column kernel, 1: blocked, 2: tiled -- what a (kl, ku) band runs under `method`; the block width with it
-int band_kind(int method, int kl, int ku) { return band_runs_blocked(method, kl, ku) ? 1 : (band_runs_tiled(method, kl, ku) ? 2 : 0); }
-int band_kind_nb(int kind, int kl, int ku) { return kind == 1 ? band_nb(kl, ku) : (kind == 2 ? band_tiled_nb(kl, ku) : 1); }
+// the wide method (maus_band_set_method(ctx, 4), further down): an outer block of NBO columns over the tiled method's steps
+#ifndef MAUS_BAND_NBO
+#define MAUS_BAND_NBO 64                                // 32 was timed and rejected; 64 is one lane per top row
+#endif
+constexpr int NBO = MAUS_BAND_NBO;                      // columns per outer block
+static_assert(NBO == 64 || NBO == 32, "the outer block row maps the top rows of a column to the lanes of one wave");
+constexpr int WID_MIN_KL = 64;                          // below it the outer block is wider than the band's reach: tiled runs
+constexpr int WID_MAX_KL = TIL_MAX_KL;
+
+bool band_runs_wide(int method, int kl, int ku) { (void)ku; return method == 4 && kl >= WID_MIN_KL && kl <= WID_MAX_KL; }
+
+// 0: the column kernel, 1: blocked, 2: tiled, 4: wide -- what a (kl, ku) band runs under `method`; the (inner) block width
+// with it.  Under method 4 a band with TIL_MIN_KL <= kl < WID_MIN_KL runs exactly what the tiled method runs.
+int band_kind(int method, int kl, int ku) {
+    if (method == 4) return band_runs_wide(4, kl, ku) ? 4 : (kl < WID_MIN_KL && band_runs_tiled(2, kl, ku) ? 2 : 0);
+    return band_runs_blocked(method, kl, ku) ? 1 : (band_runs_tiled(method, kl, ku) ? 2 : 0);
+}
+int band_kind_nb(int kind, int kl, int ku) { return kind == 1 ? band_nb(kl, ku) : (kind == 2 || kind == 4 ? band_tiled_nb(kl, ku) : 1); }
 
 // Block row of block step j0: workgroup (t, g) takes the 256 / NB columns from c0 right of the panel of matrix g, workgroup
 // (ntile, g) its right-hand side.  A column keeps 2 NB elements in LDS: slots 0 .. NB - 1 its rows j0 .. j0 + NB - 1, slot
@@ -522,7 +541,7 @@ int band_kind_nb(int kind, int kl, int ku) { return kind == 1 ? band_nb(kl, ku) 
 // Rows above a column's first stored row are read as zero and not written, as band_update_kernel.
 template <int NB>
 __global__ void __launch_bounds__(256)
-band_row_kernel(BandArgs a, BlkArgs w, int j0, int ntile)
+band_row_kernel(BandArgs a, BlkArgs w, int j0, int ntile, int cap)
 {
     constexpr int NT = 256, RC = NT / NB, SL = 2 * NB;
     __shared__ c128 s_v[RC * SL];
@@ -535,12 +554,12 @@ band_row_kernel(BandArgs a, BlkArgs w, int j0, int ntile)
     const int c0 = j0 + jb + t * RC;
     int ncol = 1;
     if (!rhs) {
-        const int ju = w.ju[g];
+        const int ju = min(w.ju[g], cap);                            // cap: INT_MAX, or the last column of the wide method's outer block
         if (c0 > ju) return;
         ncol = min(RC, ju - c0 + 1);
     }
     c128* ab = a.ab + bix(a, g);
-    const c128* lw = w.lw + (long)g * lh * NB;
+    const c128* lw = w.lw + (long)g * w.ls;
     auto col = [&](int q) -> c128* { return rhs ? a.x + (long)g * n : ab + (long)(c0 + q) * ldab + kv - (c0 + q); };
     auto lo = [&](int q) { return rhs ? 0 : c0 + q - kv; };
     if (tid < NB) {
@@ -591,7 +610,7 @@ band_row_kernel(BandArgs a, BlkArgs w, int j0, int ntile)
 // the band storage is contiguous in the row, so the loads and stores of a wave coalesce.
 template <int NB>
 __global__ void __launch_bounds__(TRT)
-band_trail_kernel(BandArgs a, BlkArgs w, int j0, int nct, int nrt)
+band_trail_kernel(BandArgs a, BlkArgs w, int j0, int nct, int nrt, int cap)
 {
     __shared__ c128 s_u[TCT * NB];
     const int ct = blockIdx.x / nrt, rt = blockIdx.x % nrt, g = blockIdx.y, tid = threadIdx.x;
@@ -601,12 +620,12 @@ band_trail_kernel(BandArgs a, BlkArgs w, int j0, int nct, int nrt)
     const int c0 = j0 + NB + ct * TCT;
     int ncol = 1;
     if (!rhs) {
-        const int ju = w.ju[g];
+        const int ju = min(w.ju[g], cap);
         if (c0 > ju) return;
         ncol = min(TCT, ju - c0 + 1);
     }
     c128* ab = a.ab + bix(a, g);
-    const c128* lw = w.lw + (long)g * lh * NB;
+    const c128* lw = w.lw + (long)g * w.ls;
     auto col = [&](int q) -> c128* { return rhs ? a.x + (long)g * n : ab + (long)(c0 + q) * ldab + kv - (c0 + q); };
     auto lo = [&](int q) { return rhs ? 0 : c0 + q - kv; };
     for (int e = tid; e < ncol * NB; e += TRT) {
@@ -662,11 +681,11 @@ hipError_t launch_tiled_nb(const BandArgs& a, const BlkArgs& w, int G, hipStream
         if (step % 64 == 0 && step >= 128) err = hipEventSynchronize(ev[(step / 64) & 1]);
         if (err != hipSuccess) break;
         launch_tiled_panel<NB>(a, w, G, st, j0);
-        hipLaunchKernelGGL(band_row_kernel<NB>, dim3(ntile + 1, G), dim3(256), 0, st, a, w, j0, ntile);
+        hipLaunchKernelGGL(band_row_kernel<NB>, dim3(ntile + 1, G), dim3(256), 0, st, a, w, j0, ntile, INT_MAX);
         const int below = std::min(a.kl + NB, a.n - j0) - NB;           // rows of L21; none in a last, short block
         if (below > 0) {
             const int nrt = (below + TRT - 1) / TRT;
-            hipLaunchKernelGGL(band_trail_kernel<NB>, dim3((nct + 1) * nrt, G), dim3(TRT), 0, st, a, w, j0, nct, nrt);
+            hipLaunchKernelGGL(band_trail_kernel<NB>, dim3((nct + 1) * nrt, G), dim3(TRT), 0, st, a, w, j0, nct, nrt, INT_MAX);
         }
         if (step % 64 == 63) { err = hipGetLastError(); if (err == hipSuccess) err = hipEventRecord(ev[(step / 64) & 1], st); }
     }
@@ -687,7 +706,264 @@ hipError_t launch_tiled(const BandArgs& a, const BlkArgs& w, int G, hipStream_t 
     }
 }
 
+// ---- the wide method (maus_band_set_method(ctx, 4)) ---------------------------------------------------------
+// zgbtrf's two levels: an outer block of NBO columns is factored by the tiled method's steps of nb = band_tiled_nb columns,
+// their block row and trailing update stopping at the outer block's last column (`cap`); the right-hand side goes with the
+// inner steps as it does in the tiled method.  The L of the whole outer block is kept in LW[matrix][(kl + NBO) x NBO],
+// column-major, in the block's final row order: the inner panels write their L straight into it (BlkArgs::lw offset by the
+// step's place in the block) and the interchanges of a step are applied to the LW columns left of it (band_lw_swap_kernel,
+// which also clears the few rows of the step's own columns that the panel does not reach).
+// Then two launches take everything right of the block up to the reach ju:
+//   outer row       one workgroup per ORC columns: the NBO interchanges in order and U12 = L11^-1 A12 on the 2 NBO elements
+//                   of a column that they touch; a wave owns whole columns, a lane one of the NBO top rows, and row k reaches
+//                   the others through v_readlane -- no barrier inside the solve.
+//   outer trailing  A22 -= L21 U12 with K = NBO on v_mfma_f64_16x16x4_f64, one workgroup per (OCT columns, ORT rows), a wave
+//                   32 rows x OCT columns.  In (row, column) coordinates the band storage is column-major with leading
+//                   dimension ldab - 1, so the product is formed transposed -- U12^T as the MFMA's A operand out of LDS,
+//                   L21^T as its B operand straight from LW -- and a result register holds 16 consecutive rows of one
+//                   column.  4M: Cre += Ure (-Lre) + Uim Lim, Cim += Uim (-Lre) + Ure (-Lim), the accumulators start from
+//                   A22 and k ascends; every element is owned by one wave and summed in that one order, whatever the grid,
+//                   the batch or the chunk.
+// A last block with fewer than NBO columns or no rows below it runs the tiled steps alone.
+constexpr int ORC = 8;                                  // columns per workgroup of the outer block row: two per wave
+constexpr int OCT = 32;                                 // columns ...
+constexpr int ORT = 128;                                // ... and rows per workgroup of the outer trailing update
+
+// After the panel of inner step d (columns J0 + d ..): its nb interchanges on the columns of LW left of it, one thread per
+// column, and zeros in the rows of its own columns below the panel's slice (d + hin .. lh - 1, at most NBO - nb of them) --
+// what the panel left there belongs to the outer block before, and the outer update and later interchanges read those rows.
+// Everything else below the diagonal of LW is written by the panels, and nothing on or above it is ever read.
+__global__ void __launch_bounds__(64)
+band_lw_swap_kernel(BandArgs a, BlkArgs w, int J0, int d, int nb, int hin)
+{
+    const int g = blockIdx.x, k = threadIdx.x;
+    c128* lw = w.lw + (long)g * w.ls;
+    const int tail = w.lh - d - hin;
+    for (int e = k; e < tail * nb; e += 64) lw[d + hin + e % tail + (long)(d + e / tail) * w.lh] = cmake(0.0, 0.0);
+    if (k >= d) return;
+    lw += (long)k * w.lh;
+    const int* ip = a.ipiv + (long)g * a.n + J0 + d;
+    for (int jj = 0; jj < nb; ++jj) {
+        const int pr = ip[jj] - 1 - J0;
+        if (pr != d + jj) { const c128 t = lw[d + jj]; lw[d + jj] = lw[pr]; lw[pr] = t; }
+    }
+}
+
+__device__ __forceinline__ double lane_bcast(double v, int l) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+
+// Outer block row of the block at J0 (a full one: NBO columns, rows below): workgroup (t, g) takes the ORC columns from c0
+// right of the block of matrix g.  Slots as band_row_kernel: 0 .. NBO - 1 the rows J0 .. J0 + NBO - 1 of a column, NBO + jj
+// the pivot row of column jj where it lies below the block.  Rows above a column's first stored row are read as zero and
+// not written.
+__global__ void __launch_bounds__(256)
+band_orow_kernel(BandArgs a, BlkArgs w, int J0)
+{
+    constexpr int SL = 2 * NBO;
+    extern __shared__ c128 s_dyn[];
+    c128* s_l11 = s_dyn;                                                // [NBO][NBO], column-major, strictly lower
+    c128* s_v = s_dyn + NBO * NBO;                                      // [SL][ORC]
+    __shared__ int s_pr[NBO], s_sl[NBO];
+    const int t = blockIdx.x, g = blockIdx.y, tid = threadIdx.x;
+    const int n = a.n, kl = a.kl, kv = kl + a.ku, ldab = a.ldab, lh = w.lh;
+    const int H = min(kl + NBO, n - J0);
+    const int c0 = J0 + NBO + t * ORC, ju = w.ju[g];
+    if (c0 > ju) return;
+    const int ncol = min(ORC, ju - c0 + 1);
+    c128* ab = a.ab + bix(a, g);
+    const c128* lw = w.lw + (long)g * w.ls;
+    auto col = [&](int q) -> c128* { return ab + (long)(c0 + q) * ldab + kv - (c0 + q); };
+    auto lo = [&](int q) { return c0 + q - kv; };
+    if (tid < NBO) {
+        const int* ip = a.ipiv + (long)g * n + J0;
+        const int pr = ip[tid] - 1 - J0;
+        int sl = pr;
+        if (pr >= NBO) {
+            sl = NBO + tid;
+            for (int k = tid - 1; k >= 0; --k) if (ip[k] - 1 - J0 == pr) sl = NBO + k;
+        }
+        s_pr[tid] = pr; s_sl[tid] = sl;
+    }
+    for (int e = tid; e < NBO * NBO; e += 256) {
+        const int r = e % NBO, k = e / NBO;
+        s_l11[e] = k < r ? lw[r + (long)k * lh] : cmake(0.0, 0.0);
+    }
+    __syncthreads();
+    for (int e = tid; e < SL * ORC; e += 256) {
+        const int q = e / SL, s = e % SL;
+        const int r = s < NBO ? s : s_pr[s - NBO];
+        s_v[s * ORC + q] = (q < ncol && r < H && J0 + r >= lo(q)) ? col(q)[J0 + r] : cmake(0.0, 0.0);
+    }
+    __syncthreads();
+    if (tid < ncol)
+        for (int jj = 0; jj < NBO; ++jj) {
+            const int sl = s_sl[jj];
+            if (sl != jj) { const c128 u = s_v[jj * ORC + tid]; s_v[jj * ORC + tid] = s_v[sl * ORC + tid]; s_v[sl * ORC + tid] = u; }
+        }
+    __syncthreads();
+    // wave `wv` owns columns wv and wv + 4, lane r < NBO their row J0 + r
+    const int r = tid & 63, wv = tid >> 6;
+    const bool mine = r < NBO;
+    c128 v0 = s_v[(mine ? r : 0) * ORC + wv], v1 = s_v[(mine ? r : 0) * ORC + wv + 4];
+    for (int k = 0; k + 1 < NBO; ++k) {
+        const c128 l = s_l11[(mine ? r : 0) + k * NBO];                 // zero for r <= k
+        const c128 u0 = cmake(lane_bcast(v0.x, k), lane_bcast(v0.y, k)), u1 = cmake(lane_bcast(v1.x, k), lane_bcast(v1.y, k));
+        if (mine && r > k) { cfms(v0, l, u0); cfms(v1, l, u1); }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int q = wv + 4 * h;
+        if (mine && q < ncol) {
+            if (J0 + r >= lo(q)) col(q)[J0 + r] = h ? v1 : v0;
+            const int pr = s_pr[r];
+            if (s_sl[r] == NBO + r && pr < H && J0 + pr >= lo(q)) col(q)[J0 + pr] = s_v[(NBO + r) * ORC + q];
+        }
+    }
+}
+
+// Outer trailing update of the block at J0: workgroup (ct * nrt + rt, g) takes rows NBO + rt ORT .. of the slice in the OCT
+// columns from c0 right of the block of matrix g; wave v its rows 32 v .. 32 v + 31 as 2 x 2 blocks of 16 x 16.  Lane maps of
+// the MFMA as in csrc/zgemm.hip, with rows and columns exchanged: a = U12[k = 4 s + lane / 16][column lane % 16],
+// b = L21[row lane % 16][k = 4 s + lane / 16], d[i] = C[row lane % 16][column lane / 16 + 4 i].  The whole rectangle is
+// stored (c <= ju <= J0 + NBO - 1 + kv, r >= J0 + NBO), so only the edges at H and ju are masked: loads are clamped into the
+// rectangle and feed elements that are not stored.
+__global__ void __launch_bounds__(256)
+band_otrail_kernel(BandArgs a, BlkArgs w, int J0, int nrt)
+{
+    __shared__ c128 s_u[NBO * OCT];                                     // [k][column ^ (k & 7)]: fragment reads and the transposing store conflict-free
+    const int ct = blockIdx.x / nrt, rt = blockIdx.x % nrt, g = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int n = a.n, kl = a.kl, kv = kl + a.ku, lh = w.lh;
+    const long ldc = a.ldab - 1;
+    const int H = min(kl + NBO, n - J0);
+    const int c0 = J0 + NBO + ct * OCT, ju = w.ju[g];
+    if (c0 > ju) return;
+    const int ncol = min(OCT, ju - c0 + 1);
+    c128* cm = a.ab + bix(a, g) + kv;                                   // element (i, c) at cm[i + c * ldc]
+    const c128* lw = w.lw + (long)g * w.ls;
+    for (int e = tid; e < NBO * OCT; e += 256) {
+        const int k = e % NBO, q = e / NBO;
+        s_u[k * OCT + (q ^ (k & 7))] = (q < ncol && J0 + k >= c0 + q - kv) ? cm[J0 + k + (long)(c0 + q) * ldc] : cmake(0.0, 0.0);
+    }
+    __syncthreads();
+    const int r0 = NBO + rt * ORT + wv * 32;
+    if (r0 >= H) return;
+    const int lr = lane & 15, lk = lane >> 4;
+    int rr[2]; bool rok[2];
+    d4 cre[2][2], cim[2][2];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb) {
+        const int r = r0 + rb * 16 + lr;
+        rok[rb] = r < H; rr[rb] = min(r, H - 1);
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int q = min(cb * 16 + lk + 4 * i, ncol - 1);
+                const c128 c = cm[J0 + rr[rb] + (long)(c0 + q) * ldc];
+                cre[rb][cb][i] = c.x; cim[rb][cb][i] = c.y;
+            }
+    }
+#pragma unroll 4
+    for (int s = 0; s < NBO / 4; ++s) {
+        const int k = 4 * s + lk;
+        c128 l[2], u[2];
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb) l[rb] = lw[rr[rb] + (long)k * lh];
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) u[cb] = s_u[k * OCT + ((cb * 16 + lr) ^ (k & 7))];
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+                cre[rb][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(u[cb].x, -l[rb].x, cre[rb][cb], 0, 0, 0);
+                cre[rb][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(u[cb].y, l[rb].y, cre[rb][cb], 0, 0, 0);
+                cim[rb][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(u[cb].y, -l[rb].x, cim[rb][cb], 0, 0, 0);
+                cim[rb][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(u[cb].x, -l[rb].y, cim[rb][cb], 0, 0, 0);
+            }
+    }
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int q = cb * 16 + lk + 4 * i;
+                if (rok[rb] && q < ncol) cm[J0 + rr[rb] + (long)(c0 + q) * ldc] = cmake(cre[rb][cb][i], cim[rb][cb][i]);
+            }
+}
+
+// The whole wide solve of G matrices on `st`.  w.lw is the tiled method's panel of L (short last blocks), lwo the LW of the
+// outer blocks.  Per inner step the tiled method's launches plus the interchanges on LW, per outer block the two outer
+// launches; the launch queue is bounded as in launch_tiled_nb, counted in inner steps.
+template <int NB>
+hipError_t launch_wide_nb(const BandArgs& a, const BlkArgs& w, c128* lwo, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
+    constexpr size_t orow_lds = sizeof(c128) * (NBO * NBO + 2 * NBO * ORC);
+    const int kv = a.kl + a.ku, RC = 256 / NB, LH = a.kl + NBO;
+    const long LS = (long)LH * NBO;
+    // every call, for the device the call runs on: cheap beside the solve, and a refusal ends the solve here
+    hipError_t err = hipFuncSetAttribute((const void*)band_orow_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)orow_lds);
+    if (err == hipSuccess) err = hipMemsetAsync(w.ju, 0, sizeof(int) * G, st);
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    for (auto& e : ev) if (err == hipSuccess) err = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+    int step = 0;
+    for (int J0 = 0; J0 < a.n && err == hipSuccess; J0 += NBO) {
+        const int HO = std::min(a.kl + NBO, a.n - J0);
+        const bool full = a.n - J0 >= NBO && HO > NBO;
+        for (int j0 = J0; j0 < std::min(J0 + NBO, a.n) && err == hipSuccess; j0 += NB, ++step) {
+            if (step % 64 == 0 && step >= 128) err = hipEventSynchronize(ev[(step / 64) & 1]);
+            if (err != hipSuccess) break;
+            const int d = j0 - J0;
+            BlkArgs wi = w;
+            if (full) { wi.lw = lwo + d + (long)d * LH; wi.lh = LH; wi.ls = LS; }
+            const int cap = full ? J0 + NBO - 1 : INT_MAX;
+            const int right = full ? NBO - d - NB : kv;                 // columns right of the panel that the step may reach
+            const int ntile = (right + RC - 1) / RC, nct = (right + TCT - 1) / TCT;
+            launch_tiled_panel<NB>(a, wi, G, st, j0);
+            if (full) {
+                BlkArgs wo = wi; wo.lw = lwo;
+                hipLaunchKernelGGL(band_lw_swap_kernel, dim3(G), dim3(64), 0, st, a, wo, J0, d, NB, std::min(a.kl + NB, a.n - j0));
+            }
+            hipLaunchKernelGGL(band_row_kernel<NB>, dim3(ntile + 1, G), dim3(256), 0, st, a, wi, j0, ntile, cap);
+            const int below = std::min(a.kl + NB, a.n - j0) - NB;
+            if (below > 0) {
+                const int nrt = (below + TRT - 1) / TRT;
+                hipLaunchKernelGGL(band_trail_kernel<NB>, dim3((nct + 1) * nrt, G), dim3(TRT), 0, st, a, wi, j0, nct, nrt, cap);
+            }
+            if (step % 64 == 63) { err = hipGetLastError(); if (err == hipSuccess) err = hipEventRecord(ev[(step / 64) & 1], st); }
+        }
+        if (full && err == hipSuccess) {
+            BlkArgs wo = w; wo.lw = lwo; wo.lh = LH; wo.ls = LS;
+            const int nrt = (HO - NBO + ORT - 1) / ORT;
+            hipLaunchKernelGGL(band_orow_kernel, dim3((kv + ORC - 1) / ORC, G), dim3(256), orow_lds, st, a, wo, J0);
+            hipLaunchKernelGGL(band_otrail_kernel, dim3((kv + OCT - 1) / OCT * nrt, G), dim3(256), 0, st, a, wo, J0, nrt);
+        }
+    }
+    if (err == hipSuccess) err = hipGetLastError();
+    if (err == hipSuccess) {
+        if (kv <= 256) hipLaunchKernelGGL((band_back_blk_kernel<256>), dim3(G), dim3(256), 0, st, a, out, ldo, slots, perm);
+        else hipLaunchKernelGGL((band_back_blk_kernel<1024>), dim3(G), dim3(1024), 0, st, a, out, ldo, slots, perm);
+        err = hipGetLastError();
+    }
+    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+    return err;
+}
+
+hipError_t launch_wide(const BandArgs& a, const BlkArgs& w, c128* lwo, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
+    switch (band_tiled_nb(a.kl, a.ku)) {
+    case BNB: return launch_wide_nb<BNB>(a, w, lwo, G, st, out, ldo, slots, perm);
+    case TNB_MID: return launch_wide_nb<TNB_MID>(a, w, lwo, G, st, out, ldo, slots, perm);
+    default: return launch_wide_nb<TNB_TALL>(a, w, lwo, G, st, out, ldo, slots, perm);
+    }
+}
+
+// the elements of the blocked / tiled panel of L per solve, and of the wide method's LW; lw of a workspace of G solves holds
+// the G panels, then the G LW
+size_t band_lw_small(int kl) { return (size_t)(kl + BNB) * BNB; }
+size_t band_lw_outer(int kl) { return (size_t)(kl + NBO) * NBO; }
+
 hipError_t launch_kind(int kind, const BandArgs& a, const BlkArgs& w, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
+    if (kind == 4) return launch_wide(a, w, w.lw + band_lw_small(a.kl) * G, G, st, out, ldo, slots, perm);
     return kind == 1 ? launch_blocked(a, w, G, st, out, ldo, slots, perm) : launch_tiled(a, w, G, st, out, ldo, slots, perm);
 }
 
@@ -733,17 +1009,29 @@ double band_tiled_bytes(int n, int kl, int ku, int G) {
     return G * steps * (32.0 * (kl + nb) * (double)(nb + kl + ku) + 16.0 * (kl + nb) * (double)nb * nct) + 16.0 * G * (double)n * (kl + ku + 1);
 }
 
-int band_class(int kind) { return kind == 1 ? KC_BAND_BLOCKED : (kind == 2 ? KC_BAND_TILED : KC_BAND); }
+// the wide method moves that upper end of the band once per outer block step, LW once per column tile of the outer trailing
+// update, and inside the block the inner steps' share: the block's NBO columns over the slice's rows and L21 once per column
+// tile of the inner trailing update.  An upper end like the two above.
+double band_wide_bytes(int n, int kl, int ku, int G) {
+    const int nb = band_tiled_nb(kl, ku);
+    const double outer = (double)(n + NBO - 1) / NBO, inner = (double)(n + nb - 1) / nb;
+    const double octs = (double)((kl + ku + OCT - 1) / OCT), icts = (double)(NBO / TCT + 1);
+    return G * outer * (32.0 * (kl + NBO) * (double)(NBO + kl + ku) + 16.0 * (kl + NBO) * (double)NBO * octs)
+         + G * inner * (32.0 * (kl + nb) * (double)NBO + 16.0 * (kl + nb) * (double)nb * icts) + 16.0 * G * (double)n * (kl + ku + 1);
+}
+
+int band_class(int kind) { return kind == 1 ? KC_BAND_BLOCKED : (kind == 2 ? KC_BAND_TILED : (kind == 4 ? KC_BAND_WIDE : KC_BAND)); }
 double band_kind_bytes(int kind, int n, int kl, int ku, int G) {
+    if (kind == 4) return band_wide_bytes(n, kl, ku, G);
     return kind == 1 ? band_blocked_bytes(n, kl, ku, G) : (kind == 2 ? band_tiled_bytes(n, kl, ku, G) : band_bytes(n, 2 * kl + ku + 1, G));
 }
 
-// bytes of one solve in the workspace; the blocked and the tiled method add their panel of L ((kl + nb) x nb, nb <= BNB) and
-// their reach
-size_t band_per_solve(int n, int kl, int ku, bool blocked) {
+// bytes of one solve in the workspace; the blocked and the tiled method (kind 1, 2) add their panel of L ((kl + nb) x nb,
+// nb <= BNB) and their reach, the wide method (kind 4) its LW as well
+size_t band_per_solve(int n, int kl, int ku, int kind) {
     const size_t ldab = 2 * (size_t)kl + ku + 1;
     return sizeof(c128) * (ldab * n + n) + sizeof(int) * (size_t)n
-         + (blocked ? sizeof(c128) * (size_t)(kl + BNB) * BNB + sizeof(int) : 0);
+         + (kind ? sizeof(c128) * band_lw_small(kl) + sizeof(int) : 0) + (kind == 4 ? sizeof(c128) * band_lw_outer(kl) : 0);
 }
 
 void band_ws_free(maus_ctx* c) {
@@ -759,9 +1047,10 @@ void band_ws_free(maus_ctx* c) {
 // memory) -- never shrunk; larger batches run in balanced chunks.
 int ensure_band_ws(maus_ctx* c, int want) {
     const int n = c->band_n, ldab = 2 * c->band_kl + c->band_ku + 1;
-    const bool blocked = band_kind(c->band_method, c->band_kl, c->band_ku) != 0;      // the methods that allocate lw and ju
-    const size_t per = band_per_solve(n, c->band_kl, c->band_ku, blocked);
-    const unsigned long long key = ((unsigned long long)n << 32) | ((unsigned long long)blocked << 31) | (unsigned)ldab;
+    const int kind = band_kind(c->band_method, c->band_kl, c->band_ku);
+    const bool blocked = kind != 0, wide = kind == 4;                   // the methods that allocate lw and ju; LW behind lw
+    const size_t per = band_per_solve(n, c->band_kl, c->band_ku, kind);
+    const unsigned long long key = ((unsigned long long)n << 32) | ((unsigned long long)blocked << 31) | ((unsigned long long)wide << 30) | (unsigned)ldab;
     const bool same = c->band_ab && c->band_ws_key == key;
     if (same && (c->band_g >= want || c->band_at_limit)) return 0;
     size_t fr = 0, tot = 0;
@@ -787,7 +1076,7 @@ int ensure_band_ws(maus_ctx* c, int want) {
     HIPCHK(c, hipMalloc((void**)&c->band_info, sizeof(int) * G));
     HIPCHK(c, hipMalloc((void**)&c->band_flags, sizeof(int) * G));
     if (blocked) {
-        HIPCHK(c, hipMalloc((void**)&c->band_lw, sizeof(c128) * (size_t)(c->band_kl + BNB) * BNB * G));
+        HIPCHK(c, hipMalloc((void**)&c->band_lw, sizeof(c128) * (band_lw_small(c->band_kl) + (wide ? band_lw_outer(c->band_kl) : 0)) * G));
         HIPCHK(c, hipMalloc((void**)&c->band_ju, sizeof(int) * G));
     }
     c->band_g = G; c->band_ws_key = key; c->band_allocs++;
@@ -804,7 +1093,8 @@ BandArgs band_args(maus_ctx* c) {
 
 BlkArgs blk_args(maus_ctx* c) {
     BlkArgs w; w.lw = c->band_lw; w.ju = c->band_ju;
-    w.lh = c->band_kl + band_kind_nb(band_kind(c->band_method, c->band_kl, c->band_ku), c->band_kl, c->band_ku);
+    const int nb = band_kind_nb(band_kind(c->band_method, c->band_kl, c->band_ku), c->band_kl, c->band_ku);
+    w.lh = c->band_kl + nb; w.ls = (long)w.lh * nb;
     return w;
 }
 
@@ -924,7 +1214,7 @@ int maus_band_workspace_allocs(maus_ctx* c) { return c ? c->band_allocs : -1; }
 
 int maus_band_set_method(maus_ctx* c, int method) {
     if (!c) return -1;
-    if (method < 0 || method > 2) FAIL(c, "maus_band_set_method: method must be 0 (column), 1 (blocked) or 2 (tiled)");
+    if (method != 4 && (method < 0 || method > 2)) FAIL(c, "maus_band_set_method: method must be 0 (column), 1 (blocked), 2 (tiled) or 4 (wide)");
     c->band_method = method;                                            // the workspace follows at its next use (ensure_band_ws)
     return 0;
 }
@@ -937,6 +1227,12 @@ int maus_band_kernel_for(maus_ctx* c, int n, int kl, int ku, int* nb_out) {
     const int kind = band_kind(c->band_method, kl, ku);
     if (nb_out) *nb_out = band_kind_nb(kind, kl, ku);
     return kind;
+}
+
+int maus_band_outer_nb(maus_ctx* c, int n, int kl, int ku) {
+    if (!c) return -1;
+    if (n <= 0 || kl < 0 || ku < 0) FAIL(c, "maus_band_outer_nb: bad sizes");
+    return band_kind(c->band_method, kl, ku) == 4 ? NBO : 0;
 }
 
 int maus_band_lu_host(maus_ctx* c, int count, int n, int kl, int ku, const double* ab, const double* b, double* x_out,
@@ -953,8 +1249,8 @@ int maus_band_lu_host(maus_ctx* c, int count, int n, int kl, int ku, const doubl
                  o_i = take(sizeof(int) * count), o_f = take(sizeof(int) * count);
     const int kind = band_kind(c->band_method, kl, ku);
     const bool blocked = kind != 0;
-    BlkArgs w; w.lw = nullptr; w.ju = nullptr; w.lh = kl + band_kind_nb(kind, kl, ku);
-    const size_t o_l = take(blocked ? sizeof(c128) * (size_t)(kl + BNB) * BNB * count : 0), o_j = take(blocked ? sizeof(int) * count : 0);
+    BlkArgs w; w.lw = nullptr; w.ju = nullptr; w.lh = kl + band_kind_nb(kind, kl, ku); w.ls = (long)w.lh * band_kind_nb(kind, kl, ku);
+    const size_t o_l = take(blocked ? sizeof(c128) * (band_lw_small(kl) + (kind == 4 ? band_lw_outer(kl) : 0)) * count : 0), o_j = take(blocked ? sizeof(int) * count : 0);
     if (ensure_scratch(c, off)) return -1;
     char* base = (char*)c->scratch;
     a.ab = (c128*)(base + o_ab); a.x = (c128*)(base + o_x); a.ipiv = (int*)(base + o_p); a.info = (int*)(base + o_i); a.flags = (int*)(base + o_f);

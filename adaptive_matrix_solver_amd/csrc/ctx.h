@@ -76,8 +76,8 @@ struct maus_ctx {
     int* band_perm = nullptr; int* band_iperm = nullptr; int band_n = 0, band_kl = -1, band_ku = -1;
     c128* band_ab = nullptr; c128* band_x = nullptr; int *band_ipiv = nullptr, *band_info = nullptr, *band_flags = nullptr;
     int band_g = 0, band_allocs = 0; bool band_at_limit = false; unsigned long long band_ws_key = 0;
-    int band_method = 0;                                // 0: column kernel, 1: blocked, 2: tiled (maus_band_set_method); kept across matrices
-    c128* band_lw = nullptr; int* band_ju = nullptr;    // the blocked / tiled method's panel of L and reach, per solve of the workspace
+    int band_method = 0;                                // 0: column kernel, 1: blocked, 2: tiled, 4: wide (maus_band_set_method); kept across matrices
+    c128* band_lw = nullptr; int* band_ju = nullptr;    // the blocked / tiled / wide method's panel of L (wide: LW behind it) and reach, per solve of the workspace
     MausLanczos lz;
     c128* b = nullptr; int bn = 0;                  // rhs
     c128* V = nullptr; int vn = 0;                  // eigenvectors (Hermitian shortcut)

@@ -237,7 +237,7 @@ def tridiagonal_eigenvalues(ctx, d, e):
     return np.sort(sla.eigvalsh_tridiagonal(d, e))
 
 
-SPARSE_DIRECT_MODES = ("auto", "dense", "band", "blocked", "tiled")
+SPARSE_DIRECT_MODES = ("auto", "dense", "band", "blocked", "tiled", "wide")
 
 
 def sparse_direct_mode(mode):
@@ -364,7 +364,9 @@ class DeviceEngine:
         # 'band' runs the band LU in the ordering of band.band_order, 'auto' the first up to maus_lu_max_n() and the second
         # above; 'blocked' is 'band' with the blocked kernels (zgbtrf's schedule, every step a launch over the whole device;
         # opt-in, 'auto' never picks it); 'tiled' is 'blocked' with the update tiled over rows as well, for bands up to
-        # kl = 4096 (opt-in too).  MAUS_SPARSE_DIRECT sets the default.  Chosen once per bound matrix (_band).
+        # kl = 4096 (opt-in too); 'wide' is 'tiled' inside outer blocks of 64 columns, each applied to everything right of it
+        # in one rank-64 update on the fp64 MFMA pipe, for 64 <= kl <= 4096 (opt-in too).  MAUS_SPARSE_DIRECT sets the
+        # default.  Chosen once per bound matrix (_band).
         self.sparse_direct = sparse_direct_mode(sparse_direct)
         # sparse Hermitian shortcut (AMS:186-216): 'dense' = one scipy.linalg.eigh of A.toarray() per matrix, 'lanczos' =
         # thick-restart Lanczos on the CSR matrix on the device, 'auto' the first up to maus_lu_max_n() and the second above.
@@ -453,7 +455,7 @@ class DeviceEngine:
 
     def uses_band(self, n: int) -> bool:
         """Whether a sparse n x n matrix takes the band solve (sparse_direct; 'auto': above maus_lu_max_n())."""
-        if self.sparse_direct in ("band", "blocked", "tiled"):
+        if self.sparse_direct in ("band", "blocked", "tiled", "wide"):
             return True
         if self.sparse_direct == "dense":
             return False
@@ -479,6 +481,8 @@ class DeviceEngine:
                 self.ctx.band_set_method(1)
             elif self.sparse_direct == "tiled":
                 self.ctx.band_set_method(2)
+            elif self.sparse_direct == "wide":
+                self.ctx.band_set_method(4)
             self.ctx.band_prepare(perm)
             self._band_ready = True
 

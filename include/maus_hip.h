@@ -118,12 +118,16 @@ int maus_matrix_is_sparse(maus_ctx* ctx);
  *   0 the column kernel (one workgroup per matrix walks the columns; the default), 1 the blocked method (zgbtrf's
  *   schedule in blocks of 16 columns, every step a launch over (matrix, tile)), 2 the tiled method (the blocked
  *   schedule with the block row and the trailing update as launches of their own over (column tile, row tile); blocks of
- *   16, 8 or 4 columns by kl).  Under method 1 a band with kl < 16 or kl > 1024 still runs the column kernel, under
- *   method 2 one with kl < 16 or kl > 4096.  For a band that both take, methods 1 and 2 give the same bits.  The method
+ *   16, 8 or 4 columns by kl), 4 the wide method (zgbtrf's two levels: outer blocks of 64 columns factored by the
+ *   tiled steps, then one rank-64 update of everything right of the block on the fp64 MFMA pipe).  There is no method 3.
+ *   Under method 1 a band with kl < 16 or kl > 1024 still runs the column kernel, under method 2 one with kl < 16 or
+ *   kl > 4096; under method 4 a band with 64 <= kl <= 4096 runs wide, one with 16 <= kl < 64 exactly what method 2 runs
+ *   and every other the column kernel.  For a band that both take, methods 1 and 2 give the same bits.  The method
  *   outlives the bound matrix; same status contract in every method.
  * maus_band_get_method: the current method.
- * maus_band_kernel_for: what (n, kl, ku) runs under the current method: returns 0 (column kernel), 1 (blocked) or 2 (tiled);
- *   nb_out (may be NULL): the block width, 1 for the column kernel. */
+ * maus_band_kernel_for: what (n, kl, ku) runs under the current method: returns 0 (column kernel), 1 (blocked), 2 (tiled)
+ *   or 4 (wide); nb_out (may be NULL): the block width (wide: of the inner steps), 1 for the column kernel.
+ * maus_band_outer_nb: the width of the outer block (64) where (n, kl, ku) runs wide under the current method, 0 elsewhere. */
 int maus_sparse_max_n(void);
 int maus_band_prepare(maus_ctx* ctx, const int32_t* perm, int n, int* kl_out, int* ku_out);
 int maus_band_reserve(maus_ctx* ctx, int count, int* capacity_out);
@@ -135,6 +139,7 @@ int maus_band_workspace_allocs(maus_ctx* ctx);
 int maus_band_set_method(maus_ctx* ctx, int method);
 int maus_band_get_method(maus_ctx* ctx);
 int maus_band_kernel_for(maus_ctx* ctx, int n, int kl, int ku, int* nb_out);
+int maus_band_outer_nb(maus_ctx* ctx, int n, int kl, int ku);
 
 /* Upload b (AMS:146, 275). */
 int maus_set_rhs(maus_ctx* ctx, const double* b_c128, int n);
@@ -388,7 +393,9 @@ int maus_timer_stop(maus_ctx* ctx, float* ms_out);
  * 6 vector ops, 7..10 zgemm inside the LU recursion with K = 128 / 64 / 32 / 16, 11 CSR products, 12 band solves,
  * 13 lanczos (reorthogonalisation, restart, match of the sparse Hermitian shortcut), 14 band solves by the blocked method
  * (maus_band_set_method; bytes: the band moved once per block step over the full reach kl + ku, not an MFMA class),
- * 15 band solves by the tiled method (bytes: as 14 plus L21 once per column tile of the trailing update) */
+ * 15 band solves by the tiled method (bytes: as 14 plus L21 once per column tile of the trailing update)
+ * 16 band solves by the wide method (bytes, an upper end: the band once per outer block of 64 columns over the full reach,
+ *    LW once per column tile of the outer update, and the inner steps' bytes inside the block) */
 /* on = 1: event pairs around every launch of every class; on = 2: around the K>=256 zgemm launches only (class 0;
  * long kernels, so cheap enough for a timed region -- full bracketing costs 3-5 % of throughput; MAUS_PROF_STRIDE
  * can thin them out, each sample then stands for `stride` launches); 0: off */

@@ -21,6 +21,14 @@ complex values of one size, so that the factorisation pivots and fills the whole
 Then the six rows of the blocked table, tiled beside blocked, same systems.
 
     python tools/band_rates.py --table tiled [--out profiles/band_tiled_rates.txt]
+
+With --table wide: the wide method (maus_band_set_method(ctx, 4)) beside the tiled method and, where it runs, the blocked
+method, in one process on the same systems -> profiles/band_wide_rates.txt: the four rows of the tiled table that only the
+tiled and the wide method take, then the six rows of the blocked table.  Per row the ms per solve of each method (the better
+of two timed calls after one warm-up call), tiled ms / wide ms, and the share of the fp64 MFMA peak that the wide method's
+executed (4M) flops reach.
+
+    python tools/band_rates.py --table wide [--out profiles/band_wide_rates.txt]
 """
 import argparse
 import os
@@ -129,7 +137,7 @@ def loop_rate(compat, direct="auto", bodies=3):
     return steps / wall, (pr["band"]["ms"] + pr["band_blocked"]["ms"]) / bodies, pr["spmm"]["ms"] / bodies
 
 
-KCLASS = {_cabi.BAND_COLUMN: "band", _cabi.BAND_BLOCKED: "band_blocked", _cabi.BAND_TILED: "band_tiled"}
+KCLASS = {_cabi.BAND_COLUMN: "band", _cabi.BAND_BLOCKED: "band_blocked", _cabi.BAND_TILED: "band_tiled", _cabi.BAND_WIDE: "band_wide"}
 
 
 def table_row(ctx, n, kl, ku, P, method, name, base_ms=None, **timing):
@@ -199,17 +207,75 @@ def main_tiled(args):
         f.write("\n".join(lines) + "\n")
 
 
+def main_wide(args):
+    ctx = _cabi.Context(0)
+    info = ctx.device_info()
+    head = (f"{'n':>7} {'kl':>4} {'ku':>4} {'batch':>5} {'nb':>3} {'wide ms':>10} {'tiled ms':>10} {'blocked ms':>10} {'tiled/wide':>10} "
+            f"{'blocked/wide':>12} {'wide TFLOP/s':>12} {'of MFMA peak':>12}")
+    lines = [f"# band solves, csrc/band.hip, the wide method beside the tiled and the blocked method in one process -- "
+             f"{info['name']}, {info['cus']} CUs",
+             "# ms per solve from the 'band_wide' / 'band_tiled' / 'band_blocked' profile class (HIP events around build + factor +",
+             "# solve of one batch), the better of two timed calls after one warm-up call; nb = width of the inner steps (the outer",
+             "# block is 64 columns); TFLOP/s = 8 n kl (kl + ku) + 8 n (2 kl + ku) executed real flops (4M: 8 per complex",
+             "# multiply-add, the reach taken as full) over the wide time; peak = 78.6 TFLOP/s (fp64 MFMA)",
+             head]
+
+    def row(n, kl, ku, P):
+        ms = {}
+        for method, name in ((_cabi.BAND_WIDE, "wide"), (_cabi.BAND_TILED, "tiled"), (_cabi.BAND_BLOCKED, "blocked")):
+            ctx.band_set_method(method)
+            kern, nb = ctx.band_kernel_for(n, kl, ku)
+            if kern != method:                                  # blocked above kl = 1024: the column kernel, minutes
+                continue
+            pr, _ = timed_band(ctx, P, KCLASS[kern])
+            ms[name] = pr["ms"] / P
+            if name == "wide":
+                tf, inner = pr["flops"] / (pr["ms"] / 1e3) / 1e12, nb
+        blk = f"{ms['blocked']:>10.3f}" if "blocked" in ms else f"{'':>10}"
+        rb = f"{ms['blocked'] / ms['wide']:>11.2f}x" if "blocked" in ms else f"{'':>12}"
+        line = (f"{n:>7} {kl:>4} {ku:>4} {P:>5} {inner:>3} {ms['wide']:>10.3f} {ms['tiled']:>10.3f} {blk} {ms['tiled'] / ms['wide']:>9.2f}x "
+                f"{rb} {tf:>12.3f} {tf * 1e12 / PEAK_F64:>12.2%}")
+        print(line, flush=True)
+        lines.append(line)
+
+    wide = [("7-point 40^3", lambda: seven_point(40, 40), False, (1, 8))]
+    wide += [(f"five diagonals k = {k}", (lambda k=k: five_diagonals(32768, k, k)), True, (1,)) for k in (2048, 4096)]
+    for label, make, identity, batches in wide:
+        if args.only and not any(o in label for o in args.only.split(",")):
+            continue
+        A = make()
+        kl, ku = bind(ctx, A, max(batches), identity=identity)
+        lines.append(f"# {label}")
+        for P in batches:
+            row(A.shape[0], kl, ku, P)
+    lines.append("# 2-D 5-point operator (the rows of profiles/band_blocked_rates.txt)")
+    cache = {}
+    for item in ([] if args.only else args.sizes.split(",")):
+        m, P = (int(v) for v in item.split(":"))
+        if m not in cache:
+            A = five_point(m, m)
+            cache.clear()
+            cache[m] = (A, bind(ctx, A, 64))
+        A, (kl, ku) = cache[m]
+        row(m * m, kl, ku, P)
+    ctx.close()
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--table", choices=("blocked", "tiled"), default="blocked")
+    ap.add_argument("--table", choices=("blocked", "tiled", "wide"), default="blocked")
     ap.add_argument("--out", default=None)
     ap.add_argument("--sizes", default="128:1,128:64,256:1,256:64,512:1,512:8")
-    ap.add_argument("--only", default=None, help="--table tiled: the wide rows whose label contains one of these, nothing else")
+    ap.add_argument("--only", default=None, help="--table tiled / wide: the wide-band rows whose label contains one of these, nothing else")
     ap.add_argument("--no-column", action="store_true", help="--table tiled: leave the column kernel's minutes out")
     args = ap.parse_args()
     args.out = args.out or f"profiles/band_{args.table}_rates.txt"
     if args.table == "tiled":
         return main_tiled(args)
+    if args.table == "wide":
+        return main_wide(args)
     ctx = _cabi.Context(0)
     info = ctx.device_info()
     lines = [f"# band solves, csrc/band.hip, column kernel and blocked method in one process -- {info['name']}, {info['cus']} CUs",
