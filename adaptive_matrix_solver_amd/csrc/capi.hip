@@ -1196,13 +1196,14 @@ int maus_gram(maus_ctx* c, int which, const int* slots, int count, int len, doub
 int maus_gmres(maus_ctx* c, const int* slots, int count, const double* shift, const double* psi, int rhs_mode,
                const int32_t* use_jacobi, double rtol, int restart, int maxiter, int32_t* info_out, int32_t* inner_out, int32_t* status) {
     av_drop_all(c);
+    if (c && (restart < 1 || restart > 20)) FAIL(c, "maus_gmres: restart must be between 1 and 20 (the Krylov basis holds 20 vectors)");
     // Above maus_lu_max_n() (CSR only) one candidate's basis, iterate and product take (R + 3) n complex entries, 386 MB at
     // n = 2^20: a batch runs in chunks whose scratch stays within 1/16 of the device's total HBM (a rule of n and the device).
     // Candidates never share arithmetic (per-row SpMM, one workgroup per candidate), so the chunking changes no result.
     if (c && c->csr && c->rows > maus_lu_max_n() && count > 1 && slots && shift && psi && use_jacobi && info_out && inner_out && status) {
         size_t fr = 0, tot = 0;
         HIPCHK(c, hipMemGetInfo(&fr, &tot));
-        const size_t per = sizeof(c128) * (size_t)(std::max(1, std::min(restart, 20)) + 3) * c->rows + 4096;
+        const size_t per = sizeof(c128) * (size_t)(restart + 3) * c->rows + 4096;
         const int chunk = (int)std::max<size_t>(1, tot / 16 / per);
         if (count > chunk) {
             for (int off = 0; off < count; off += chunk) {
@@ -1225,6 +1226,7 @@ int maus_gmres_pert(maus_ctx* c, const int* slots, int count, const double* shif
     if (c->rows != c->cols) FAIL(c, "maus_gmres_pert: square matrix required");
     if (rhs_mode == 1 && (!c->b || c->bn != c->rows)) FAIL(c, "maus_gmres_pert: rhs b not set");
     if ((pert_mode == MAUS_PERT_UNIFORM || pert_mode == MAUS_PERT_MT19937) && !pert_data) FAIL(c, "pert_data missing");
+    if (restart < 1 || restart > 20) FAIL(c, "maus_gmres_pert: restart must be between 1 and 20 (the Krylov basis holds 20 vectors)");
     if (count == 0) return 0;
     const int n = c->rows;
     if (check_slots(c, slots, count)) return -1;

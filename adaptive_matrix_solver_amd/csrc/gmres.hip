@@ -32,6 +32,7 @@ void maus_zgemm_launch_idx(hipStream_t st, int M, int N, int K, const c128* A, l
 namespace {
 
 constexpr int MAXR = 20;
+constexpr int PAD_ROWS = 33;      // fewest rows for which the zgemm launcher picks the kernel family of a full population product
 constexpr int GT = 256;
 constexpr double EPS = 2.220446049250313e-16;
 
@@ -231,6 +232,14 @@ __global__ void __launch_bounds__(256)
 bcast_row_kernel(c128* __restrict__ Y, int n, const int* __restrict__ act, int first) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) Y[(long)act[first + blockIdx.y] * n + i] = Y[(long)act[0] * n + i];
+}
+
+// Rows nact .. to - 1 of the product's row lists repeat row 0 (see the dense shared product in maus_gmres_run): the product
+// kernel then computes candidate act[0]'s row several times and every copy stores the same bits to the same row of Y.
+__global__ void __launch_bounds__(64)
+gmres_pad_rows_kernel(int* __restrict__ act, int* __restrict__ zrow, int nact, int to) {
+    const int p = nact + threadIdx.x;
+    if (p < to) { act[p] = act[0]; zrow[p] = zrow[0]; }
 }
 
 // active list + the row of the basis array each active candidate multiplies next
@@ -644,11 +653,12 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
     if (c->csr && Hdense) FAIL(c, "maus_gmres: a sparse matrix has no random term (no materialised H)");
     if (c->rows != c->cols) FAIL(c, "maus_gmres: square matrix required");
     if (rhs_mode == 1 && (!c->b || c->bn != c->rows)) FAIL(c, "maus_gmres: rhs b not set");
+    if (restart < 1 || restart > MAXR) FAIL(c, "maus_gmres: restart must be between 1 and 20 (the Krylov basis holds 20 vectors)");
     if (count <= 0) return 0;
     const int n = c->rows;
     if (n > maus_lu_max_n() && !c->csr) FAIL(c, "maus_gmres: n <= 16384 in this build (a CSR matrix: n <= maus_sparse_max_n())");
     if (n > maus_sparse_max_n()) FAIL(c, "maus_gmres: n exceeds maus_sparse_max_n()");
-    const int R = std::max(1, std::min(std::min(restart, MAXR), n));
+    const int R = std::min(restart, n);                      // SciPy: restart = min(restart, n)
     if (maxiter < 1) maxiter = 1;
     if (upload_slots(c, slots, count)) return -1;
     // scratch: diag | basis (count*(R+2) rows) | Y (count rows) | states | act | zrow | nact | jac | info/inner/status
@@ -656,7 +666,8 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
     const size_t o_d = take(sizeof(c128) * n), o_v = take(sizeof(c128) * rows_per * count * n), o_y = take(sizeof(c128) * (size_t)count * n),
-                 o_s = take(sizeof(GState) * count), o_a = take(sizeof(int) * count), o_z = take(sizeof(int) * count),
+                 o_s = take(sizeof(GState) * count), o_a = take(sizeof(int) * std::max(count, PAD_ROWS)),
+                 o_z = take(sizeof(int) * std::max(count, PAD_ROWS)),
                  o_n = take(sizeof(int)), o_j = take(sizeof(int) * count), o_o = take(sizeof(int) * 3 * count);
     if (ensure_scratch(c, off)) return -1;
     char* base = (char*)c->scratch;
@@ -700,8 +711,19 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
               maus_zgemm_launch_idx(c->st, 33, n, n, a.Vb, n, 0, c->A, n, 0, a.Y, n, 0, 1.0, 0, 1, 1, false, false, zrow, act); }
             hipLaunchKernelGGL(bcast_row_kernel, dim3((n + 255) / 256, h_nact - 33), dim3(256), 0, c->st, a.Y, n, act, 33);
         } else
-        { ProfScope ps(c, KC_GEMM, 8.0 * h_nact * (double)n * n, 16.0 * ((double)n * n + 2.0 * h_nact * n));
-          maus_zgemm_launch_idx(c->st, h_nact, n, n, a.Vb, n, 0, c->A, n, 0, a.Y, n, 0, 1.0, 0, 1, 1, false, false, zrow, act); }
+        {
+            // A candidate's product must not depend on how many others are still active.  The launcher takes the DMA-staged 3M
+            // kernel from 33 rows on (K a multiple of 8, K >= 64) and 4M kernels below, and the two round differently: where the
+            // 3M kernel applies, a product of fewer rows is padded to 33 with copies of its first row, so every product of a
+            // solve -- alone or in any batch -- comes from the same kernel, whose rows do not depend on one another.
+            int m = h_nact;
+            if (m < PAD_ROWS && (n % 8) == 0 && n >= 64) {
+                hipLaunchKernelGGL(gmres_pad_rows_kernel, dim3(1), dim3(64), 0, c->st, act, zrow, h_nact, PAD_ROWS);
+                m = PAD_ROWS;
+            }
+            ProfScope ps(c, KC_GEMM, 8.0 * m * (double)n * n, 16.0 * ((double)n * n + 2.0 * m * n));
+            maus_zgemm_launch_idx(c->st, m, n, n, a.Vb, n, 0, c->A, n, 0, a.Y, n, 0, 1.0, 0, 1, 1, false, false, zrow, act);
+        }
         { ProfScope ps(c, KC_VEC, 0, 16.0 * h_nact * (double)n * (R + 4));
           if (n <= 4 * GT) hipLaunchKernelGGL((gmres_post_kernel<4>), dim3(h_nact), dim3(GT), 0, c->st, a, act);
           else if (n <= 16 * GT) hipLaunchKernelGGL((gmres_post_kernel<16>), dim3(h_nact), dim3(GT), 0, c->st, a, act);

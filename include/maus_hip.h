@@ -321,7 +321,20 @@ int maus_gram(maus_ctx* ctx, int which, const int* slots, int count, int len, do
  *   H_k = A - shift_k I + psi_k I (the random term of AMS:49-50 is left out: see maus_gmres_pert); x0 = rhs; W[slot] <- x
  * use_jacobi[count]: 1 -> M = diag(1/diag H_k) (caller applies AMS:65/72 gating via
  * maus_jacobi_check below).
- * info_out: 0 converged, maxiter otherwise (SciPy convention); inner_out: inner iterations. */
+ * info_out: 0 converged, maxiter otherwise (SciPy convention); inner_out: inner iterations.
+ * restart: 1 .. 20 (the Krylov basis holds 20 vectors); anything else is an error -- no clamping, the call never runs another
+ *   algorithm than the one asked for.  The cycle length is min(restart, n), as in SciPy.  maxiter < 1 counts as 1.
+ * Non-finite data: maus_gmres does not scan the matrix or the right-hand sides.  A NaN or Inf in either makes the residual
+ *   norm NaN, which passes no exit test: that candidate ends with info = maxiter, status = 0 (at once for a non-finite
+ *   right-hand side, after one cycle for a non-finite matrix; SciPy reports the same after maxiter cycles of NaN), W[slot] then
+ *   holds x0 or NaN.  status is never -1 here; -2: info = 0 although x is not finite (kept for the callers' AMS:94 test: with
+ *   a finite ||b||^2 a converged residual implies a finite H x, so no finite system is known to reach it).
+ * Range: norms are plain sums of squares (no scaling): right-hand sides and matrices must keep ||b||^2, ||M r||^2 and the
+ *   squares of the Krylov vectors inside the double range -- entries of b between 1e-150 and 1e+150 in magnitude at unit-scale
+ *   matrices; tested at |b| ~ 1e+-120.  Beyond that the norms overflow or underflow and the outcome is info = maxiter.
+ * A candidate's x, info and inner count do not depend on the batch it is solved in (bit for bit): SpMM rows are independent,
+ *   and a dense product of fewer than 33 rows is padded to 33 where the zgemm launcher would otherwise change from its 3M to its
+ *   4M kernels (n a multiple of 8, n >= 64). */
 int maus_gmres(maus_ctx* ctx, const int* slots, int count, const double* shift_c128, const double* psi,
                int rhs_mode, const int32_t* use_jacobi, double rtol, int restart, int maxiter,
                int32_t* info_out, int32_t* inner_out, int32_t* status);
@@ -331,7 +344,10 @@ int maus_gmres(maus_ctx* ctx, const int* slots, int count, const double* shift_c
  * as there), matvec = one GEMV per candidate against its own H_k.  For escalated psi (retry ladder, large aggression /
  * stuck factors) where the random term is no longer below the rounding of a matvec; maus_gmres is the fast path below
  * that.  want_jacobi[count]: 1 -> use M = diag(1/diag H_k) provided the AMS:67-72 gate holds on diag(H_k) (evaluated on
- * the device; jacobi_out[count], may be NULL, reports whether it was used).  status -1: non-finite H_k or rhs. */
+ * the device; jacobi_out[count], may be NULL, reports whether it was used).  status -1: non-finite H_k or rhs (this entry
+ * point scans both while it builds H_k, the AMS:94 analogue; maus_gmres never reports -1).  restart and the range of the data
+ * as for maus_gmres.  A batch beyond the LU workspace capacity runs in chunks; a candidate's result does not depend on the
+ * batch (one GEMV per candidate). */
 int maus_gmres_pert(maus_ctx* ctx, const int* slots, int count, const double* shift_c128, const double* psi,
                     int rhs_mode, const int32_t* want_jacobi, int pert_mode, const void* pert_data,
                     double rtol, int restart, int maxiter,

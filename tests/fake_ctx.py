@@ -11,6 +11,13 @@ import scipy.linalg as sla
 from oracle import maus_oracle as orc
 
 
+def check_restart(what, restart):
+    """maus_gmres / maus_gmres_pert refuse a restart outside 1 .. 20 (the device's Krylov basis holds 20 vectors)."""
+    if not 1 <= int(restart) <= 20:
+        from adaptive_matrix_solver_amd._cabi import MausHipError
+        raise MausHipError(f"{what} failed (rc=-1): {what}: restart must be between 1 and 20 (the Krylov basis holds 20 vectors)")
+
+
 class FakeContext:
     def __init__(self):
         self.rows = self.cols = 0
@@ -202,6 +209,7 @@ class FakeContext:
         return ok
 
     def gmres(self, slots, shift, psi, rhs_mode, use_jacobi, rtol=1e-8, restart=20, maxiter=50):
+        check_restart("maus_gmres", restart)
         n = self.rows
         info = np.zeros(len(slots), dtype=np.int32)
         inner = np.zeros(len(slots), dtype=np.int32)
@@ -210,7 +218,11 @@ class FakeContext:
             H = (self.A - shift[k] * np.eye(n)) + psi[k] * np.eye(n)
             rhs = self.pop[0][s, :n].copy() if rhs_mode == 0 else self.b
             if not (np.all(np.isfinite(H)) and np.all(np.isfinite(rhs))):
-                status[k] = -1
+                # maus_gmres has no finiteness scan (status -1 is maus_gmres_pert's): the residual norm is NaN, no exit test can
+                # pass, and the device ends at once with info = maxiter, status 0 -- where SciPy arrives after maxiter cycles of
+                # NaN.  W[slot] holds nothing of use then (the device leaves x0 or NaN there).
+                info[k] = max(1, maxiter)
+                self.pop[2][s, :n] = rhs
                 continue
             inv_d = (1.0 / np.diag(H)) if use_jacobi[k] else None
             x, inf, inn, cyc = orc.gmres_restated(H, rhs, rhs, inv_d, rtol=rtol, maxiter=maxiter, restart=restart)
@@ -222,6 +234,7 @@ class FakeContext:
 
     def gmres_pert(self, slots, shift, psi, rhs_mode, want_jacobi, pert_mode, pert_data, rtol=1e-8, restart=20, maxiter=50):
         """NumPy double of maus_gmres_pert: GMRES against H_solve including the random term (AMS:49-52, 89)."""
+        check_restart("maus_gmres_pert", restart)
         n = self.rows
         info = np.zeros(len(slots), dtype=np.int32)
         inner = np.zeros(len(slots), dtype=np.int32)

@@ -12,7 +12,7 @@ import pytest
 import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
-from fake_ctx import FakeContext
+from fake_ctx import FakeContext, check_restart
 
 
 class FakeSparseContext(FakeContext):
@@ -71,6 +71,7 @@ class FakeSparseContext(FakeContext):
         return ok
 
     def gmres(self, slots, shift, psi, rhs_mode, use_jacobi, rtol=1e-8, restart=20, maxiter=50):
+        check_restart("maus_gmres", restart)
         n = self.rows
         info = np.zeros(len(slots), dtype=np.int32)
         inner = np.zeros(len(slots), dtype=np.int32)
@@ -78,6 +79,11 @@ class FakeSparseContext(FakeContext):
         for k, s in enumerate(slots):
             H = self._h(k, shift, psi, rhs_mode)
             rhs = self.pop[0][s, :n].copy() if rhs_mode == 0 else self.b
+            if not (np.all(np.isfinite(H.data if sp.issparse(H) else np.asarray(H))) and np.all(np.isfinite(rhs))):
+                # what SciPy reports after maxiter cycles of NaN and the device at once: info = maxiter, status 0
+                info[k] = max(1, maxiter)
+                self.pop[2][s, :n] = rhs
+                continue
             M = sp.diags(1.0 / H.diagonal(), format="csc") if use_jacobi[k] else None           # AMS:67-75
             count = [0]
             x, inf = spla.gmres(H, rhs, x0=rhs, rtol=rtol, restart=restart, maxiter=maxiter, M=M,
