@@ -24,6 +24,7 @@ SYMBOLS = [
     "maus_lanczos_begin", "maus_lanczos_inject", "maus_lanczos_extend", "maus_lanczos_restart", "maus_lanczos_finish", "maus_herm_match_rows", "maus_get_ritz_rows",
     "maus_sparse_max_n", "maus_band_prepare", "maus_band_reserve", "maus_band_solve", "maus_band_lu_host", "maus_band_workspace_allocs",
     "maus_band_set_method", "maus_band_get_method", "maus_band_kernel_for", "maus_band_outer_nb",
+    "maus_gmres_set_method", "maus_gmres_get_method", "maus_gmres_kernel_for",
     "maus_device_count", "maus_comm_unique_id", "maus_comm_init", "maus_comm_destroy", "maus_comm_info",
     "maus_comm_allgather_records", "maus_comm_allgather_rows", "maus_comm_bcast", "maus_comm_bcast_eigvecs", "maus_comm_set_matrix", "maus_comm_stats",
 ]
@@ -34,9 +35,10 @@ POP_X, POP_U, POP_W, POP_Y = 0, 1, 2, 3
 KIND_EIG, KIND_LINEAR, KIND_SVD = 1, 2, 3
 PERT_NONE, PERT_UNIFORM, PERT_MT19937 = 0, 1, 2
 KC_NAMES = ["zgemm", "lu_panel", "trsm", "laswp", "build_h", "backsolve", "vector",
-            "zgemm_k128", "zgemm_k64", "zgemm_k32", "zgemm_k16", "spmm", "band", "lanczos", "band_blocked", "band_tiled", "band_wide"]
+            "zgemm_k128", "zgemm_k64", "zgemm_k32", "zgemm_k16", "spmm", "band", "lanczos", "band_blocked", "band_tiled", "band_wide", "gmres_wide"]
 BAND_COLUMN, BAND_BLOCKED, BAND_TILED = 0, 1, 2      # maus_band_set_method
 BAND_WIDE = 4                                        # (there is no method 3)
+GMRES_DEFAULT, GMRES_WIDE = 0, 1                     # maus_gmres_set_method
 SPMM_SCHEDULES = {0: None, 1: "rows", 2: "wave"}     # maus_matrix_is_sparse: dense / lane per row / wave per row
 
 
@@ -135,6 +137,9 @@ def load_library():
         "maus_band_set_method": ([vp, C.c_int], C.c_int),
         "maus_band_get_method": ([vp], C.c_int),
         "maus_band_kernel_for": ([vp, C.c_int, C.c_int, C.c_int, ip], C.c_int),
+        "maus_gmres_set_method": ([vp, C.c_int], C.c_int),
+        "maus_gmres_get_method": ([vp], C.c_int),
+        "maus_gmres_kernel_for": ([vp, C.c_int, C.c_int], C.c_int),
         "maus_band_outer_nb": ([vp, C.c_int, C.c_int, C.c_int], C.c_int),
         "maus_device_count": ([], C.c_int),
         "maus_comm_unique_id": ([C.c_char_p], C.c_int),
@@ -645,6 +650,21 @@ class Context:
         """Width of the outer block (64) where an (n, kl, ku) band runs the wide method under the current method, else 0."""
         k = self.lib.maus_band_outer_nb(self.h, int(n), int(kl), int(ku))
         self._ck(min(k, 0), "maus_band_outer_nb")
+        return int(k)
+
+    def gmres_set_method(self, method):
+        """The schedule of gmres()'s post step for a CSR-bound matrix: GMRES_DEFAULT (one workgroup per candidate) or GMRES_WIDE
+        (n split over workgroups, csrc/gmres.hip); dense matrices and gmres_pert ignore it.  Kept across matrices."""
+        self._ck(self.lib.maus_gmres_set_method(self.h, int(method)), "maus_gmres_set_method")
+
+    def gmres_method(self) -> int:
+        return int(self.lib.maus_gmres_get_method(self.h))
+
+    def gmres_kernel_for(self, n, csr) -> int:
+        """What the post step of an n x n matrix (csr: CSR-bound) runs under the current method: 0 a register kernel, 1 the
+        stream kernel, 2 the wide step."""
+        k = self.lib.maus_gmres_kernel_for(self.h, int(n), int(bool(csr)))
+        self._ck(min(k, 0), "maus_gmres_kernel_for")
         return int(k)
 
     def band_lu(self, ab, b, kl, ku, method=None):

@@ -1199,11 +1199,14 @@ int maus_gmres(maus_ctx* c, const int* slots, int count, const double* shift, co
     if (c && (restart < 1 || restart > 20)) FAIL(c, "maus_gmres: restart must be between 1 and 20 (the Krylov basis holds 20 vectors)");
     // Above maus_lu_max_n() (CSR only) one candidate's basis, iterate and product take (R + 3) n complex entries, 386 MB at
     // n = 2^20: a batch runs in chunks whose scratch stays within 1/16 of the device's total HBM (a rule of n and the device).
-    // Candidates never share arithmetic (per-row SpMM, one workgroup per candidate), so the chunking changes no result.
+    // Candidates never share arithmetic (per-row SpMM; a post step whose sums are a candidate's own, whether one workgroup per
+    // candidate or, under maus_gmres_set_method(ctx, 1), the wide step with its per-candidate partial sums, which the rule
+    // counts), so the chunking changes no result.
     if (c && c->csr && c->rows > maus_lu_max_n() && count > 1 && slots && shift && psi && use_jacobi && info_out && inner_out && status) {
         size_t fr = 0, tot = 0;
         HIPCHK(c, hipMemGetInfo(&fr, &tot));
-        const size_t per = sizeof(c128) * (size_t)(restart + 3) * c->rows + 4096;
+        const size_t per = sizeof(c128) * (size_t)(restart + 3) * c->rows + 4096
+                           + (c->gmres_method == 1 ? maus_gmres_wide_bytes_per_candidate(c->rows) : 0);
         const int chunk = (int)std::max<size_t>(1, tot / 16 / per);
         if (count > chunk) {
             for (int off = 0; off < count; off += chunk) {

@@ -52,6 +52,7 @@ int maus_gmres_run(maus_ctx* ctx, const int* slots, int count, const double* shi
                    const c128* Hdense, long ldh, long strideH, int32_t* jacobi_out);
 void maus_band_drop(maus_ctx* c);            // band.hip: the ordering and workspace of the previous sparse matrix
 void maus_lanczos_drop(maus_ctx* c);         // lanczos.hip: the basis and the Ritz rows of the previous sparse matrix
+size_t maus_gmres_wide_bytes_per_candidate(int n);   // gmres.hip: what the wide step adds to a candidate's scratch
 int maus_jacobi_check_run(maus_ctx* ctx, int count, const double* shift, const double* psi, int32_t* ok);
 
 // ---- context ---------------------------------------------------------------------------
@@ -79,6 +80,7 @@ struct maus_ctx {
     int band_method = 0;                                // 0: column kernel, 1: blocked, 2: tiled, 4: wide (maus_band_set_method); kept across matrices
     c128* band_lw = nullptr; int* band_ju = nullptr;    // the blocked / tiled / wide method's panel of L (wide: LW behind it) and reach, per solve of the workspace
     MausLanczos lz;
+    int gmres_method = 0;                               // 0: one workgroup per candidate, 1: the wide step for CSR matrices (maus_gmres_set_method); kept across matrices
     c128* b = nullptr; int bn = 0;                  // rhs
     c128* V = nullptr; int vn = 0;                  // eigenvectors (Hermitian shortcut)
     c128* hq = nullptr; c128* htau = nullptr; int hqn = 0;   // Householder reflectors of maus_herm_tridiag, until the back-transformation (herm.hip)

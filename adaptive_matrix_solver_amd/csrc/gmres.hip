@@ -20,6 +20,10 @@
 // and the candidates' H_k are materialised in the LU workspace (the same build kernels as the direct solve, i.e. the
 // same bits as the reference's H_solve) -- the matvec is then one HBM-bound GEMV per candidate against its own H_k,
 // and the Jacobi scale and its AMS:67-72 gate read diag(H_k) from the materialised matrix.
+//
+// The post step has two schedules for a CSR-bound matrix (maus_gmres_set_method): by default one workgroup per candidate
+// (gmres_post_kernel with w in registers up to n = 16384, gmres_post_stream_kernel above); under method 1 the wide step further
+// down (the gw_* kernels), which splits n over workgroups and joins every sum from per-piece partials in one fixed order.
 #include "ctx.h"
 #include <algorithm>
 #include <cstring>
@@ -606,6 +610,370 @@ gmres_post_stream_kernel(GArgs a, const int* __restrict__ act) {
     }
 }
 
+// ---- the wide step (maus_gmres_set_method(ctx, 1)): the post step of a CSR-bound solve over the whole device ----
+// The arithmetic is gmres_post_stream_kernel's; the ownership is lanczos.hip's.  A workgroup of GW_BT threads owns GW_SPAN
+// consecutive entries of ONE candidate's vectors, two per thread; workgroup q of a launch is piece q % np of active candidate
+// q / np.  Every reduction goes through per-piece partial sums in memory and is joined in one fixed order by every workgroup
+// that needs it (gw_join): thread t adds pieces t, t + 256, ..., then the 64 lanes on the DPP tree of wave_sum_dpp, then the
+// four waves in index order.  All pieces of a candidate compute the same bits from the same partials; piece 0 keeps the value.
+// No atomics on values, no workgroup waits for another: the launch boundaries of the stream are the only synchronisation.
+// A candidate's sums depend on its own data and on n alone -- not on the batch, its order or its neighbours' states.
+constexpr int GW_BT = 256;
+constexpr int GW_E = 2;
+constexpr int GW_SPAN = GW_BT * GW_E;
+
+// what a tick's kernels need of a candidate besides GState: phase and column as the compact kernel found them (the state kernel
+// moves GState on while the finish kernel still needs them), the Hessenberg column under construction, and the state kernel's
+// verdict for the finish kernel
+struct WState {
+    int phase, col, cont, end;        // cont: phase 1 goes on to a new cycle; end: the inner loop ended, x += y @ V[:col+1]
+    double inv, pad;
+    c128 hcol[MAXR + 2];
+    c128 y[MAXR + 1];
+};
+
+// zlartg_dev, operation for operation, with every result component a scalar that is assigned once per branch and the call
+// inlined: the compiler keeps c, s and r in registers (zlartg_dev's reference parameters cost its callers 24 bytes of scratch
+// per lane)
+struct GwRot { double c, sx, sy, rx, ry; };
+__device__ __forceinline__ GwRot gw_zlartg(c128 f, c128 g) {
+    const double safmin = 2.2250738585072014e-308, rtmin = 1.4916681462400413e-154;
+    GwRot o;
+    if (g.x == 0.0 && g.y == 0.0) { o.c = 1.0; o.sx = 0.0; o.sy = 0.0; o.rx = f.x; o.ry = f.y; return o; }
+    if (f.x == 0.0 && f.y == 0.0) {
+        const double d = (g.x == 0.0) ? fabs(g.y) : ((g.y == 0.0) ? fabs(g.x) : sqrt(g.x * g.x + g.y * g.y));
+        o.c = 0.0; o.sx = g.x / d; o.sy = -g.y / d; o.rx = d; o.ry = 0.0; return o;
+    }
+    const double f2 = f.x * f.x + f.y * f.y, g2 = g.x * g.x + g.y * g.y, h2 = f2 + g2;
+    const c128 gc_ = cconj(g);
+    c128 sv;
+    if (f2 >= h2 * safmin) {
+        o.c = sqrt(f2 / h2);
+        o.rx = f.x / o.c; o.ry = f.y / o.c;
+        const double rtmax2 = 6.703903964971299e+153;
+        if (f2 > rtmin && h2 < rtmax2) { const double d = sqrt(f2 * h2); sv = cmul(gc_, cmake(f.x / d, f.y / d)); }
+        else sv = cmul(gc_, cmake(o.rx / h2, o.ry / h2));
+    } else {
+        const double d = sqrt(f2 * h2);
+        o.c = f2 / d;
+        if (o.c >= safmin) { o.rx = f.x / o.c; o.ry = f.y / o.c; } else { const double q = h2 / d; o.rx = f.x * q; o.ry = f.y * q; }
+        sv = cmul(gc_, cmake(f.x / d, f.y / d));
+    }
+    o.sx = sv.x; o.sy = sv.y;
+    return o;
+}
+
+__device__ __forceinline__ c128 gw_block_sum(c128 v, c128* sbuf) {
+    const double re = wave_sum_dpp(v.x), im = wave_sum_dpp(v.y);
+    if ((threadIdx.x & 63) == 0) sbuf[threadIdx.x >> 6] = cmake(re, im);
+    __syncthreads();
+    const c128 s = cmake((sbuf[0].x + sbuf[1].x) + (sbuf[2].x + sbuf[3].x), (sbuf[0].y + sbuf[1].y) + (sbuf[2].y + sbuf[3].y));
+    __syncthreads();
+    return s;
+}
+__device__ __forceinline__ c128 gw_join(const c128* __restrict__ part, int np, c128* sbuf) {
+    c128 acc = cmake(0.0, 0.0);
+    for (int b = threadIdx.x; b < np; b += GW_BT) acc = cadd(acc, part[b]);
+    return gw_block_sum(acc, sbuf);
+}
+
+// gmres_compact_kernel for the wide step: the same lists, the tick's (phase, col) of every active candidate, and what the host
+// needs to issue only the launches the tick has work for: out[0] = active candidates, out[1] = largest col among those in phase 0
+// (-1: none), out[2] = candidates in phase 1, out[3] = sum of col over phase 0 (the byte count of the profile class)
+__global__ void __launch_bounds__(1024)
+gmres_compact_wide_kernel(const GState* __restrict__ st, int count, int rows_per, int R, int* __restrict__ act,
+                          int* __restrict__ zrow, WState* __restrict__ ws, int* __restrict__ out) {
+    __shared__ int scnt[16];
+    __shared__ int sbase, smax, sp1, ssum;
+    if (threadIdx.x == 0) { sbase = 0; smax = -1; sp1 = 0; ssum = 0; }
+    __syncthreads();
+    int mx = -1, p1 = 0, sum = 0;
+    for (int k0 = 0; k0 < count; k0 += 1024) {
+        const int k = k0 + threadIdx.x;
+        const bool on = k < count && st[k].phase != 2;
+        const unsigned long long m = __ballot(on);
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if (lane == 0) scnt[wave] = __popcll(m);
+        __syncthreads();
+        int off = sbase;
+        for (int w = 0; w < wave; ++w) off += scnt[w];
+        if (on) {
+            const int p = off + __popcll(m & ((1ull << lane) - 1ull));
+            const int ph = st[k].phase, col = st[k].col;
+            act[p] = k;
+            zrow[p] = k * rows_per + (ph == 1 ? R + 1 : col);
+            ws[k].phase = ph; ws[k].col = col; ws[k].cont = 0; ws[k].end = 0;
+            if (ph == 1) p1 += 1; else { mx = max(mx, col); sum += col; }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < 16; ++w) t += scnt[w]; sbase += t; }
+        __syncthreads();
+    }
+    atomicMax(&smax, mx); atomicAdd(&sp1, p1); atomicAdd(&ssum, sum);     // integers: any order gives the same result
+    __syncthreads();
+    if (threadIdx.x == 0) { out[0] = sbase; out[1] = smax; out[2] = sp1; out[3] = ssum; }
+}
+
+struct WArgs {
+    WState* ws; c128* part0; c128* part1; c128* pn;     // part0 / part1: the dot products, alternating by column; pn: (|w|^2 before, after)
+    int np;
+};
+
+// Form.  Phase 0: w = psolve(y + sh z) into V[col + 1], pn.x = the piece's share of ||w||^2, part0 = its share of vdot(V[0], w).
+// Phase 1: r = b - (y + sh x) into V[0], pn.x = its share of ||r||^2.
+__global__ void __launch_bounds__(GW_BT)
+gw_form_kernel(GArgs a, const int* __restrict__ act, WArgs wa) {
+    __shared__ c128 sbuf[GW_BT / 64];
+    const int piece = blockIdx.x % wa.np, k = act[blockIdx.x / wa.np];
+    const WState& W = wa.ws[k];
+    const int n = a.n, phase = W.phase, col = W.col;
+    c128* Vk = a.Vb + (long)k * a.rows_per * n;
+    const c128* y = a.Y + (long)k * n;
+    const c128 lam = a.shift[k];
+    const c128 sh = cmake(a.psi[k] - lam.x, -lam.y);
+    const int x0 = piece * GW_SPAN + threadIdx.x;
+    const long o = (long)k * wa.np + piece;
+    if (phase == 1) {
+        const c128* b = rhs_of(a, k);
+        const c128* x = Vk + (long)(a.R + 1) * n;
+        double ss = 0.0;
+#pragma unroll
+        for (int e = 0; e < GW_E; ++e) {
+            const int i = x0 + e * GW_BT;
+            if (i < n) {
+                c128 hx = y[i]; cfma(hx, sh, x[i]);
+                const c128 r = cmake(b[i].x - hx.x, b[i].y - hx.y);
+                Vk[i] = r;
+                ss = fma(r.x, r.x, ss); ss = fma(r.y, r.y, ss);
+            }
+        }
+        const c128 s = gw_block_sum(cmake(ss, 0.0), sbuf);
+        if (threadIdx.x == 0) wa.pn[o].x = s.x;
+        return;
+    }
+    const c128* z = Vk + (long)col * n;
+    const c128* v0 = Vk;
+    c128* w = Vk + (long)(col + 1) * n;
+    double ss = 0.0;
+    c128 acc = cmake(0.0, 0.0);
+#pragma unroll
+    for (int e = 0; e < GW_E; ++e) {
+        const int i = x0 + e * GW_BT;
+        if (i < n) {
+            c128 av = y[i]; cfma(av, sh, z[i]);
+            const c128 v = psolve1(a, k, i, av);
+            w[i] = v;
+            ss = fma(v.x, v.x, ss); ss = fma(v.y, v.y, ss);
+            cfma_conj(acc, v0[i], v);
+        }
+    }
+    const c128 s = gw_block_sum(cmake(ss, 0.0), sbuf);
+    const c128 d = gw_block_sum(acc, sbuf);
+    if (threadIdx.x == 0) { wa.pn[o].x = s.x; wa.part0[o] = d; }
+}
+
+// Phase 1, the decisions of iterative.py:737-748 / 826-838 from the joined ||r||: done (phase 2) or a new cycle (cont)
+__global__ void __launch_bounds__(GW_BT)
+gw_resid_kernel(GArgs a, const int* __restrict__ act, WArgs wa) {
+    __shared__ c128 sbuf[GW_BT / 64];
+    const int k = act[blockIdx.x];
+    WState& W = wa.ws[k];
+    if (W.phase != 1) return;
+    const double rnorm = sqrt(gw_join(wa.pn + (long)k * wa.np, wa.np, sbuf).x);
+    if (threadIdx.x != 0) return;
+    GState& s = a.st[k];
+    bool done = false; int info = 0;
+    double pmf = s.pmf, ptol = s.ptol; int cycle = s.cycle;
+    if (!(rnorm == rnorm)) { done = true; info = a.maxiter; }
+    else if (s.first) { if (rnorm < s.atol) { done = true; info = 0; } }
+    else {
+        if (rnorm <= s.atol) { done = true; info = 0; }
+        else if (s.breakdown) { done = true; info = a.maxiter; }
+        else {
+            if (s.presid <= s.ptol) pmf = fmax(EPS, 0.25 * pmf); else pmf = fmin(1.0, 1.5 * pmf);
+            ptol = s.presid * fmin(pmf, s.atol / rnorm);
+            cycle += 1;
+            if (cycle >= a.maxiter) { done = true; info = a.maxiter; }
+        }
+    }
+    if (done) { s.rnorm = rnorm; s.info = info; s.phase = 2; return; }
+    s.rnorm = rnorm; s.pmf = pmf; s.ptol = ptol; s.cycle = cycle; s.first = 0;
+    W.cont = 1;
+}
+
+// Phase 1, new cycle: V[0] = psolve(r), pn.y = the piece's share of its squared norm
+__global__ void __launch_bounds__(GW_BT)
+gw_psolve_kernel(GArgs a, const int* __restrict__ act, WArgs wa) {
+    __shared__ c128 sbuf[GW_BT / 64];
+    const int piece = blockIdx.x % wa.np, k = act[blockIdx.x / wa.np];
+    const WState& W = wa.ws[k];
+    if (W.phase != 1 || !W.cont) return;
+    const int n = a.n;
+    c128* w = a.Vb + (long)k * a.rows_per * n;
+    const int x0 = piece * GW_SPAN + threadIdx.x;
+    double sv = 0.0;
+#pragma unroll
+    for (int e = 0; e < GW_E; ++e) {
+        const int i = x0 + e * GW_BT;
+        if (i < n) {
+            const c128 v = psolve1(a, k, i, w[i]);
+            w[i] = v;
+            sv = fma(v.x, v.x, sv); sv = fma(v.y, v.y, sv);
+        }
+    }
+    const c128 s = gw_block_sum(cmake(sv, 0.0), sbuf);
+    if (threadIdx.x == 0) wa.pn[(long)k * wa.np + piece].y = s.x;
+}
+
+// Phase 1, new cycle: V[0] /= ||V[0]||; piece 0 starts the cycle in GState (nothing of this tick reads GState after it)
+__global__ void __launch_bounds__(GW_BT)
+gw_start_kernel(GArgs a, const int* __restrict__ act, WArgs wa) {
+    __shared__ c128 sbuf[GW_BT / 64];
+    const int piece = blockIdx.x % wa.np, k = act[blockIdx.x / wa.np];
+    const WState& W = wa.ws[k];
+    if (W.phase != 1 || !W.cont) return;
+    const int n = a.n;
+    c128* w = a.Vb + (long)k * a.rows_per * n;
+    const double tmp = sqrt(gw_join(wa.pn + (long)k * wa.np, wa.np, sbuf).y);
+    const double inv = 1.0 / tmp;
+    const int x0 = piece * GW_SPAN + threadIdx.x;
+#pragma unroll
+    for (int e = 0; e < GW_E; ++e) {
+        const int i = x0 + e * GW_BT;
+        if (i < n) w[i] = cmake(w[i].x * inv, w[i].y * inv);
+    }
+    if (piece == 0 && threadIdx.x == 0) {
+        GState& s = a.st[k];
+        for (int j = 0; j <= a.R; ++j) s.S[j] = cmake(0.0, 0.0);
+        s.S[0] = cmake(tmp, 0.0);
+        s.col = 0; s.breakdown = 0; s.phase = 0;
+    }
+}
+
+// One column of the modified Gram-Schmidt sweep.  kk >= 1: candidates with col >= kk join dot kk - 1 (written by the launch
+// before, or by the form kernel), apply w -= t V[kk - 1] and write their share of vdot(V[kk], w) from the w that leaves.
+// kk == 0 is the tail: every phase-0 candidate joins its last dot (column col), applies the last subtraction and writes
+// pn.y = its share of ||w||^2.
+__global__ void __launch_bounds__(GW_BT)
+gw_mgs_kernel(GArgs a, const int* __restrict__ act, WArgs wa, int kk) {
+    __shared__ c128 sbuf[GW_BT / 64];
+    const int piece = blockIdx.x % wa.np, k = act[blockIdx.x / wa.np];
+    WState& W = wa.ws[k];
+    if (W.phase != 0) return;
+    const int col = W.col;
+    const bool tail = kk == 0;
+    if (tail) kk = col + 1; else if (kk > col) return;
+    const int j = kk - 1, n = a.n;
+    const long o = (long)k * wa.np;
+    const c128 t = gw_join(((j & 1) ? wa.part1 : wa.part0) + o, wa.np, sbuf);
+    if (piece == 0 && threadIdx.x == 0) W.hcol[j] = t;
+    c128* Vk = a.Vb + (long)k * a.rows_per * n;
+    const c128* vj = Vk + (long)j * n;
+    const c128* vk = Vk + (long)kk * n;          // the tail never reads it (it is w)
+    c128* w = Vk + (long)(col + 1) * n;
+    const int x0 = piece * GW_SPAN + threadIdx.x;
+    c128 acc = cmake(0.0, 0.0);
+#pragma unroll
+    for (int e = 0; e < GW_E; ++e) {
+        const int i = x0 + e * GW_BT;
+        if (i < n) {
+            c128 wi = w[i]; cfms(wi, t, vj[i]); w[i] = wi;
+            if (tail) { acc.x = fma(wi.x, wi.x, acc.x); acc.x = fma(wi.y, wi.y, acc.x); }
+            else cfma_conj(acc, vk[i], wi);
+        }
+    }
+    const c128 s = gw_block_sum(acc, sbuf);
+    if (threadIdx.x == 0) {
+        if (tail) wa.pn[o + piece].y = s.x;
+        else ((kk & 1) ? wa.part1 : wa.part0)[o + piece] = s;
+    }
+}
+
+// State: h0 and h1 from the joined partials, then gmres_post_stream_kernel's scalar tail as it stands (Hessenberg column,
+// rotations, S, presid, end_inner, the triangular solve, the next phase / col) on one lane per candidate
+__global__ void __launch_bounds__(GW_BT)
+gw_state_kernel(GArgs a, const int* __restrict__ act, WArgs wa) {
+    __shared__ c128 sbuf[GW_BT / 64];
+    const int k = act[blockIdx.x];
+    WState& W = wa.ws[k];
+    if (W.phase != 0) return;
+    const c128 nn = gw_join(wa.pn + (long)k * wa.np, wa.np, sbuf);
+    if (threadIdx.x != 0) return;
+    GState& s = a.st[k];
+    const int col = W.col, R = a.R;
+    c128* s_h = W.hcol; c128* s_y = W.y;
+    const double h0 = sqrt(nn.x), h1 = sqrt(nn.y);
+    const bool brk = h1 <= EPS * h0;
+    W.inv = brk ? 1.0 : 1.0 / h1;
+    s_h[col + 1] = cmake(brk ? 0.0 : h1, 0.0);
+    for (int kk = 0; kk < col; ++kk) {
+        const double c = s.gc[kk]; const c128 sg = s.gs[kk];
+        const c128 n0 = s_h[kk], n1 = s_h[kk + 1];
+        c128 a0 = cmake(c * n0.x, c * n0.y); cfma(a0, sg, n1);
+        c128 a1 = cmake(c * n1.x, c * n1.y); cfms(a1, cconj(sg), n0);
+        s_h[kk] = a0; s_h[kk + 1] = a1;
+    }
+    const GwRot rot = gw_zlartg(s_h[col], s_h[col + 1]);
+    const double c = rot.c; const c128 sg = cmake(rot.sx, rot.sy), mag = cmake(rot.rx, rot.ry);
+    s.gc[col] = c; s.gs[col] = sg;
+    s_h[col] = mag; s_h[col + 1] = cmake(0.0, 0.0);
+    const c128 Sc = s.S[col];
+    const c128 tmp = cmul(cmake(-sg.x, sg.y), Sc);
+    s.S[col] = cmake(c * Sc.x, c * Sc.y);
+    s.S[col + 1] = tmp;
+    const double presid = hypot(tmp.x, tmp.y);
+    s.presid = presid;
+    s.inner += 1;
+    for (int j = 0; j <= col + 1; ++j) s.h[col][j] = s_h[j];
+    if (brk) s.breakdown = 1;
+    const bool end_inner = (presid <= s.ptol) || brk || (col == R - 1);
+    W.end = end_inner ? 1 : 0;
+    if (end_inner) {
+        if (s.h[col][col].x == 0.0 && s.h[col][col].y == 0.0) s.S[col] = cmake(0.0, 0.0);
+        for (int j = 0; j <= col; ++j) s_y[j] = s.S[j];
+        for (int kk = col; kk > 0; --kk) {
+            if (s_y[kk].x != 0.0 || s_y[kk].y != 0.0) {
+                s_y[kk] = cdiv_np(s_y[kk], s.h[kk][kk]);
+                const c128 t = s_y[kk];
+                for (int j = 0; j < kk; ++j) cfms(s_y[j], t, s.h[kk][j]);
+            }
+        }
+        if (s_y[0].x != 0.0 || s_y[0].y != 0.0) s_y[0] = cdiv_np(s_y[0], s.h[0][0]);
+        s.phase = 1;
+    } else {
+        s.col = col + 1;
+    }
+}
+
+// Finish: V[col + 1] = w * inv, and x += y @ V[:col + 1] where the inner loop ended
+__global__ void __launch_bounds__(GW_BT)
+gw_finish_kernel(GArgs a, const int* __restrict__ act, WArgs wa) {
+    __shared__ c128 s_y[MAXR + 1];
+    const int piece = blockIdx.x % wa.np, k = act[blockIdx.x / wa.np];
+    const WState& W = wa.ws[k];
+    if (W.phase != 0) return;
+    const int n = a.n, col = W.col, end = W.end;
+    const double inv = W.inv;
+    if (end && threadIdx.x <= col) s_y[threadIdx.x] = W.y[threadIdx.x];
+    __syncthreads();
+    c128* Vk = a.Vb + (long)k * a.rows_per * n;
+    c128* w = Vk + (long)(col + 1) * n;
+    c128* x = Vk + (long)(a.R + 1) * n;
+    const int x0 = piece * GW_SPAN + threadIdx.x;
+#pragma unroll
+    for (int e = 0; e < GW_E; ++e) {
+        const int i = x0 + e * GW_BT;
+        if (i < n) {
+            w[i] = cmake(w[i].x * inv, w[i].y * inv);
+            if (end) {
+                c128 acc = x[i];
+                for (int j = 0; j <= col; ++j) cfma(acc, s_y[j], Vk[(long)j * n + i]);
+                x[i] = acc;
+            }
+        }
+    }
+}
+
 // W[slot] <- x ; outputs
 __global__ void __launch_bounds__(GT)
 gmres_finish_kernel(GArgs a, c128* __restrict__ W, long ldw, int* __restrict__ info, int* __restrict__ inner, int* __restrict__ status) {
@@ -668,7 +1036,12 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
     const size_t o_d = take(sizeof(c128) * n), o_v = take(sizeof(c128) * rows_per * count * n), o_y = take(sizeof(c128) * (size_t)count * n),
                  o_s = take(sizeof(GState) * count), o_a = take(sizeof(int) * std::max(count, PAD_ROWS)),
                  o_z = take(sizeof(int) * std::max(count, PAD_ROWS)),
-                 o_n = take(sizeof(int)), o_j = take(sizeof(int) * count), o_o = take(sizeof(int) * 3 * count);
+                 o_n = take(sizeof(int) * 4), o_j = take(sizeof(int) * count), o_o = take(sizeof(int) * 3 * count);
+    // the wide step (method 1, CSR only): per-candidate tick state and three partial-sum buffers of one entry per piece
+    const bool wide = c->gmres_method == 1 && c->csr && !Hdense;
+    const int np = (n + GW_SPAN - 1) / GW_SPAN;
+    const size_t o_w = wide ? take(sizeof(WState) * count) : 0, o_p = wide ? take(sizeof(c128) * 3 * (size_t)count * np) : 0;
+    if (wide && (size_t)count * np > 0x7fffffffull) FAIL(c, "maus_gmres: candidates x pieces of the wide step exceed a launch");
     if (ensure_scratch(c, off)) return -1;
     char* base = (char*)c->scratch;
     GArgs a;
@@ -687,7 +1060,40 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
     hipLaunchKernelGGL(gmres_init_kernel, dim3(count), dim3(GT), 0, c->st, a);
     const long max_ticks = (long)maxiter * (R + 1) + 2;
     int h_nact = 0;
-    for (long tick = 0; tick < max_ticks; ++tick) {
+    WArgs wa;
+    wa.ws = (WState*)(base + o_w); wa.part0 = (c128*)(base + o_p); wa.part1 = wa.part0 + (size_t)count * np;
+    wa.pn = wa.part1 + (size_t)count * np; wa.np = np;
+    for (long tick = 0; wide && tick < max_ticks; ++tick) {
+        // one read-back per tick, as below: how many candidates are active, the largest column among those in phase 0 and how
+        // many are in phase 1 -- the host issues only the launches this tick has work for
+        int h[4] = {0, -1, 0, 0};
+        hipLaunchKernelGGL(gmres_compact_wide_kernel, dim3(1), dim3(1024), 0, c->st, a.st, count, (int)rows_per, R, act, zrow, wa.ws, nact);
+        if (maus_d2h(c, h, nact, sizeof(int) * 4, c->st)) return -1;
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        h_nact = h[0];
+        if (h_nact <= 0) break;
+        const int maxcol = h[1], n1 = h[2], n0 = h_nact - n1;
+        if (maxcol >= R || (n0 > 0) != (maxcol >= 0)) FAIL(c, "maus_gmres: inconsistent tick summary of the wide step");
+        { ProfScope ps(c, KC_SPMM, 8.0 * h_nact * c->Acsr.nnz, 12.0 * c->Acsr.nnz * ((h_nact + 7) / 8) + 32.0 * h_nact * n);
+          maus_spmm_launch(c->st, c->Acsr, c->csr_sched, a.Vb, n, a.Y, n, zrow, act, h_nact); }
+        // bytes: form 64 n per candidate; a Gram-Schmidt column 64 n (w in and out, V[kk - 1], V[kk]), the tail 48 n; finish 32 n;
+        // a new cycle 64 n (x += y @ V of the candidates whose inner loop ends is not counted)
+        ProfScope ps(c, KC_GMRES_WIDE, 0, (double)n * (64.0 * h_nact + 64.0 * h[3] + 80.0 * n0 + 64.0 * n1));
+        const dim3 gp((unsigned)((size_t)h_nact * np)), gc(h_nact), bt(GW_BT);
+        hipLaunchKernelGGL(gw_form_kernel, gp, bt, 0, c->st, a, act, wa);
+        if (n1 > 0) {
+            hipLaunchKernelGGL(gw_resid_kernel, gc, bt, 0, c->st, a, act, wa);
+            hipLaunchKernelGGL(gw_psolve_kernel, gp, bt, 0, c->st, a, act, wa);
+            hipLaunchKernelGGL(gw_start_kernel, gp, bt, 0, c->st, a, act, wa);
+        }
+        if (n0 > 0) {
+            for (int kk = 1; kk <= maxcol; ++kk) hipLaunchKernelGGL(gw_mgs_kernel, gp, bt, 0, c->st, a, act, wa, kk);
+            hipLaunchKernelGGL(gw_mgs_kernel, gp, bt, 0, c->st, a, act, wa, 0);
+            hipLaunchKernelGGL(gw_state_kernel, gc, bt, 0, c->st, a, act, wa);
+            hipLaunchKernelGGL(gw_finish_kernel, gp, bt, 0, c->st, a, act, wa);
+        }
+    }
+    for (long tick = 0; !wide && tick < max_ticks; ++tick) {
         hipLaunchKernelGGL(gmres_compact_kernel, dim3(1), dim3(1024), 0, c->st, a.st, count, (int)rows_per, R, act, zrow, nact);
         if (maus_d2h(c, &h_nact, nact, sizeof(int), c->st)) return -1;
         HIPCHK(c, hipStreamSynchronize(c->st));
@@ -739,4 +1145,24 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
     HIPCHK(c, hipStreamSynchronize(c->st));
     HIPCHK(c, hipGetLastError());
     return 0;
+}
+
+int maus_gmres_set_method(maus_ctx* c, int method) {
+    if (!c) return -1;
+    if (method != 0 && method != 1) FAIL(c, "maus_gmres_set_method: method must be 0 (default) or 1 (wide)");
+    c->gmres_method = method;
+    return 0;
+}
+
+int maus_gmres_get_method(maus_ctx* c) { return c ? c->gmres_method : -1; }
+
+int maus_gmres_kernel_for(maus_ctx* c, int n, int csr) {
+    if (!c) return -1;
+    if (n <= 0 || n > maus_sparse_max_n() || (!csr && n > maus_lu_max_n())) FAIL(c, "maus_gmres_kernel_for: bad size");
+    if (csr && c->gmres_method == 1) return 2;
+    return n <= 64 * GT ? 0 : 1;
+}
+
+size_t maus_gmres_wide_bytes_per_candidate(int n) {
+    return sizeof(WState) + sizeof(c128) * 3 * (size_t)((n + GW_SPAN - 1) / GW_SPAN) + 512;
 }

@@ -248,6 +248,17 @@ def sparse_direct_mode(mode):
     return mode
 
 
+SPARSE_GMRES_MODES = ("auto", "wide")
+
+
+def sparse_gmres_mode(mode):
+    """The `sparse_gmres` keyword: an explicit value, else MAUS_SPARSE_GMRES, else 'auto'."""
+    mode = mode if mode is not None else os.environ.get("MAUS_SPARSE_GMRES", "auto")
+    if mode not in SPARSE_GMRES_MODES:
+        raise ValueError(f"sparse_gmres must be one of {SPARSE_GMRES_MODES}, not {mode!r}")
+    return mode
+
+
 SPARSE_EIGSH_MODES = ("auto", "dense", "lanczos")
 
 
@@ -347,7 +358,8 @@ class DeviceEngine:
     _default = None
 
     def __init__(self, device: int = 0, pert_mode: str = "auto", gmres_compat: str = "rtol",
-                 comm=None, ctx=None, eigh_mode: str = "auto", sparse_mode=None, sparse_direct=None, sparse_eigsh=None):
+                 comm=None, ctx=None, eigh_mode: str = "auto", sparse_mode=None, sparse_direct=None, sparse_eigsh=None,
+                 sparse_gmres=None):
         self.ctx = ctx if ctx is not None else _cabi.Context(device)
         cap_blas_threads()
         # Hermitian eigendecomposition (AMS:161), once per matrix: 'host' = scipy.linalg.eigh, the reference's call, (lambda, V)
@@ -368,6 +380,11 @@ class DeviceEngine:
         # in one rank-64 update on the fp64 MFMA pipe, for 64 <= kl <= 4096 (opt-in too).  MAUS_SPARSE_DIRECT sets the
         # default.  Chosen once per bound matrix (_band).
         self.sparse_direct = sparse_direct_mode(sparse_direct)
+        # GMRES of a sparse matrix: 'auto' = the post step of csrc/gmres.hip with one workgroup per candidate, as
+        # ever; 'wide' = the same step with n split over workgroups of 512 entries and every sum joined in a fixed order, so
+        # that a few candidates at large n occupy the whole device (opt-in, 'auto' never picks it; x agrees to rounding, not
+        # bit for bit).  MAUS_SPARSE_GMRES sets the default.  Told to the context when a sparse matrix is bound.
+        self.sparse_gmres = sparse_gmres_mode(sparse_gmres)
         # sparse Hermitian shortcut (AMS:186-216): 'dense' = one scipy.linalg.eigh of A.toarray() per matrix, 'lanczos' =
         # thick-restart Lanczos on the CSR matrix on the device, 'auto' the first up to maus_lu_max_n() and the second above.
         # MAUS_SPARSE_EIGSH sets the default.
@@ -426,6 +443,8 @@ class DeviceEngine:
             if comm is not None and comm.world > 1:
                 raise NotImplementedError("sharded runs (comm.world > 1) with a sparse matrix are not supported")
             self.ctx.set_matrix_csr(A)
+            if self.sparse_gmres == "wide":     # the only mode that touches the method: contexts without it keep working
+                self.ctx.gmres_set_method(1)
             self._sparse = True
             self._band = self.uses_band(A.shape[0]) and A.shape[0] == A.shape[1]
             self._band_ready = False            # set_matrix_csr dropped the previous ordering

@@ -31,7 +31,7 @@ import numpy as np
 from . import _cabi
 from ._cabi import POP_U, POP_X
 from .candstore import C_NP as _C_NP, C_PY as _C_PY, EXACT as _EXACT, F_NP as _F_NP, F_PY as _F_PY, HREF as _HREF, MISSING as _MISSING
-from .engine import DIRECT, GMRES, DeviceEngine, _advance_numpy_stream, sparse_direct_mode, sparse_eigsh_mode
+from .engine import DIRECT, GMRES, DeviceEngine, _advance_numpy_stream, sparse_direct_mode, sparse_eigsh_mode, sparse_gmres_mode
 
 
 class ProblemType(Enum):                     # AMS:10-13
@@ -160,7 +160,7 @@ class InverseIterateSolver:
     _engine = None          # private context: every call uploads its own A_target
 
     def __init__(self, N, base_psi_epsilon, max_attempts, preferred_method="direct_solve", is_sparse=False,
-                 gmres_compat="rtol", pert_mode="uniform", sparse_mode=None, sparse_direct=None):
+                 gmres_compat="rtol", pert_mode="uniform", sparse_mode=None, sparse_direct=None, sparse_gmres=None):
         self.N = N
         self.base_psi_epsilon = base_psi_epsilon
         self.max_attempts = max_attempts
@@ -171,6 +171,7 @@ class InverseIterateSolver:
         self.pert_mode = pert_mode
         self.sparse_mode = _sparse_mode(sparse_mode)
         self.sparse_direct = sparse_direct_mode(sparse_direct)
+        self.sparse_gmres = sparse_gmres_mode(sparse_gmres)
         self.last_trace = []
 
     @classmethod
@@ -191,6 +192,11 @@ class InverseIterateSolver:
             import scipy.sparse as sp
             A_sp = A_target if _is_sparse(A_target) else sp.csr_matrix(A_target)
             ctx.set_matrix_csr(A_sp)
+            # the context is shared by every InverseIterateSolver: each solve states the GMRES schedule ('wide' is opt-in)
+            if self.sparse_gmres == "wide":
+                ctx.gmres_set_method(_cabi.GMRES_WIDE)
+            elif getattr(ctx, "gmres_method", None) is not None and ctx.gmres_method() != _cabi.GMRES_DEFAULT:
+                ctx.gmres_set_method(_cabi.GMRES_DEFAULT)
             # direct solves above maus_lu_max_n() (or with sparse_direct='band'): the band LU of csrc/band.hip
             band = self.sparse_direct in ("band", "blocked", "tiled", "wide") or (self.sparse_direct == "auto" and n > ctx.lu_max_n())
             if band:
@@ -761,10 +767,11 @@ class MAUS_Solver:
                  global_convergence_tol=1e-8, *, device=0, pert_mode="auto", gmres_compat="rtol",
                  record_history=None, comm=None, quiet=False, engine=None, gram_min=8, cond_exact_max=1024,
                  diag_info=None, eigh_mode="auto", sparse_mode=None, sparse_direct=None, sparse_eigsh=None,
-                 sparse_hermitian_check=None):
+                 sparse_hermitian_check=None, sparse_gmres=None):
         sparse_mode = _sparse_mode(sparse_mode)
         sparse_direct = sparse_direct_mode(sparse_direct)
         sparse_eigsh = sparse_eigsh_mode(sparse_eigsh)
+        sparse_gmres = sparse_gmres_mode(sparse_gmres)
         # symmetry test of a sparse matrix in the start-up diagnostics: 'reference' = AMS:386-396 (dense copy, given up above
         # n^2 = 1e7), 'sparse' = the same two verdicts from the stored entries at any n (opt-in)
         self._sparse_hermitian_check = _sparse_hermitian_check(sparse_hermitian_check)
@@ -788,7 +795,7 @@ class MAUS_Solver:
         self.engine = engine if engine is not None else DeviceEngine(device=device, pert_mode=pert_mode,
                                                                      gmres_compat=gmres_compat, comm=comm, eigh_mode=eigh_mode,
                                                                      sparse_mode=sparse_mode, sparse_direct=sparse_direct,
-                                                                     sparse_eigsh=sparse_eigsh)
+                                                                     sparse_eigsh=sparse_eigsh, sparse_gmres=sparse_gmres)
         # `diag_info`: start-up diagnostics of the same matrix taken from an earlier solver (bench side runs)
         if diag_info is not None:
             self.diag_info = dict(diag_info)

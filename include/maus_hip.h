@@ -352,6 +352,20 @@ int maus_gmres_pert(maus_ctx* ctx, const int* slots, int count, const double* sh
                     int rhs_mode, const int32_t* want_jacobi, int pert_mode, const void* pert_data,
                     double rtol, int restart, int maxiter,
                     int32_t* info_out, int32_t* inner_out, int32_t* status, int32_t* jacobi_out);
+/* The schedule of maus_gmres's post step (scale, Gram-Schmidt, rotations, exits) for a CSR-bound matrix.
+ *   maus_gmres_set_method  0 (the default): one workgroup per candidate holds or streams that candidate's vectors.
+ *                          1 (wide): the entries of n are split over workgroups of 512, every reduction goes through per-piece
+ *                          partial sums joined in one fixed order, about col + 6 launches per tick over the whole device.  The
+ *                          algorithm, its exits and the status contract are the same; the dot products are summed in another
+ *                          order, so x agrees with method 0 to rounding, not bit for bit.  A candidate's x, info and inner count
+ *                          still depend on its own data and on n alone.  Under method 1 EVERY CSR-bound maus_gmres runs the wide
+ *                          step, at any n >= 1; dense matrices and maus_gmres_pert ignore the method.  Kept across matrices.
+ *   maus_gmres_get_method  the current method.
+ *   maus_gmres_kernel_for  what the post step of an n x n matrix (csr != 0: CSR-bound) runs under the current method:
+ *                          0 a register kernel (n <= 16384), 1 the stream kernel, 2 the wide step. */
+int maus_gmres_set_method(maus_ctx* ctx, int method);
+int maus_gmres_get_method(maus_ctx* ctx);
+int maus_gmres_kernel_for(maus_ctx* ctx, int n, int csr);
 /* AMS:67-72 gate: ok[i]=1 iff all 1/diag(H_k) finite and all |diag(H_k)| > 1e-12 */
 int maus_jacobi_check(maus_ctx* ctx, int count, const double* shift_c128, const double* psi, int32_t* ok);
 
@@ -411,7 +425,9 @@ int maus_timer_stop(maus_ctx* ctx, float* ms_out);
  * (maus_band_set_method; bytes: the band moved once per block step over the full reach kl + ku, not an MFMA class),
  * 15 band solves by the tiled method (bytes: as 14 plus L21 once per column tile of the trailing update)
  * 16 band solves by the wide method (bytes, an upper end: the band once per outer block of 64 columns over the full reach,
- *    LW once per column tile of the outer update, and the inner steps' bytes inside the block) */
+ *    LW once per column tile of the outer update, and the inner steps' bytes inside the block)
+ * 17 the wide GMRES post step (maus_gmres_set_method; one bracket per tick around all its launches; flops 0, bytes 64 n per
+ *    candidate and Gram-Schmidt column plus the form, tail, finish and new-cycle passes) */
 /* on = 1: event pairs around every launch of every class; on = 2: around the K>=256 zgemm launches only (class 0;
  * long kernels, so cheap enough for a timed region -- full bracketing costs 3-5 % of throughput; MAUS_PROF_STRIDE
  * can thin them out, each sample then stands for `stride` launches); 0: off */
