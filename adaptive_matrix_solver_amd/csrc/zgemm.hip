@@ -23,7 +23,9 @@
 // but only if independent waves fill each other's waits: see the launcher for the measured
 // tile / occupancy choice.
 #include "common.h"
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #ifndef MAUS_WC
 #define MAUS_WC 8
@@ -329,6 +331,9 @@ zgemm_kernel(int M, int N, int K,
 //   B image [8 k][32 n]  (512 B per k-row): natural order; the fragment read b = B[k = lane>>4][col = lane&15] is 16
 //       consecutive elements of one row.
 // ---------------------------------------------------------------------------------------
+// MB x NB = 4 x 2 (the 128 x 64 workgroup tile of the large LU updates, 64 x 32 per wave): 192 accumulator registers, so the
+// kernel runs at two workgroups per CU and keeps everything else small -- see OFF32 below.  Per MFMA it reads a quarter less
+// from LDS than the 32 x 32 wave tile and passes half as many barriers and DMA issues.
 // BLAY = 1 (round 3): B is row-major [n][k] (dot-product form: Y = X A^T, Gram blocks, [V W][W V]^H) and gets the A image's
 // treatment -- [BN rows][8 k], 8 lanes per row, the same source-side swizzle and fragment read.  CONJA / CONJB: the operand's
 // imaginary part enters with the opposite sign, i.e. with a_i' = -Ai (b_i' = -Bi)
@@ -377,7 +382,38 @@ zgemm3m_dma_kernel(int M, int N, int K,
     const int wm = wave / WN, wn = wave - wm * WN;
 
     // per-lane DMA sources.  A: wave w issues the 8-row blocks A_PW*w .. ; B: wave w issues the 64-element pieces B_PW*w ..
-    const c128* srcA[A_PW];
+    // OFF32 (the 128 x 64 tile of the LU updates, whose 192 accumulator registers leave no room for six 64-bit pointers per
+    // lane): the sources are 32-bit byte offsets of the lane against a wave-uniform base.  Tile-major, everything that moves
+    // with k0 or with the wave is uniform: an A source is row * 1 KB + 16 kk inside the 64-column tile of k0 (at most npad KB),
+    // and the B sources of a wave differ from one per-lane column offset (per 64-column piece of the image) only by whole
+    // rows of 1 KB (the columns reach at most two column tiles past the tile of n0: 2 npad KB).  global_load_lds takes
+    // exactly this form (SGPR base + VGPR offset).
+    constexpr bool OFF32 = TILED && BLAY == 0 && MB * NB >= 8;
+    constexpr int B_CP = OFF32 ? BN / 64 : 1;                  // 64-column pieces per k-row of the B image
+    static_assert(!OFF32 || (BN % 64 == 0 && B_PW % B_CP == 0), "OFF32: whole 64-column pieces");
+    const c128* srcA[OFF32 ? 1 : A_PW];
+    const c128* srcB[OFF32 ? 1 : B_PW];
+    unsigned offA[OFF32 ? A_PW : 1], offB[OFF32 ? B_CP : 1];
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    const long ldb_e = TILED ? 64 : ldb;
+    static_assert(!(TILED && BLAY), "tiled operands: plain layout only");
+    if constexpr (OFF32) {
+#pragma unroll
+        for (int j = 0; j < A_PW; ++j) {
+            const int r = (A_PW * wave + j) * 8 + (lane >> 3);
+            const int kk = (lane & 7) ^ ((r >> 1) & 7);
+            const int gm = min(m0 + r, M - 1);
+            offA[j] = (unsigned)((a_rows ? a_rows[gm] : gm) * 64 + kk) * 16u;
+        }
+        const int ct0 = (tcol.z + n0) >> 6;                    // column tile of the block's first column
+#pragma unroll
+        for (int c = 0; c < B_CP; ++c) {
+            const int col = tcol.z + min(n0 + c * 64 + lane, N - 1);
+            offB[c] = (unsigned)(((col >> 6) - ct0) * (int)ldb * 64 + (col & 63)) * 16u;
+        }
+        srcA[0] = A;
+        srcB[0] = B + ((long)ct0 * ldb << 6) + (long)(tcol.y + (B_PW / B_CP) * wave_u) * 64;
+    } else {
 #pragma unroll
     for (int j = 0; j < A_PW; ++j) {
         const int r = (A_PW * wave + j) * 8 + (lane >> 3);
@@ -385,9 +421,6 @@ zgemm3m_dma_kernel(int M, int N, int K,
         const int gm = min(m0 + r, M - 1);
         srcA[j] = A + (long)(a_rows ? a_rows[gm] : gm) * (TILED ? 64 : lda) + kk;
     }
-    static_assert(!(TILED && BLAY), "tiled operands: plain layout only");
-    const c128* srcB[B_PW];
-    const long ldb_e = TILED ? 64 : ldb;
 #pragma unroll
     for (int j = 0; j < B_PW; ++j) {
         if (BLAY == 0) {
@@ -400,11 +433,35 @@ zgemm3m_dma_kernel(int M, int N, int K,
             srcB[j] = B + (long)min(n0 + r, N - 1) * ldb + kk;
         }
     }
+    }
 
     auto issue = [&](int st, int k0) {
         c128* As = smem + st * (A_ST + B_ST);
         c128* Bs = As + A_ST;
         const long ta = TILED ? tile_off(lda, tcol.x + k0) : (long)k0;     // wave-uniform; 8 consecutive k never leave a tile
+        if constexpr (OFF32) {
+            // the bases pass through an SGPR constraint and the offsets through a VGPR one: otherwise loop strength reduction
+            // turns base + offset back into per-lane 64-bit pointers that advance with k0, or the zero extension of the
+            // offset is hoisted out of the loop and the SGPR-base form of the instruction is no longer matched.  The LDS
+            // destinations (m0) come from the scalar wave number.
+            const char* ba = (const char*)(srcA[0] + ta);
+            const char* bb = (const char*)(srcB[0] + (long)k0 * 64);
+            asm volatile("" : "+s"(ba), "+s"(bb));
+#pragma unroll
+            for (int j = 0; j < A_PW; ++j) {
+                unsigned o = offA[j];
+                asm volatile("" : "+v"(o));
+                __builtin_amdgcn_global_load_lds((const void*)(ba + o), (__attribute__((address_space(3))) void*)(As + (A_PW * wave_u + j) * 64), 16, 0, 0);
+            }
+#pragma unroll
+            for (int j = 0; j < B_PW; ++j) {    // piece j: k-row (B_PW / B_CP) * wave + j / B_CP, columns 64 (j % B_CP) ..
+                unsigned o = offB[j % B_CP];
+                asm volatile("" : "+v"(o));
+                if (j && j % B_CP == 0) { bb += 1024; asm volatile("" : "+s"(bb)); }
+                __builtin_amdgcn_global_load_lds((const void*)(bb + o), (__attribute__((address_space(3))) void*)(Bs + (B_PW * wave_u + j) * 64), 16, 0, 0);
+            }
+            return;
+        }
 #pragma unroll
         for (int j = 0; j < A_PW; ++j)
             __builtin_amdgcn_global_load_lds((const void*)(srcA[j] + ta), (__attribute__((address_space(3))) void*)(As + (A_PW * wave + j) * 64), 16, 0, 0);
@@ -427,6 +484,17 @@ zgemm3m_dma_kernel(int M, int N, int K,
     const int arow0 = wm * 16 * MB + (lane & 15);
     const int bcol0 = wn * 16 * NB + (lane & 15);
     const int q = lane >> 4;
+    // OFF32: the fragment reads as three per-lane LDS byte addresses (A for each half-step: the swizzle (r >> 1) & 7 is the
+    // same for every 16-row block of the wave tile; B), everything else an instruction offset
+    typedef double lds_d2_t __attribute__((ext_vector_type(2)));
+    typedef __attribute__((address_space(3))) const lds_d2_t lds_d2;          // one ds_read_b128
+    unsigned ra[2] = {0, 0}, rb = 0;
+    if constexpr (OFF32) {
+        static_assert(NST == 2, "OFF32: two stages");
+        const unsigned sb = (unsigned)(unsigned long)(__attribute__((address_space(3))) void*)smem;
+        for (int ks = 0; ks < 2; ++ks) ra[ks] = sb + 16u * (arow0 * BKS + ((ks * 4 + q) ^ ((arow0 >> 1) & 7)));
+        rb = sb + 16u * (A_ST + q * BN + bcol0);
+    }
     for (int t = 0; t < nst; ++t) {
         // stage t has landed once at most NST-2 younger stages (DMA_PW instructions each) are still in flight
         if (NST >= 3 && t + NST - 2 < nst) asm volatile("s_waitcnt vmcnt(%0)" :: "n"((NST - 2) * DMA_PW) : "memory");
@@ -445,12 +513,14 @@ zgemm3m_dma_kernel(int M, int N, int K,
 #pragma unroll
             for (int i = 0; i < MB; ++i) {
                 const int r = arow0 + i * 16;
-                fa[ks][i] = As[r * BKS + (k ^ ((r >> 1) & 7))];
+                if constexpr (OFF32) { const lds_d2_t v = *(lds_d2*)(unsigned long)(ra[ks] + (t & 1) * (16u * (A_ST + B_ST)) + 16u * (i * 16 * BKS)); fa[ks][i] = cmake(v.x, v.y); }
+                else fa[ks][i] = As[r * BKS + (k ^ ((r >> 1) & 7))];
             }
 #pragma unroll
             for (int j = 0; j < NB; ++j) {
                 const int cn = bcol0 + j * 16;
-                fb[ks][j] = BLAY ? Bs[cn * BKS + (k ^ ((cn >> 1) & 7))] : Bs[k * BN + cn];
+                if constexpr (OFF32) { const lds_d2_t v = *(lds_d2*)(unsigned long)(rb + (t & 1) * (16u * (A_ST + B_ST)) + 16u * (ks * 4 * BN + j * 16)); fb[ks][j] = cmake(v.x, v.y); }
+                else fb[ks][j] = BLAY ? Bs[cn * BKS + (k ^ ((cn >> 1) & 7))] : Bs[k * BN + cn];
             }
         }
         if (t + NST - 1 < nst) issue((t + NST - 1) % NST, (t + NST - 1) * BKS);     // into the buffer stage t-1 used
@@ -561,6 +631,26 @@ void launch_lu_only(hipStream_t st, int M, int N, int K, const c128* A, long lda
                        M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, alpha, beta, tiles_n, nwg, a_rows, c_rows, rows_stride, tcol);
 }
 
+// MAUS_LU_TILE=64x64|128x64 (read once per process): the workgroup tile of the large LU trailing updates, for timing one tile
+// against the other in one binary and for comparing their bits.  128x64: every update with M, N >= MAUS_LU_LT_MIN on the DMA
+// path, whatever its K; 64x64: the rule before the 128 x 64 tile (64 x 64 from 1536).  Unset: the rule of maus_zgemm_launch_lu.
+#ifndef MAUS_LU_LT_MIN
+#define MAUS_LU_LT_MIN 1024
+#endif
+int lu_tile_mode()
+{
+    static const int mode = [] {
+        const char* e = getenv("MAUS_LU_TILE");
+        if (!e || !*e) return 0;
+        if (!strcmp(e, "128x64")) return 2;
+        if (!strcmp(e, "64x64")) return 3;
+        fprintf(stderr, "MAUS_LU_TILE=%s: expected 64x64 or 128x64\n", e);
+        abort();
+        return 0;
+    }();
+    return mode;
+}
+
 }  // namespace
 
 // Host-side launcher (device pointers).  batch matrices at element strides sA/sB/sC.
@@ -639,8 +729,18 @@ void maus_zgemm_launch_lu(hipStream_t st, int M, int N, int K, const c128* H, co
     if (M > 32 && (K % 8) == 0 && K >= dma_kmin) {
         // (round 3: 64 x 64 tiles from M >= 1024 / 512 and N >= 128 / 256 / 1024, or only from 2048: the 181-solve sweep stays
         // within 0.5 ms of 494 ms -- the K = 128 / 256 levels are not bound by the tile shape)
-        if (M >= 1536 && N >= 1536) launch_dma<2, 3, 2, 2, true>(ARGS);      // 64 x 64 tiles, three workgroups per CU
-        else launch_dma<2, 5, 2, 1, true>(ARGS);
+        // 128 x 64 tiles (64 x 32 per wave: a quarter less LDS traffic per MFMA than the 32 x 32 wave tile, half the barriers
+        // and DMA issues), two workgroups per CU, for the outer updates: 90.4 against 88.4 at 3584 x 3616 x 512 and 86.6
+        // against 84.9 (64 x 32 tiles) at 1024 x 1056 x 512, 181 matrices; the 64 x 128 tile stayed at 64 x 64's rate (89.1)
+        // and is gone (profiles/zgemm_large_tile_rates.txt).  Same summation order, same bits.
+        // Only where the grid is at least eight rounds of the 512 workgroups the chip holds: with fewer, larger tiles the last,
+        // partly filled round weighs more (one to eight matrices: 37-66 against 47-70 at 1024, 46 / 62 against 58 / 69 at 1536
+        // with one / two matrices, equal from 1200-3200 tiles on).
+        const int tile = lu_tile_mode();
+        const long tiles = (long)((M + 127) / 128) * ((N + 63) / 64) * batch;
+        if (M >= MAUS_LU_LT_MIN && N >= MAUS_LU_LT_MIN && (tile == 2 || (tile == 0 && K >= 256 && tiles >= 4096))) { launch_dma<2, 2, 4, 2, true>(ARGS); return; }
+        if (M >= 1536 && N >= 1536) { launch_dma<2, 3, 2, 2, true>(ARGS); return; }      // 64 x 64 tiles, three workgroups per CU
+        launch_dma<2, 5, 2, 1, true>(ARGS);
         return;
     }
     if (M <= 32) { launch_lu_only<32, 64, 16, 1, 4, false, 4, true, true>(ARGS); return; }
