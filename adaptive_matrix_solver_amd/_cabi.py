@@ -38,6 +38,7 @@ KC_NAMES = ["zgemm", "lu_panel", "trsm", "laswp", "build_h", "backsolve", "vecto
             "zgemm_k128", "zgemm_k64", "zgemm_k32", "zgemm_k16", "spmm", "band", "lanczos", "band_blocked", "band_tiled", "band_wide", "gmres_wide"]
 BAND_COLUMN, BAND_BLOCKED, BAND_TILED = 0, 1, 2      # maus_band_set_method
 BAND_WIDE = 4                                        # (there is no method 3)
+BAND_NARROW = 8                                      # (nor 5, 6, 7)
 GMRES_DEFAULT, GMRES_WIDE = 0, 1                     # maus_gmres_set_method
 SPMM_SCHEDULES = {0: None, 1: "rows", 2: "wave"}     # maus_matrix_is_sparse: dense / lane per row / wave per row
 
@@ -631,8 +632,8 @@ class Context:
         return int(self.lib.maus_band_workspace_allocs(self.h))
 
     def band_set_method(self, method):
-        """The kernels of the band entry points: BAND_COLUMN (the default), BAND_BLOCKED, BAND_TILED or BAND_WIDE; kept across
-        matrices."""
+        """The kernels of the band entry points: BAND_COLUMN (the default), BAND_BLOCKED, BAND_TILED, BAND_WIDE or
+        BAND_NARROW; kept across matrices."""
         self._ck(self.lib.maus_band_set_method(self.h, int(method)), "maus_band_set_method")
 
     def band_method(self) -> int:
@@ -640,7 +641,7 @@ class Context:
 
     def band_kernel_for(self, n, kl, ku):
         """(kernel, nb) that an (n, kl, ku) band runs under the current method: (BAND_COLUMN, 1), (BAND_BLOCKED, nb),
-        (BAND_TILED, nb) or (BAND_WIDE, nb of the inner steps)."""
+        (BAND_TILED, nb), (BAND_WIDE, nb of the inner steps) or (BAND_NARROW, 1)."""
         nb = C.c_int()
         k = self.lib.maus_band_kernel_for(self.h, int(n), int(kl), int(ku), C.byref(nb))
         self._ck(min(k, 0), "maus_band_kernel_for")

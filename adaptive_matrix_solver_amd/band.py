@@ -71,10 +71,21 @@ def runs_wide(kl: int, ku: int) -> bool:
     return WIDE_MIN_KL <= kl <= WIDE_MAX_KL
 
 
-def band_bytes_per_solve(n: int, kl: int, ku: int, blocked: bool = False, tiled: bool = False, wide: bool = False) -> int:
+NARROW_MAX_KL = 15              # the narrow method's range under sparse_direct='narrow': the bands whose live columns
+NARROW_MAX_KV = 31              # (kl + ku + 1 of them) fit its LDS ring; the column kernel outside it
+
+
+def runs_narrow(kl: int, ku: int) -> bool:
+    """Whether the narrow method takes a (kl, ku) band when it is selected (band_runs_narrow in csrc/band.hip)."""
+    return 0 <= kl <= NARROW_MAX_KL and kl + ku <= NARROW_MAX_KV
+
+
+def band_bytes_per_solve(n: int, kl: int, ku: int, blocked: bool = False, tiled: bool = False, wide: bool = False,
+                         narrow: bool = False) -> int:
     """Device memory of one band solve: the band storage, the right-hand side and the pivots (csrc/band.hip); with
     `blocked` (`tiled`), and a band the blocked (tiled) method takes, its panel of L and its reach as well; with `wide` the
-    tiled method's where that runs, and the L of the outer block ((kl + 64) x 64) where the wide method does."""
+    tiled method's where that runs, and the L of the outer block ((kl + 64) x 64) where the wide method does.  `narrow` adds
+    nothing: the narrow method works in the column kernel's workspace."""
     per = 16 * ((2 * kl + ku + 1) * n + n) + 4 * n
     if (blocked and runs_blocked(kl, ku)) or ((tiled or wide) and runs_tiled(kl, ku)):
         per += 16 * (kl + BLOCKED_NB) * BLOCKED_NB + 4

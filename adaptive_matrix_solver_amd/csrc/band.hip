@@ -22,6 +22,8 @@
 // block row and the trailing update as launches of their own over (column tile, row tile)) for kl up to TIL_MAX_KL.
 // maus_band_set_method(ctx, 4) selects the wide method at the end (zgbtrf's two levels: outer blocks of 64 columns factored by
 // the tiled steps, then one rank-64 update on the MFMA pipe) for WID_MIN_KL <= kl <= WID_MAX_KL.
+// maus_band_set_method(ctx, 8) selects the narrow method (the column kernel's steps by one wave per matrix on an LDS ring of
+// column slots, the band streamed through it in chunks) for kl <= NAR_MAX_KL, kl + ku <= NAR_MAX_KV; the column kernel's bits.
 #include "ctx.h"
 #include <climits>
 #include <utility>
@@ -527,9 +529,18 @@ constexpr int WID_MAX_KL = TIL_MAX_KL;
 
 bool band_runs_wide(int method, int kl, int ku) { (void)ku; return method == 4 && kl >= WID_MIN_KL && kl <= WID_MAX_KL; }
 
-// 0: the column kernel, 1: blocked, 2: tiled, 4: wide -- what a (kl, ku) band runs under `method`; the (inner) block width
-// with it.  Under method 4 a band with TIL_MIN_KL <= kl < WID_MIN_KL runs exactly what the tiled method runs.
+// the narrow method (maus_band_set_method(ctx, 8), further down): the widest band whose live columns fit its LDS ring
+constexpr int NAR_MAX_KL = 15;
+constexpr int NAR_MAX_KV = 31;
+
+bool band_runs_narrow(int method, int kl, int ku) { return method == 8 && kl <= NAR_MAX_KL && kl + ku <= NAR_MAX_KV; }
+
+// 0: the column kernel, 1: blocked, 2: tiled, 4: wide, 8: narrow -- what a (kl, ku) band runs under `method`; the (inner)
+// block width with it.  Under method 4 a band with TIL_MIN_KL <= kl < WID_MIN_KL runs exactly what the tiled method runs.
+// Kinds 1, 2 and 4 keep a panel of L and a reach per solve (band_kind_blocked); kinds 0 and 8 share one workspace.
+bool band_kind_blocked(int kind) { return kind == 1 || kind == 2 || kind == 4; }
 int band_kind(int method, int kl, int ku) {
+    if (method == 8) return band_runs_narrow(8, kl, ku) ? 8 : 0;
     if (method == 4) return band_runs_wide(4, kl, ku) ? 4 : (kl < WID_MIN_KL && band_runs_tiled(2, kl, ku) ? 2 : 0);
     return band_runs_blocked(method, kl, ku) ? 1 : (band_runs_tiled(method, kl, ku) ? 2 : 0);
 }
@@ -957,6 +968,220 @@ hipError_t launch_wide(const BandArgs& a, const BlkArgs& w, c128* lwo, int G, hi
     }
 }
 
+// ---- the narrow method (maus_band_set_method(ctx, 8)) -------------------------------------------------------
+// The column kernel's steps on a band that never leaves the chip while it is live.  One wave per matrix; the columns a step
+// can touch (j .. j + kv, kv <= NAR_MAX_KV) sit in an LDS ring of NAR_SLOTS column slots of NAR_LD rows, column c in slot
+// c % NAR_SLOTS, the right-hand side beside them.  In zgbtf2 an interchange goes to the right only, so column j is final after
+// step j: a column enters the ring once and leaves once, NAR_CH columns (one chunk, contiguous in band storage) at a time.
+// At the top of the chunk of steps j0 .. j0 + 15:
+//     enter   columns j0 + 32 .. j0 + 47 from the registers they were loaded into one chunk earlier (their fill rows zeroed,
+//             as zgbtf2 zeroes them before a pivot row can reach them); columns j0 .. j0 + 47 are then resident, and the last
+//             step of the chunk reaches column j0 + 15 + kv <= j0 + 46,
+//     leave   columns j0 - 16 .. j0 - 1, x and ipiv with them, by coalesced stores,
+//     load    columns j0 + 48 .. j0 + 63 into registers: in flight for the 16 steps of the chunk.
+// A step is band_factor_kernel's, operation for operation: every element is changed by the same fused operation on the same
+// operands and the pivot search is the same exact maximum, so x, ipiv, info and flags are the column kernel's bits.  Only who
+// does what differs: the candidates of column j sit one per lane, so the pivot and the old top entry come by v_readlane; every
+// lane of a row forms the row's multiplier itself (the same operation on the same operands) instead of reading it back; and
+// the km x (ju - j) update is spread over all 64 lanes, RW (the power of two >= kl) rows by 64 / RW columns at a time.
+// All barriers are lds_barrier(): the wave is alone in its workgroup and must not wait for its loads in flight.
+constexpr int NAR_CH = 16;                              // columns per chunk
+constexpr int NAR_SLOTS = 64;                           // column slots of the ring: four chunks
+constexpr int NAR_LD = 48;                              // rows of a slot, >= ldab = 2 kl + ku + 1 <= 47
+constexpr int NAR_EL = NAR_CH * NAR_LD / 64;            // elements of a chunk per lane
+static_assert(NAR_CH + NAR_MAX_KV <= 3 * NAR_CH, "the last step of a chunk must stay inside the three resident chunks");
+static_assert(2 * NAR_MAX_KL + (NAR_MAX_KV - NAR_MAX_KL) + 1 <= NAR_LD && NAR_MAX_KL + 1 <= 64, "slot height, one candidate per lane");
+
+// Where element lane + 64 k of a chunk (16 columns of ldab rows, contiguous) sits relative to the chunk's first slot, or -1
+// past the chunk's end.  Chunks start at multiples of 16 columns, so the map is the same for every chunk.
+__device__ __forceinline__ void nar_chunk_map(int (&loff)[NAR_EL], int lane, int ldab) {
+#pragma unroll
+    for (int k = 0; k < NAR_EL; ++k) {
+        const int e = lane + 64 * k;
+        loff[k] = e < NAR_CH * ldab ? e / ldab * NAR_LD + e % ldab : -1;
+    }
+}
+
+template <int RW>
+__global__ void __launch_bounds__(64)
+band_narrow_factor_kernel(BandArgs a)
+{
+    constexpr int CG = 64 / RW;
+    __shared__ c128 s_ab[NAR_SLOTS * NAR_LD];
+    __shared__ c128 s_x[NAR_SLOTS];
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const int n = a.n, kl = a.kl, ku = a.ku, kv = kl + ku, ldab = a.ldab;
+    c128* ab = a.ab + bix(a, g);
+    c128* x = a.x + (long)g * n;
+    int* ipiv = a.ipiv + (long)g * n;
+    const long end = (long)ldab * n;
+    int loff[NAR_EL];
+    nar_chunk_map(loff, lane, ldab);
+    auto S = [&](int r, int c) -> c128& { return s_ab[(c & (NAR_SLOTS - 1)) * NAR_LD + r]; };
+    // columns c0 .. c0 + 15 and their x (c0 a multiple of 16; nothing is read at or past column n)
+    auto load = [&](int c0, c128 (&v)[NAR_EL], c128& vx) {
+        const long e0 = (long)c0 * ldab + lane;
+#pragma unroll
+        for (int k = 0; k < NAR_EL; ++k) v[k] = (loff[k] >= 0 && e0 + 64 * k < end) ? ab[e0 + 64 * k] : cmake(0.0, 0.0);
+        vx = (lane < NAR_CH && c0 + lane < n) ? x[c0 + lane] : cmake(0.0, 0.0);
+    };
+    // the fill-in rows of column c, kv - c <= r < kl, start at zero (zgbtf2: columns ku + 1 .. kv - 1 before the first step,
+    // column j + kv at step j -- in both cases before a pivot row reaches the column)
+    auto enter = [&](int c0, const c128 (&v)[NAR_EL], const c128& vx) {
+        const int s0 = (c0 & (NAR_SLOTS - 1)) * NAR_LD;
+#pragma unroll
+        for (int k = 0; k < NAR_EL; ++k)
+            if (loff[k] >= 0) {
+                const int r = loff[k] % NAR_LD, c = c0 + loff[k] / NAR_LD;
+                s_ab[s0 + loff[k]] = (r < kl && r + c >= kv) ? cmake(0.0, 0.0) : v[k];
+            }
+        if (lane < NAR_CH) s_x[(c0 & (NAR_SLOTS - 1)) + lane] = vx;
+    };
+    auto leave = [&](int c0, int pv) {
+        const int s0 = (c0 & (NAR_SLOTS - 1)) * NAR_LD;
+        const long e0 = (long)c0 * ldab + lane;
+#pragma unroll
+        for (int k = 0; k < NAR_EL; ++k)
+            if (loff[k] >= 0 && e0 + 64 * k < end) ab[e0 + 64 * k] = s_ab[s0 + loff[k]];
+        if (lane < NAR_CH && c0 + lane < n) { x[c0 + lane] = s_x[(c0 & (NAR_SLOTS - 1)) + lane]; ipiv[c0 + lane] = pv; }
+    };
+    c128 pre[NAR_EL], prex;
+    load(0, pre, prex); enter(0, pre, prex);
+    load(NAR_CH, pre, prex); enter(NAR_CH, pre, prex);
+    load(2 * NAR_CH, pre, prex);
+    int ju = 0, info = 0, pv = 0;                                       // pv: ipiv of column j0 + lane of the chunk
+    for (int j0 = 0; j0 < n; j0 += NAR_CH) {
+        enter(j0 + 2 * NAR_CH, pre, prex);
+        if (j0 > 0) leave(j0 - NAR_CH, pv);
+        load(j0 + 3 * NAR_CH, pre, prex);
+        lds_barrier();
+        const int je = min(j0 + NAR_CH, n);
+        for (int j = j0; j < je; ++j) {
+            const int km = min(kl, n - 1 - j);
+            const c128 cand = lane <= km ? S(kv + lane, j) : cmake(0.0, 0.0);
+            double best = -1.0; int bidx = INT_MAX;
+            if (lane <= km) {
+                const double v = cabs1(cand);
+                if (v > best) { best = v; bidx = lane; }                 // NaN never wins (izamax)
+            }
+            wave_argmax(best, bidx);
+            int jp = __builtin_amdgcn_readfirstlane(bidx);
+            if (jp == INT_MAX) jp = 0;
+            const c128 piv = cmake(lane_bcast(cand.x, jp), lane_bcast(cand.y, jp));
+            const c128 top = cmake(lane_bcast(cand.x, 0), lane_bcast(cand.y, 0));
+            if (lane == (j & (NAR_CH - 1))) pv = j + jp + 1;            // LAPACK's 1-based row
+            if (piv.x == 0.0 && piv.y == 0.0) {
+                if (info == 0) info = j + 1;
+                continue;
+            }
+            ju = max(ju, min(j + ku + jp, n - 1));
+            if (jp != 0) {
+                const int c = j + 1 + lane;
+                if (c <= ju) {
+                    const c128 t = S(kv + jp + j - c, c);
+                    S(kv + jp + j - c, c) = S(kv + j - c, c);
+                    S(kv + j - c, c) = t;
+                }
+                if (lane == 0) {
+                    c128& xa = s_x[(j + jp) & (NAR_SLOTS - 1)];
+                    c128& xb = s_x[j & (NAR_SLOTS - 1)];
+                    const c128 t = xa; xa = xb; xb = t;
+                }
+                lds_barrier();
+            }
+            if (km > 0) {
+                const c128 r = crecip(piv);
+                const c128 xj = s_x[j & (NAR_SLOTS - 1)];
+                const int p = lane % RW, cg = lane / RW;
+                if (p < km) {
+                    const c128 own = S(kv + 1 + p, j);
+                    const c128 l = cmul(p + 1 == jp ? top : own, r);
+                    if (cg == 0) {
+                        S(kv + 1 + p, j) = l;
+                        cfms(s_x[(j + 1 + p) & (NAR_SLOTS - 1)], l, xj);
+                    }
+                    const int ncol = ju - j;
+                    for (int c = 1 + cg; c <= ncol; c += CG) cfms(S(kv + 1 + p - c, j + c), l, S(kv - c, j + c));
+                }
+            }
+            if (lane == 0 && jp != 0) S(kv, j) = piv;
+            lds_barrier();
+        }
+    }
+    leave((n - 1) / NAR_CH * NAR_CH, pv);
+    if (lane == 0) a.info[g] = info;
+}
+
+// U x = y on matrix blockIdx.x by one wave, band_back_kernel's operations in its order, walking the chunks downwards.  The
+// columns of the chunk at hand sit in LDS, the chunk below it is in flight in registers; x lives in a ring of NAR_SLOTS
+// entries (a step reaches kv entries up, so the chunk at hand and the two below it are resident, the third below in flight).
+// x[j] goes to out[perm[j]] a chunk at a time; flags |= 2 on a non-finite result.
+__global__ void __launch_bounds__(64)
+band_narrow_back_kernel(BandArgs a, c128* __restrict__ out, long ldo, const int* __restrict__ slots, const int* __restrict__ perm)
+{
+    __shared__ c128 s_u[NAR_CH * NAR_LD];
+    __shared__ c128 s_x[NAR_SLOTS];
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const int n = a.n, kv = a.kl + a.ku, ldab = a.ldab;
+    const c128* ab = a.ab + bix(a, g);
+    const c128* x = a.x + (long)g * n;
+    c128* o = out + (slots ? (long)slots[g] : (long)g) * ldo;
+    const long end = (long)ldab * n;
+    int loff[NAR_EL];
+    nar_chunk_map(loff, lane, ldab);
+    // chunk k of the band (columns 16 k ..) and chunk k - 2 of x; nothing is read below index 0 or at or past n
+    auto load = [&](int k, c128 (&v)[NAR_EL], c128& vx) {
+        const long e0 = (long)k * NAR_CH * ldab + lane;
+#pragma unroll
+        for (int q = 0; q < NAR_EL; ++q) v[q] = (k >= 0 && loff[q] >= 0 && e0 + 64 * q < end) ? ab[e0 + 64 * q] : cmake(0.0, 0.0);
+        const int i = (k - 2) * NAR_CH + lane;
+        vx = (lane < NAR_CH && i >= 0 && i < n) ? x[i] : cmake(0.0, 0.0);
+    };
+    auto enter = [&](int k, const c128 (&v)[NAR_EL], const c128& vx) {
+#pragma unroll
+        for (int q = 0; q < NAR_EL; ++q) if (loff[q] >= 0) s_u[loff[q]] = v[q];
+        if (lane < NAR_CH && k >= 2) s_x[((k - 2) * NAR_CH + lane) & (NAR_SLOTS - 1)] = vx;
+    };
+    const int K = (n - 1) / NAR_CH;
+    {
+        const int i = (K - 1) * NAR_CH + lane;                          // x of the last two chunks
+        if (lane < 2 * NAR_CH && i >= 0 && i < n) s_x[i & (NAR_SLOTS - 1)] = x[i];
+    }
+    c128 pre[NAR_EL], prex;
+    load(K, pre, prex);
+    bool bad = false;
+    for (int k = K; k >= 0; --k) {
+        enter(k, pre, prex);
+        load(k - 1, pre, prex);
+        const int jo = k * NAR_CH + lane;                               // the entry of x this lane writes out
+        const int po = (lane < NAR_CH && jo < n) ? (perm ? perm[jo] : jo) : 0;
+        c128 xo = cmake(0.0, 0.0);
+        lds_barrier();
+        for (int j = min(k * NAR_CH + NAR_CH, n) - 1; j >= k * NAR_CH; --j) {
+            const c128* u = s_u + (j & (NAR_CH - 1)) * NAR_LD + kv;     // the diagonal entry of column j
+            c128 xj = s_x[j & (NAR_SLOTS - 1)];
+            if (xj.x != 0.0 || xj.y != 0.0) {
+                xj = cdiv(xj, u[0]);
+                const int i = j - 1 - lane;
+                if (lane < kv && i >= 0) cfms(s_x[i & (NAR_SLOTS - 1)], xj, u[i - j]);
+            }
+            if (lane == (j & (NAR_CH - 1))) xo = xj;
+            lds_barrier();
+        }
+        if (lane < NAR_CH && jo < n) { o[po] = xo; bad |= !cfinite(xo); }
+    }
+    if (__any(bad) && lane == 0) atomicOr(&a.flags[g], 2);
+}
+
+void launch_narrow(const BandArgs& a, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
+    if (a.kl <= 1) hipLaunchKernelGGL((band_narrow_factor_kernel<1>), dim3(G), dim3(64), 0, st, a);
+    else if (a.kl <= 2) hipLaunchKernelGGL((band_narrow_factor_kernel<2>), dim3(G), dim3(64), 0, st, a);
+    else if (a.kl <= 4) hipLaunchKernelGGL((band_narrow_factor_kernel<4>), dim3(G), dim3(64), 0, st, a);
+    else if (a.kl <= 8) hipLaunchKernelGGL((band_narrow_factor_kernel<8>), dim3(G), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL((band_narrow_factor_kernel<16>), dim3(G), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(band_narrow_back_kernel, dim3(G), dim3(64), 0, st, a, out, ldo, slots, perm);
+}
+
 // the elements of the blocked / tiled panel of L per solve, and of the wide method's LW; lw of a workspace of G solves holds
 // the G panels, then the G LW
 size_t band_lw_small(int kl) { return (size_t)(kl + BNB) * BNB; }
@@ -987,6 +1212,13 @@ void launch_back(const BandArgs& a, int G, hipStream_t st, c128* out, long ldo, 
     case 256: hipLaunchKernelGGL((band_back_kernel<256>), dim3(G), dim3(256), 0, st, a, out, ldo, slots, perm); break;
     default: hipLaunchKernelGGL((band_back_kernel<1024>), dim3(G), dim3(1024), 0, st, a, out, ldo, slots, perm); break;
     }
+}
+
+// kinds 0 and 8: the two one-launch-per-phase schedules on the same workspace
+void launch_column(int kind, const BandArgs& a, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
+    if (kind == 8) { launch_narrow(a, G, st, out, ldo, slots, perm); return; }
+    launch_factor(a, G, st);
+    launch_back(a, G, st, out, ldo, slots, perm);
 }
 
 // algorithmic flops and bytes of G solves: 8 n kl (kl + ku) for the factorisation, 8 n (2 kl + ku) for the
@@ -1027,11 +1259,11 @@ double band_kind_bytes(int kind, int n, int kl, int ku, int G) {
 }
 
 // bytes of one solve in the workspace; the blocked and the tiled method (kind 1, 2) add their panel of L ((kl + nb) x nb,
-// nb <= BNB) and their reach, the wide method (kind 4) its LW as well
+// nb <= BNB) and their reach, the wide method (kind 4) its LW as well; the narrow method (kind 8) adds nothing
 size_t band_per_solve(int n, int kl, int ku, int kind) {
     const size_t ldab = 2 * (size_t)kl + ku + 1;
     return sizeof(c128) * (ldab * n + n) + sizeof(int) * (size_t)n
-         + (kind ? sizeof(c128) * band_lw_small(kl) + sizeof(int) : 0) + (kind == 4 ? sizeof(c128) * band_lw_outer(kl) : 0);
+         + (band_kind_blocked(kind) ? sizeof(c128) * band_lw_small(kl) + sizeof(int) : 0) + (kind == 4 ? sizeof(c128) * band_lw_outer(kl) : 0);
 }
 
 void band_ws_free(maus_ctx* c) {
@@ -1048,7 +1280,7 @@ void band_ws_free(maus_ctx* c) {
 int ensure_band_ws(maus_ctx* c, int want) {
     const int n = c->band_n, ldab = 2 * c->band_kl + c->band_ku + 1;
     const int kind = band_kind(c->band_method, c->band_kl, c->band_ku);
-    const bool blocked = kind != 0, wide = kind == 4;                   // the methods that allocate lw and ju; LW behind lw
+    const bool blocked = band_kind_blocked(kind), wide = kind == 4;     // the methods that allocate lw and ju; LW behind lw
     const size_t per = band_per_solve(n, c->band_kl, c->band_ku, kind);
     const unsigned long long key = ((unsigned long long)n << 32) | ((unsigned long long)blocked << 31) | ((unsigned long long)wide << 30) | (unsigned)ldab;
     const bool same = c->band_ab && c->band_ws_key == key;
@@ -1195,11 +1427,8 @@ int maus_band_solve(maus_ctx* c, const int* slots, int count, const double* shif
             HIPCHK(c, hipMemsetAsync(a.ab, 0, sizeof(c128) * (size_t)a.ldab * a.n * G, c->st));
             hipLaunchKernelGGL(band_build_csr_kernel, dim3((a.n + 255) / 256, G), dim3(256), 0, c->st, a, c->Acsr.ptr, c->Acsr.idx,
                                c->Acsr.val, c->band_perm, c->band_iperm, c->d_c1, c->d_r1, rhs_mode, c->X, c->ldp, c->d_slots, c->b);
-            if (kind) HIPCHK(c, launch_kind(kind, a, w, G, c->st, c->W, c->ldp, c->d_slots, c->band_perm));
-            else {
-                launch_factor(a, G, c->st);
-                launch_back(a, G, c->st, c->W, c->ldp, c->d_slots, c->band_perm);
-            }
+            if (band_kind_blocked(kind)) HIPCHK(c, launch_kind(kind, a, w, G, c->st, c->W, c->ldp, c->d_slots, c->band_perm));
+            else launch_column(kind, a, G, c->st, c->W, c->ldp, c->d_slots, c->band_perm);
         }
         if (maus_d2h(c, h_info.data(), a.info, sizeof(int) * G, c->st)) return -1;
         if (maus_d2h(c, h_flags.data(), a.flags, sizeof(int) * G, c->st)) return -1;
@@ -1214,7 +1443,8 @@ int maus_band_workspace_allocs(maus_ctx* c) { return c ? c->band_allocs : -1; }
 
 int maus_band_set_method(maus_ctx* c, int method) {
     if (!c) return -1;
-    if (method != 4 && (method < 0 || method > 2)) FAIL(c, "maus_band_set_method: method must be 0 (column), 1 (blocked), 2 (tiled) or 4 (wide)");
+    if (method != 4 && method != 8 && (method < 0 || method > 2))
+        FAIL(c, "maus_band_set_method: method must be 0 (column), 1 (blocked), 2 (tiled), 4 (wide) or 8 (narrow)");
     c->band_method = method;                                            // the workspace follows at its next use (ensure_band_ws)
     return 0;
 }
@@ -1248,7 +1478,7 @@ int maus_band_lu_host(maus_ctx* c, int count, int n, int kl, int ku, const doubl
     const size_t o_ab = take(abb * count), o_x = take(xb * count), o_o = take(xb * count), o_p = take(ib * count),
                  o_i = take(sizeof(int) * count), o_f = take(sizeof(int) * count);
     const int kind = band_kind(c->band_method, kl, ku);
-    const bool blocked = kind != 0;
+    const bool blocked = band_kind_blocked(kind);
     BlkArgs w; w.lw = nullptr; w.ju = nullptr; w.lh = kl + band_kind_nb(kind, kl, ku); w.ls = (long)w.lh * band_kind_nb(kind, kl, ku);
     const size_t o_l = take(blocked ? sizeof(c128) * (band_lw_small(kl) + (kind == 4 ? band_lw_outer(kl) : 0)) * count : 0), o_j = take(blocked ? sizeof(int) * count : 0);
     if (ensure_scratch(c, off)) return -1;
@@ -1266,10 +1496,7 @@ int maus_band_lu_host(maus_ctx* c, int count, int n, int kl, int ku, const doubl
         if (blocked) {
             hipLaunchKernelGGL(band_zero_fill_kernel, dim3(64, count), dim3(256), 0, c->st, a);
             HIPCHK(c, launch_kind(kind, a, w, count, c->st, out, n, nullptr, nullptr));
-        } else {
-            launch_factor(a, count, c->st);
-            launch_back(a, count, c->st, out, n, nullptr, nullptr);
-        }
+        } else launch_column(kind, a, count, c->st, out, n, nullptr, nullptr);
     }
     std::vector<int> h_info(count), h_flags(count);
     if (maus_stage_d2h(c, x_out, out, xb * count, c->st)) return -1;

@@ -237,7 +237,7 @@ def tridiagonal_eigenvalues(ctx, d, e):
     return np.sort(sla.eigvalsh_tridiagonal(d, e))
 
 
-SPARSE_DIRECT_MODES = ("auto", "dense", "band", "blocked", "tiled", "wide")
+SPARSE_DIRECT_MODES = ("auto", "dense", "band", "blocked", "tiled", "narrow", "wide")
 
 
 def sparse_direct_mode(mode):
@@ -377,8 +377,9 @@ class DeviceEngine:
         # above; 'blocked' is 'band' with the blocked kernels (zgbtrf's schedule, every step a launch over the whole device;
         # opt-in, 'auto' never picks it); 'tiled' is 'blocked' with the update tiled over rows as well, for bands up to
         # kl = 4096 (opt-in too); 'wide' is 'tiled' inside outer blocks of 64 columns, each applied to everything right of it
-        # in one rank-64 update on the fp64 MFMA pipe, for 64 <= kl <= 4096 (opt-in too).  MAUS_SPARSE_DIRECT sets the
-        # default.  Chosen once per bound matrix (_band).
+        # in one rank-64 update on the fp64 MFMA pipe, for 64 <= kl <= 4096 (opt-in too); 'narrow' is 'band' with the column
+        # kernel's steps run by one wave per matrix on an LDS ring of columns, for kl <= 15 and kl + ku <= 31 (opt-in too,
+        # the column kernel's bits).  MAUS_SPARSE_DIRECT sets the default.  Chosen once per bound matrix (_band).
         self.sparse_direct = sparse_direct_mode(sparse_direct)
         # GMRES of a sparse matrix: 'auto' = the post step of csrc/gmres.hip with one workgroup per candidate, as
         # ever; 'wide' = the same step with n split over workgroups of 512 entries and every sum joined in a fixed order, so
@@ -474,7 +475,7 @@ class DeviceEngine:
 
     def uses_band(self, n: int) -> bool:
         """Whether a sparse n x n matrix takes the band solve (sparse_direct; 'auto': above maus_lu_max_n())."""
-        if self.sparse_direct in ("band", "blocked", "tiled", "wide"):
+        if self.sparse_direct in ("band", "blocked", "tiled", "narrow", "wide"):
             return True
         if self.sparse_direct == "dense":
             return False
@@ -502,6 +503,8 @@ class DeviceEngine:
                 self.ctx.band_set_method(2)
             elif self.sparse_direct == "wide":
                 self.ctx.band_set_method(4)
+            elif self.sparse_direct == "narrow":
+                self.ctx.band_set_method(8)
             self.ctx.band_prepare(perm)
             self._band_ready = True
 

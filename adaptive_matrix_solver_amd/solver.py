@@ -198,17 +198,19 @@ class InverseIterateSolver:
             elif getattr(ctx, "gmres_method", None) is not None and ctx.gmres_method() != _cabi.GMRES_DEFAULT:
                 ctx.gmres_set_method(_cabi.GMRES_DEFAULT)
             # direct solves above maus_lu_max_n() (or with sparse_direct='band'): the band LU of csrc/band.hip
-            band = self.sparse_direct in ("band", "blocked", "tiled", "wide") or (self.sparse_direct == "auto" and n > ctx.lu_max_n())
+            band = self.sparse_direct in ("band", "blocked", "tiled", "narrow", "wide") or (self.sparse_direct == "auto" and n > ctx.lu_max_n())
             if band:
                 from .band import band_order
-                # the context is shared by every InverseIterateSolver: each solve states its method ('blocked', 'tiled' and
-                # 'wide' are opt-in)
+                # the context is shared by every InverseIterateSolver: each solve states its method ('blocked', 'tiled',
+                # 'wide' and 'narrow' are opt-in)
                 if self.sparse_direct == "blocked":
                     ctx.band_set_method(_cabi.BAND_BLOCKED)
                 elif self.sparse_direct == "tiled":
                     ctx.band_set_method(_cabi.BAND_TILED)
                 elif self.sparse_direct == "wide":
                     ctx.band_set_method(_cabi.BAND_WIDE)
+                elif self.sparse_direct == "narrow":
+                    ctx.band_set_method(_cabi.BAND_NARROW)
                 elif getattr(ctx, "band_method", None) is not None and ctx.band_method() != _cabi.BAND_COLUMN:
                     ctx.band_set_method(_cabi.BAND_COLUMN)
                 ctx.band_prepare(band_order(A_sp)[0])
@@ -1431,7 +1433,8 @@ class MAUS_Solver:
             raise NotImplementedError(f"sparse eigenvalue / linear problems need n <= {max_n}: n = {n}")
         perm, kl, ku = self.engine.band_shape(self.M)
         direct = getattr(self.engine, "sparse_direct", None)
-        per = band_bytes_per_solve(n, kl, ku, blocked=direct == "blocked", tiled=direct == "tiled", wide=direct == "wide")
+        per = band_bytes_per_solve(n, kl, ku, blocked=direct == "blocked", tiled=direct == "tiled", wide=direct == "wide",
+                                   narrow=direct == "narrow")
         hbm = int(ctx.device_info()["hbm_total"])
         if per * 16 > hbm:
             raise NotImplementedError(f"sparse eigenvalue / linear problem too wide for the band solve: n = {n}, kl = {kl}, "

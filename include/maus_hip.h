@@ -119,14 +119,19 @@ int maus_matrix_is_sparse(maus_ctx* ctx);
  *   schedule in blocks of 16 columns, every step a launch over (matrix, tile)), 2 the tiled method (the blocked
  *   schedule with the block row and the trailing update as launches of their own over (column tile, row tile); blocks of
  *   16, 8 or 4 columns by kl), 4 the wide method (zgbtrf's two levels: outer blocks of 64 columns factored by the
- *   tiled steps, then one rank-64 update of everything right of the block on the fp64 MFMA pipe).  There is no method 3.
+ *   tiled steps, then one rank-64 update of everything right of the block on the fp64 MFMA pipe), 8 the narrow method
+ *   (the column kernel's steps by one wave per matrix, the live columns of the band in an LDS ring that the band streams
+ *   through in chunks of 16 columns; same workspace as method 0).  There are no methods 3, 5, 6 and 7.
  *   Under method 1 a band with kl < 16 or kl > 1024 still runs the column kernel, under method 2 one with kl < 16 or
  *   kl > 4096; under method 4 a band with 64 <= kl <= 4096 runs wide, one with 16 <= kl < 64 exactly what method 2 runs
- *   and every other the column kernel.  For a band that both take, methods 1 and 2 give the same bits.  The method
- *   outlives the bound matrix; same status contract in every method.
+ *   and every other the column kernel; under method 8 a band with kl <= 15 and kl + ku <= 31 runs narrow and every other
+ *   the column kernel.  For a band that both take, methods 1 and 2 give the same bits; method 8 gives the bits of method
+ *   0 (x, ipiv, info and status) for every band.  The method outlives the bound matrix; same status contract in every
+ *   method.
  * maus_band_get_method: the current method.
- * maus_band_kernel_for: what (n, kl, ku) runs under the current method: returns 0 (column kernel), 1 (blocked), 2 (tiled)
- *   or 4 (wide); nb_out (may be NULL): the block width (wide: of the inner steps), 1 for the column kernel.
+ * maus_band_kernel_for: what (n, kl, ku) runs under the current method: returns 0 (column kernel), 1 (blocked), 2 (tiled),
+ *   4 (wide) or 8 (narrow); nb_out (may be NULL): the block width (wide: of the inner steps), 1 for the column kernel and
+ *   for narrow.
  * maus_band_outer_nb: the width of the outer block (64) where (n, kl, ku) runs wide under the current method, 0 elsewhere. */
 int maus_sparse_max_n(void);
 int maus_band_prepare(maus_ctx* ctx, const int32_t* perm, int n, int* kl_out, int* ku_out);
@@ -420,7 +425,8 @@ int maus_timer_start(maus_ctx* ctx);
 int maus_timer_stop(maus_ctx* ctx, float* ms_out);
 /* Per-kernel-class accounting (event pairs around each launch of the class while enabled).
  * classes: 0 zgemm (LU trailing update with K>=256 / A@X), 1 lu_panel, 2 trsm, 3 (unused since round 2: row-swap sweeps), 4 build_H, 5 backsolve,
- * 6 vector ops, 7..10 zgemm inside the LU recursion with K = 128 / 64 / 32 / 16, 11 CSR products, 12 band solves,
+ * 6 vector ops, 7..10 zgemm inside the LU recursion with K = 128 / 64 / 32 / 16, 11 CSR products, 12 band solves (the
+ * column kernel and the narrow method: same flops and bytes),
  * 13 lanczos (reorthogonalisation, restart, match of the sparse Hermitian shortcut), 14 band solves by the blocked method
  * (maus_band_set_method; bytes: the band moved once per block step over the full reach kl + ku, not an MFMA class),
  * 15 band solves by the tiled method (bytes: as 14 plus L21 once per column tile of the trailing update)

@@ -29,6 +29,16 @@ of two timed calls after one warm-up call), tiled ms / wide ms, and the share of
 executed (4M) flops reach.
 
     python tools/band_rates.py --table wide [--out profiles/band_wide_rates.txt]
+
+With --table narrow: the narrow method (maus_band_set_method(ctx, 8)) against the column kernel, which runs these bands in
+every other mode, in one process on the same systems -> profiles/band_narrow_rates.txt.  Tridiagonal and pentadiagonal
+operators at n = 65536, 262144 and 2^20 and kl = ku = 15 at n = 65536 and 262144 (complex normal values on every diagonal, the
+identity ordering: the factorisation pivots and fills the band), each alone and in a batch of 64; per row the ms per solve of
+both (the better of two timed calls after one warm-up call), the microseconds per column, and column ms / narrow ms against
+the 1.25x bar of an opt-in schedule.  Then MAUS_Solver linear loop bodies on a tridiagonal operator at n = 262144, P = 64 on
+the direct path with sparse_direct 'band' and 'narrow'.
+
+    python tools/band_rates.py --table narrow [--out profiles/band_narrow_rates.txt]
 """
 import argparse
 import os
@@ -263,12 +273,98 @@ def main_wide(args):
         f.write("\n".join(lines) + "\n")
 
 
+def diagonals(n, k, seed=0):
+    """Offsets -k .. k, complex normal values: kl = ku = k in the identity ordering, and partial pivoting fills the band."""
+    rng = np.random.default_rng(seed)
+    offs = list(range(-k, k + 1))
+    return sp.diags([rng.standard_normal(n - abs(o)) + 1j * rng.standard_normal(n - abs(o)) for o in offs], offs, format="csr")
+
+
+def loop_rate_narrow(direct, n=262144, P=64, bodies=3):
+    """Candidate-steps per second and band-class ms per body of MAUS_Solver linear loop bodies on a tridiagonal operator
+    (diagonal near 4 + i, off-diagonals of modulus <= 1) with every solve a band solve."""
+    import random
+    from adaptive_matrix_solver_amd.solver import MAUS_Solver, ProblemType, SolutionCandidate
+    rng = np.random.default_rng(8)
+    off = [rng.uniform(0.2, 1.0, n - 1) * np.exp(2j * np.pi * rng.random(n - 1)) for _ in range(2)]
+    A = sp.diags([off[0], 4.0 + 1j + 0.1 * rng.standard_normal(n), off[1]], [-1, 0, 1], format="csr")
+    b = rng.standard_normal(n) + 1j * rng.standard_normal(n)
+    np.random.seed(3); random.seed(3); SolutionCandidate._candidate_id_counter = 0
+    diag = {"is_sparse_init": True, "condition_number": 1e7, "is_singular": False, "is_hermitian": False,
+            "is_complex_symmetric": False}
+    s = MAUS_Solver(A, ProblemType.SOLVE_LINEAR_SYSTEM, b_vector=b, initial_num_candidates=P, quiet=True, sparse_mode="device",
+                    gmres_compat="scipy-legacy", sparse_direct=direct, diag_info=diag)
+    s.loop_body(1)
+    ctx = s.engine.ctx
+    ctx.profile_enable(False)
+    ctx.profile_enable(True)
+    steps, t0 = 0, time.perf_counter()
+    for it in range(bodies):
+        steps += len(s.candidates)
+        s.loop_body(it + 2)
+    ctx.sync()
+    wall = time.perf_counter() - t0
+    pr = ctx.profile_read()
+    ctx.profile_enable(False)
+    return steps / wall, pr["band"]["ms"] / bodies
+
+
+def main_narrow(args):
+    ctx = _cabi.Context(0)
+    info = ctx.device_info()
+    head = (f"{'n':>8} {'kl':>3} {'ku':>3} {'batch':>5} {'column ms':>10} {'narrow ms':>10} {'column us/col':>13} {'narrow us/col':>13} "
+            f"{'column/narrow':>13} {'1.25x bar':>9}")
+    lines = [f"# band solves, csrc/band.hip, the narrow method against the column kernel in one process -- {info['name']}, {info['cus']} CUs",
+             "# ms per solve from the 'band' profile class (HIP events around build + factor + solve of one batch), the better of two",
+             "# timed calls after one warm-up call; us/col = ms per solve / n, for a batch the batch's time / (batch n); complex normal",
+             "# values on every diagonal, identity ordering (the factorisation pivots and fills the band); bar: the 1.25x of an opt-in schedule",
+             head]
+
+    def flush():
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+    shapes = [(k, n) for k in (1, 2) for n in (65536, 262144, 1 << 20)] + [(15, n) for n in (65536, 262144)]
+    for k, n in shapes:
+        if args.only and f"{k}:{n}" not in args.only.split(","):
+            continue
+        A = diagonals(n, k, k + n)
+        kl, ku = bind(ctx, A, 64, identity=True)
+        assert (kl, ku) == (k, k)
+        for P in (1, 64):
+            ms = {}
+            for method, name in ((_cabi.BAND_COLUMN, "column"), (_cabi.BAND_NARROW, "narrow")):
+                ctx.band_set_method(method)
+                assert ctx.band_kernel_for(n, kl, ku) == (method, 1)
+                pr, _ = timed_band(ctx, P, "band")
+                ms[name] = pr["ms"] / P
+            up = ms["column"] / ms["narrow"]
+            lines.append(f"{n:>8} {kl:>3} {ku:>3} {P:>5} {ms['column']:>10.3f} {ms['narrow']:>10.3f} {ms['column'] * 1e3 / n:>13.4f} "
+                         f"{ms['narrow'] * 1e3 / n:>13.4f} {up:>12.2f}x {'met' if up >= 1.25 else 'MISSED':>9}")
+            print(lines[-1], flush=True)
+            flush()
+    ctx.close()                                                # its workspaces would crowd out the solver's own context
+    if not args.only or "loop" in args.only.split(","):
+        lines += ["", "# MAUS_Solver linear loop bodies on a tridiagonal operator at n = 262144, P = 64, direct path (gmres_compat='scipy-legacy':",
+                  "# every solve a band solve): 1 untimed + 3 timed bodies; candidate-steps = candidates at the start of each timed body"]
+        rates = {}
+        for direct in ("band", "narrow"):
+            rates[direct], band_ms = loop_rate_narrow(direct)
+            lines.append(f"sparse_direct={direct:<7} {rates[direct]:9.1f} candidate-steps/s   (band class {band_ms:9.1f} ms per body)")
+            print(lines[-1], flush=True)
+        up = rates["narrow"] / rates["band"]
+        lines.append(f"narrow / band: {up:.2f}x candidate-steps/s ({'meets' if up >= 1.25 else 'MISSES'} the 1.25x bar)")
+        print(lines[-1], flush=True)
+    flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--table", choices=("blocked", "tiled", "wide"), default="blocked")
+    ap.add_argument("--table", choices=("blocked", "tiled", "wide", "narrow"), default="blocked")
     ap.add_argument("--out", default=None)
     ap.add_argument("--sizes", default="128:1,128:64,256:1,256:64,512:1,512:8")
-    ap.add_argument("--only", default=None, help="--table tiled / wide: the wide-band rows whose label contains one of these, nothing else")
+    ap.add_argument("--only", default=None, help="--table tiled / wide: the wide-band rows whose label contains one of these, nothing else; "
+                         "--table narrow: the rows k:n (half-bandwidth:size) and 'loop' listed here, nothing else")
     ap.add_argument("--no-column", action="store_true", help="--table tiled: leave the column kernel's minutes out")
     args = ap.parse_args()
     args.out = args.out or f"profiles/band_{args.table}_rates.txt"
@@ -276,6 +372,8 @@ def main():
         return main_tiled(args)
     if args.table == "wide":
         return main_wide(args)
+    if args.table == "narrow":
+        return main_narrow(args)
     ctx = _cabi.Context(0)
     info = ctx.device_info()
     lines = [f"# band solves, csrc/band.hip, column kernel and blocked method in one process -- {info['name']}, {info['cus']} CUs",
