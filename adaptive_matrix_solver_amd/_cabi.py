@@ -445,9 +445,9 @@ class Context:
         n = d.shape[0]
         if e.shape[0] != max(n - 1, 0):
             raise ValueError("tridiagonal matrix: e must have n - 1 entries")
-        t = max(float(np.max(np.abs(d))) if n else 0.0, float(np.max(np.abs(e))) if n > 1 else 0.0)
-        if not np.isfinite(t):
+        if not (np.isfinite(d).all() and np.isfinite(e).all()):    # (max(t, nan) is t: a NaN in e alone would pass a test of t)
             raise ValueError("tridiagonal matrix is not finite")
+        t = max(float(np.max(np.abs(d))) if n else 0.0, float(np.max(np.abs(e))) if n > 1 else 0.0)
         s = 2.0 ** int(np.floor(np.log2(t))) if t > 0.0 else 1.0           # a power of two: the scaling is exact
         return n, d / s, np.ascontiguousarray(e / s if n > 1 else np.zeros(1)), s
 

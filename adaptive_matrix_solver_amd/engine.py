@@ -914,17 +914,24 @@ class DeviceEngine:
         # say the spectrum is well separated and the residuals are at rounding level -- a vector is then off by
         # eps ||T|| / gap <= ~1e-9 -- and by LAPACK dstemr on the host (the kernel zheevr uses; 7.4 of the decomposition's
         # 8.5 s at n = 8192) for clustered spectra or on MAUS_EIGH_TRIDIAG=host.
+        # A spectrum rejected for its gap alone keeps the bisection's eigenvalues and takes only the vectors from dstemr: the
+        # gap says nothing against the eigenvalues, which stay within one eps ||T|| of the true ones however clustered they
+        # are, while dstemr's need 8 eps ||T|| on a Wilkinson matrix -- and the caller gets the same eigenvalues
+        # under either verdict.  Both lists are ascending, so column k of Z still goes with evals[k].
         self.tridiag_solver = "host"
+        kept = None
         if os.environ.get("MAUS_EIGH_TRIDIAG", "auto") != "host" and hasattr(self.ctx, "herm_tridiag_eig") and np.isfinite(d).all() and np.isfinite(e).all():
             evals, (gap, resid, tnorm) = self.ctx.herm_tridiag_eig(d, e)
             self.tridiag_diag = (gap, resid, tnorm)
-            if np.isfinite(evals).all() and gap >= TRIDIAG_MIN_GAP and resid <= TRIDIAG_MAX_RESID:
-                self.ctx.herm_backtransform(None)
-                self.tridiag_solver = "device"
-                return evals
+            if np.isfinite(evals).all() and resid <= TRIDIAG_MAX_RESID:
+                if gap >= TRIDIAG_MIN_GAP:
+                    self.ctx.herm_backtransform(None)
+                    self.tridiag_solver = "device"
+                    return evals
+                kept = evals
         evals, Z = sla.eigh_tridiagonal(d, e)                      # LAPACK dstemr
         self.ctx.herm_backtransform(Z)
-        return evals
+        return evals if kept is None else kept
 
     def _eigh_once(self, A):
         """One decomposition per matrix version instead of one per candidate; the same LAPACK call as the
