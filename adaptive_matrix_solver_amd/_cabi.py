@@ -10,6 +10,8 @@ import os
 
 import numpy as np
 
+from .band import DIRECT_METHOD
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmaus_hip.so")
 
@@ -23,7 +25,7 @@ SYMBOLS = [
     "maus_profile_enable", "maus_profile_read", "maus_sync", "maus_mt19937_jump",
     "maus_lanczos_begin", "maus_lanczos_inject", "maus_lanczos_extend", "maus_lanczos_restart", "maus_lanczos_finish", "maus_herm_match_rows", "maus_get_ritz_rows",
     "maus_sparse_max_n", "maus_band_prepare", "maus_band_reserve", "maus_band_solve", "maus_band_lu_host", "maus_band_workspace_allocs",
-    "maus_band_set_method", "maus_band_get_method", "maus_band_kernel_for", "maus_band_outer_nb",
+    "maus_band_set_method", "maus_band_get_method", "maus_band_kernel_for", "maus_band_outer_nb", "maus_band_plan",
     "maus_gmres_set_method", "maus_gmres_get_method", "maus_gmres_kernel_for",
     "maus_device_count", "maus_comm_unique_id", "maus_comm_init", "maus_comm_destroy", "maus_comm_info",
     "maus_comm_allgather_records", "maus_comm_allgather_rows", "maus_comm_bcast", "maus_comm_bcast_eigvecs", "maus_comm_set_matrix", "maus_comm_stats",
@@ -36,9 +38,8 @@ KIND_EIG, KIND_LINEAR, KIND_SVD = 1, 2, 3
 PERT_NONE, PERT_UNIFORM, PERT_MT19937 = 0, 1, 2
 KC_NAMES = ["zgemm", "lu_panel", "trsm", "laswp", "build_h", "backsolve", "vector",
             "zgemm_k128", "zgemm_k64", "zgemm_k32", "zgemm_k16", "spmm", "band", "lanczos", "band_blocked", "band_tiled", "band_wide", "gmres_wide"]
-BAND_COLUMN, BAND_BLOCKED, BAND_TILED = 0, 1, 2      # maus_band_set_method
-BAND_WIDE = 4                                        # (there is no method 3)
-BAND_NARROW = 8                                      # (nor 5, 6, 7)
+BAND_COLUMN, BAND_BLOCKED, BAND_TILED, BAND_WIDE, BAND_NARROW = (      # maus_band_set_method: 0, 1, 2, 4, 8 (no 3, 5, 6, 7)
+    DIRECT_METHOD[m] for m in ("band", "blocked", "tiled", "wide", "narrow"))
 GMRES_DEFAULT, GMRES_WIDE = 0, 1                     # maus_gmres_set_method
 SPMM_SCHEDULES = {0: None, 1: "rows", 2: "wave"}     # maus_matrix_is_sparse: dense / lane per row / wave per row
 
@@ -142,6 +143,7 @@ def load_library():
         "maus_gmres_get_method": ([vp], C.c_int),
         "maus_gmres_kernel_for": ([vp, C.c_int, C.c_int], C.c_int),
         "maus_band_outer_nb": ([vp, C.c_int, C.c_int, C.c_int], C.c_int),
+        "maus_band_plan": ([C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p, i32p, C.POINTER(C.c_int64)], C.c_int),
         "maus_device_count": ([], C.c_int),
         "maus_comm_unique_id": ([C.c_char_p], C.c_int),
         "maus_comm_init": ([vp, C.c_int, C.c_int, C.c_char_p], C.c_int),
@@ -764,6 +766,15 @@ class Context:
 def device_count() -> int:
     """HIP devices visible to this process (0 on a box without a GPU)."""
     return int(load_library().maus_device_count())
+
+
+def band_plan(method, n, kl, ku):
+    """(kind, nb, outer nb, workspace bytes per solve) of an (n, kl, ku) band under `method` (maus_band_plan): needs neither
+    a context nor a device."""
+    kind, nb, nbo, per = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    if load_library().maus_band_plan(int(method), int(n), int(kl), int(ku), C.byref(kind), C.byref(nb), C.byref(nbo), C.byref(per)) != 0:
+        raise MausHipError(f"maus_band_plan: bad method or sizes ({method}, {n}, {kl}, {ku})")
+    return int(kind.value), int(nb.value), int(nbo.value), int(per.value)
 
 
 def comm_unique_id() -> bytes:

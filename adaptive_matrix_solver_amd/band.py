@@ -42,13 +42,18 @@ def band_order(A) -> tuple[np.ndarray, int, int]:
     return rcm, kl_r, ku_r
 
 
-BLOCKED_NB = 16                 # block width of the blocked method (8 where kl + 16 > 1024), csrc/band.hip
+# The rule of csrc/band.hip's band_plan, restated for sizing before a context exists; tests/test_band_plan_host.py compares the
+# two over every boundary (maus_band_plan needs no device).
+# sparse_direct -> maus_band_set_method, in the order the keyword lists its modes
+DIRECT_METHOD = {"band": 0, "blocked": 1, "tiled": 2, "narrow": 8, "wide": 4}
+
+BLOCKED_NB = 16                 # block width of the blocked method (8 where kl + 16 > 1024)
 BLOCKED_MIN_KL = 16             # narrower bands run the column kernel under sparse_direct='blocked' too ...
 BLOCKED_MAX_KL = 1024           # ... and so do bands too tall for its one-workgroup panel
 
 
 def runs_blocked(kl: int, ku: int) -> bool:
-    """Whether the blocked method takes a (kl, ku) band when it is selected (band_runs_blocked in csrc/band.hip)."""
+    """Whether the blocked method takes a (kl, ku) band when it is selected (pinned by tests/test_band_plan_host.py)."""
     return BLOCKED_MIN_KL <= kl <= BLOCKED_MAX_KL
 
 
@@ -57,17 +62,17 @@ TILED_MAX_KL = 4096             # ... which is where its register panel ends (ab
 
 
 def runs_tiled(kl: int, ku: int) -> bool:
-    """Whether the tiled method takes a (kl, ku) band when it is selected (band_runs_tiled in csrc/band.hip)."""
+    """Whether the tiled method takes a (kl, ku) band when it is selected (pinned by tests/test_band_plan_host.py)."""
     return TILED_MIN_KL <= kl <= TILED_MAX_KL
 
 
 WIDE_MIN_KL = 64                # the wide method's range under sparse_direct='wide': below it the outer block is wider than
 WIDE_MAX_KL = 4096              # the band's reach (the tiled method runs from kl = 16), above it the inner panel ends
-WIDE_NBO = 64                   # columns of the outer block, csrc/band.hip
+WIDE_NBO = 64                   # columns of the outer block
 
 
 def runs_wide(kl: int, ku: int) -> bool:
-    """Whether the wide method takes a (kl, ku) band when it is selected (band_runs_wide in csrc/band.hip)."""
+    """Whether the wide method takes a (kl, ku) band when it is selected (pinned by tests/test_band_plan_host.py)."""
     return WIDE_MIN_KL <= kl <= WIDE_MAX_KL
 
 
@@ -76,16 +81,33 @@ NARROW_MAX_KV = 31              # (kl + ku + 1 of them) fit its LDS ring; the co
 
 
 def runs_narrow(kl: int, ku: int) -> bool:
-    """Whether the narrow method takes a (kl, ku) band when it is selected (band_runs_narrow in csrc/band.hip)."""
+    """Whether the narrow method takes a (kl, ku) band when it is selected (pinned by tests/test_band_plan_host.py)."""
     return 0 <= kl <= NARROW_MAX_KL and kl + ku <= NARROW_MAX_KV
 
 
+def kernel_for(method: int, kl: int, ku: int) -> tuple[int, int]:
+    """(kind, nb) that a (kl, ku) band runs under `method`, as maus_band_kernel_for: kind one of DIRECT_METHOD's values (0
+    where the method does not take the band; under 4 the tiled kernels for 16 <= kl < 64), nb the (inner) block width."""
+    nb = BLOCKED_NB if kl + BLOCKED_NB <= 1024 else 8                   # while two rows per thread of the panel hold kl + nb
+    if method == 1 and runs_blocked(kl, ku):
+        return 1, nb
+    if method in (2, 4) and runs_tiled(kl, ku):
+        if kl > BLOCKED_MAX_KL:                                          # the widest block whose panel stays in registers
+            nb = 16 if kl + 16 <= 1536 else (8 if kl + 8 <= 3072 else 4)
+        return (4 if method == 4 and runs_wide(kl, ku) else 2), nb
+    if method == 8 and runs_narrow(kl, ku):
+        return 8, 1
+    return 0, 1
+
+
 def band_bytes_per_solve(n: int, kl: int, ku: int, blocked: bool = False, tiled: bool = False, wide: bool = False,
-                         narrow: bool = False) -> int:
-    """Device memory of one band solve: the band storage, the right-hand side and the pivots (csrc/band.hip); with
-    `blocked` (`tiled`), and a band the blocked (tiled) method takes, its panel of L and its reach as well; with `wide` the
-    tiled method's where that runs, and the L of the outer block ((kl + 64) x 64) where the wide method does.  `narrow` adds
-    nothing: the narrow method works in the column kernel's workspace."""
+                         narrow: bool = False, method: int | None = None) -> int:
+    """Device memory of one band solve: the band storage, the right-hand side and the pivots; with `blocked` (`tiled`), and
+    a band the blocked (tiled) method takes, its panel of L and its reach as well; with `wide` the tiled method's where that
+    runs, and the L of the outer block ((kl + 64) x 64) where the wide method does.  `narrow` adds nothing: the narrow method
+    works in the column kernel's workspace.  `method` (a value of DIRECT_METHOD) stands for the flag of that method."""
+    if method is not None:
+        blocked, tiled, wide = method == 1, method == 2, method == 4
     per = 16 * ((2 * kl + ku + 1) * n + n) + 4 * n
     if (blocked and runs_blocked(kl, ku)) or ((tiled or wide) and runs_tiled(kl, ku)):
         per += 16 * (kl + BLOCKED_NB) * BLOCKED_NB + 4

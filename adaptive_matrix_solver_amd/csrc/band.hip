@@ -221,8 +221,8 @@ constexpr int BLK_MAX_KL = 1024;                        // ... and so do bands t
 // ls = lh * nb); ju: reach so far
 struct BlkArgs { c128* lw; int* ju; int lh; long ls; };
 
-bool band_runs_blocked(int method, int kl, int ku) { (void)ku; return method == 1 && kl >= BLK_MIN_KL && kl <= BLK_MAX_KL; }
-int band_nb(int kl, int ku) { (void)ku; return kl + BNB <= 1024 ? BNB : BNB_TALL; }
+bool band_runs_blocked(int kl) { return kl >= BLK_MIN_KL && kl <= BLK_MAX_KL; }
+int band_nb(int kl) { return kl + BNB <= 1024 ? BNB : BNB_TALL; }
 
 // the fill-in rows of the band storage start at zero (zgbtf2 clears them column by column as it goes)
 __global__ void __launch_bounds__(256)
@@ -452,43 +452,51 @@ band_back_blk_kernel(BandArgs a, c128* __restrict__ out, long ldo, const int* __
     if (bad) atomicOr(&a.flags[g], 2);
 }
 
-// The whole blocked solve of G matrices on `st`: n / BNB block steps of two launches each, then the back substitution.  The
-// launch queue is bounded as maus_herm_tridiag bounds it: an event every 64 block steps, wait for the one before last.
+// The launch queue of a solve of many block steps is bounded as maus_herm_tridiag bounds it: an event every 64 steps, wait
+// for the one before last.
+struct StepThrottle {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipError_t err = hipSuccess;                                        // of creating the events
+    StepThrottle() { for (auto& e : ev) if (err == hipSuccess) err = hipEventCreateWithFlags(&e, hipEventDisableTiming); }
+    ~StepThrottle() { for (auto& e : ev) if (e) (void)hipEventDestroy(e); }
+    StepThrottle(const StepThrottle&) = delete;
+    StepThrottle& operator=(const StepThrottle&) = delete;
+    hipError_t before_step(int step) { return step % 64 == 0 && step >= 128 ? hipEventSynchronize(ev[(step / 64) & 1]) : hipSuccess; }
+    hipError_t after_step(int step, hipStream_t st) {
+        if (step % 64 != 63) return hipSuccess;
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? hipEventRecord(ev[(step / 64) & 1], st) : e;
+    }
+};
+
+// the back substitution of the blocked, tiled and wide methods
+hipError_t launch_back_blk(const BandArgs& a, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
+    if (a.kl + a.ku <= 256) hipLaunchKernelGGL((band_back_blk_kernel<256>), dim3(G), dim3(256), 0, st, a, out, ldo, slots, perm);
+    else hipLaunchKernelGGL((band_back_blk_kernel<1024>), dim3(G), dim3(1024), 0, st, a, out, ldo, slots, perm);
+    return hipGetLastError();
+}
+
+// The whole blocked solve of G matrices on `st`: n / NB block steps of two launches each, then the back substitution.
 template <int NB>
 hipError_t launch_blocked_nb(const BandArgs& a, const BlkArgs& w, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)band_update_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        attr_set = true;
-    }
     const int kv = a.kl + a.ku, H = a.kl + NB, ntile = (kv + BTC - 1) / BTC;
     const size_t lds = sizeof(c128) * (size_t)w.lh * BTC;
-    hipError_t err = hipMemsetAsync(w.ju, 0, sizeof(int) * G, st);
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    for (auto& e : ev) if (err == hipSuccess) err = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+    // every call, for the device the call runs on: cheap beside the solve, and a refusal ends the solve here
+    hipError_t err = hipFuncSetAttribute((const void*)band_update_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    if (err == hipSuccess) err = hipMemsetAsync(w.ju, 0, sizeof(int) * G, st);
+    StepThrottle th;
+    if (err == hipSuccess) err = th.err;
     int step = 0;
     for (int j0 = 0; j0 < a.n && err == hipSuccess; j0 += NB, ++step) {
-        if (step % 64 == 0 && step >= 128) err = hipEventSynchronize(ev[(step / 64) & 1]);
-        if (err != hipSuccess) break;
+        if ((err = th.before_step(step)) != hipSuccess) break;
         if (H <= 256) hipLaunchKernelGGL((band_panel_kernel<256, 1, NB>), dim3(G), dim3(256), 0, st, a, w, j0);
         else if (H <= 512) hipLaunchKernelGGL((band_panel_kernel<512, 1, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
         else if (H <= 1024) hipLaunchKernelGGL((band_panel_kernel<512, 2, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
         else hipLaunchKernelGGL((band_panel_kernel<512, 3, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
         hipLaunchKernelGGL(band_update_kernel<NB>, dim3(ntile + 1, G), dim3(256), lds, st, a, w, j0, ntile);
-        if (step % 64 == 63) { err = hipGetLastError(); if (err == hipSuccess) err = hipEventRecord(ev[(step / 64) & 1], st); }
+        err = th.after_step(step, st);
     }
-    if (err == hipSuccess) {
-        if (kv <= 256) hipLaunchKernelGGL((band_back_blk_kernel<256>), dim3(G), dim3(256), 0, st, a, out, ldo, slots, perm);
-        else hipLaunchKernelGGL((band_back_blk_kernel<1024>), dim3(G), dim3(1024), 0, st, a, out, ldo, slots, perm);
-        err = hipGetLastError();
-    }
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    return err;
-}
-
-hipError_t launch_blocked(const BandArgs& a, const BlkArgs& w, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
-    return band_nb(a.kl, a.ku) == BNB ? launch_blocked_nb<BNB>(a, w, G, st, out, ldo, slots, perm)
-                                      : launch_blocked_nb<BNB_TALL>(a, w, G, st, out, ldo, slots, perm);
+    return err == hipSuccess ? launch_back_blk(a, G, st, out, ldo, slots, perm) : err;
 }
 
 // ---- the tiled method (maus_band_set_method(ctx, 2)) --------------------------------------------------------
@@ -510,11 +518,11 @@ constexpr int TNB_TALL = 4;                             // ... and 4 up to TIL_M
 constexpr int TCT = 16;                                 // columns per tile of the trailing update
 constexpr int TRT = 256;                                // rows per tile of the trailing update: one per thread
 
-bool band_runs_tiled(int method, int kl, int ku) { (void)ku; return method == 2 && kl >= TIL_MIN_KL && kl <= TIL_MAX_KL; }
+bool band_runs_tiled(int kl) { return kl >= TIL_MIN_KL && kl <= TIL_MAX_KL; }
 // up to BLK_MAX_KL the blocked method's width, so that both methods do the same arithmetic there; above it the widest block
 // whose panel stays in registers (measured: DESIGN §11)
-int band_tiled_nb(int kl, int ku) {
-    if (kl <= BLK_MAX_KL) return band_nb(kl, ku);
+int band_tiled_nb(int kl) {
+    if (kl <= BLK_MAX_KL) return band_nb(kl);
     return kl + BNB <= TIL_NB16_H ? BNB : (kl + TNB_MID <= 3072 ? TNB_MID : TNB_TALL);
 }
 
@@ -527,24 +535,51 @@ static_assert(NBO == 64 || NBO == 32, "the outer block row maps the top rows of 
 constexpr int WID_MIN_KL = 64;                          // below it the outer block is wider than the band's reach: tiled runs
 constexpr int WID_MAX_KL = TIL_MAX_KL;
 
-bool band_runs_wide(int method, int kl, int ku) { (void)ku; return method == 4 && kl >= WID_MIN_KL && kl <= WID_MAX_KL; }
+bool band_runs_wide(int kl) { return kl >= WID_MIN_KL && kl <= WID_MAX_KL; }
 
 // the narrow method (maus_band_set_method(ctx, 8), further down): the widest band whose live columns fit its LDS ring
 constexpr int NAR_MAX_KL = 15;
 constexpr int NAR_MAX_KV = 31;
 
-bool band_runs_narrow(int method, int kl, int ku) { return method == 8 && kl <= NAR_MAX_KL && kl + ku <= NAR_MAX_KV; }
+bool band_runs_narrow(int kl, int ku) { return kl <= NAR_MAX_KL && kl + ku <= NAR_MAX_KV; }
 
-// 0: the column kernel, 1: blocked, 2: tiled, 4: wide, 8: narrow -- what a (kl, ku) band runs under `method`; the (inner)
-// block width with it.  Under method 4 a band with TIL_MIN_KL <= kl < WID_MIN_KL runs exactly what the tiled method runs.
-// Kinds 1, 2 and 4 keep a panel of L and a reach per solve (band_kind_blocked); kinds 0 and 8 share one workspace.
-bool band_kind_blocked(int kind) { return kind == 1 || kind == 2 || kind == 4; }
-int band_kind(int method, int kl, int ku) {
-    if (method == 8) return band_runs_narrow(8, kl, ku) ? 8 : 0;
-    if (method == 4) return band_runs_wide(4, kl, ku) ? 4 : (kl < WID_MIN_KL && band_runs_tiled(2, kl, ku) ? 2 : 0);
-    return band_runs_blocked(method, kl, ku) ? 1 : (band_runs_tiled(method, kl, ku) ? 2 : 0);
+// What a (kl, ku) band runs under `method`; the values are those of maus_band_set_method and maus_band_kernel_for.
+enum BandKind : int { BK_COLUMN = 0, BK_BLOCKED = 1, BK_TILED = 2, BK_WIDE = 4, BK_NARROW = 8 };
+
+bool band_method_ok(int m) { return m == BK_COLUMN || m == BK_BLOCKED || m == BK_TILED || m == BK_WIDE || m == BK_NARROW; }
+
+// Everything the host side derives from (method, kl, ku): the only reader of the ranges above and of the method.
+struct BandPlan {
+    BandKind kind = BK_COLUMN;
+    int nb = 1;                                         // (inner) block width; 1 for the column kernel and for narrow
+    int nbo = 0;                                        // outer block width: NBO where the band runs wide
+    bool panel = false;                                 // lw and ju exist: blocked, tiled and wide; column and narrow share one workspace
+    size_t lw_small = 0, lw_outer = 0, lw = 0;          // elements of lw per solve: the (kl + BNB) x BNB panel of L, the wide
+                                                        // method's LW, their sum; lw of G solves holds the G panels, then the G LW
+    int cls = KC_BAND;                                  // ProfScope class
+};
+
+// Under method 4 a band with TIL_MIN_KL <= kl < WID_MIN_KL runs exactly what the tiled method runs.
+BandPlan band_plan(int method, int kl, int ku) {
+    BandPlan p;
+    switch (method) {
+    case BK_BLOCKED: if (band_runs_blocked(kl)) p.kind = BK_BLOCKED; break;
+    case BK_TILED: if (band_runs_tiled(kl)) p.kind = BK_TILED; break;
+    case BK_WIDE: if (band_runs_wide(kl)) p.kind = BK_WIDE; else if (kl < WID_MIN_KL && band_runs_tiled(kl)) p.kind = BK_TILED; break;
+    case BK_NARROW: if (band_runs_narrow(kl, ku)) p.kind = BK_NARROW; break;
+    default: break;
+    }
+    switch (p.kind) {
+    case BK_BLOCKED: p.nb = band_nb(kl); p.cls = KC_BAND_BLOCKED; break;
+    case BK_TILED: p.nb = band_tiled_nb(kl); p.cls = KC_BAND_TILED; break;
+    case BK_WIDE: p.nb = band_tiled_nb(kl); p.cls = KC_BAND_WIDE; p.nbo = NBO; p.lw_outer = (size_t)(kl + NBO) * NBO; break;
+    default: return p;
+    }
+    p.panel = true;
+    p.lw_small = (size_t)(kl + BNB) * BNB;
+    p.lw = p.lw_small + p.lw_outer;
+    return p;
 }
-int band_kind_nb(int kind, int kl, int ku) { return kind == 1 ? band_nb(kl, ku) : (kind == 2 || kind == 4 ? band_tiled_nb(kl, ku) : 1); }
 
 // Block row of block step j0: workgroup (t, g) takes the 256 / NB columns from c0 right of the panel of matrix g, workgroup
 // (ntile, g) its right-hand side.  A column keeps 2 NB elements in LDS: slots 0 .. NB - 1 its rows j0 .. j0 + NB - 1, slot
@@ -676,44 +711,6 @@ void launch_tiled_panel(const BandArgs& a, const BlkArgs& w, int G, hipStream_t 
     } else {                                                            // 3065 <= kl <= 4096
         if (H <= 4096) hipLaunchKernelGGL((band_panel_kernel<512, 8, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
         else hipLaunchKernelGGL((band_panel_kernel<512, 9, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
-    }
-}
-
-// The whole tiled solve of G matrices on `st`: three launches per block step (the trailing update only where rows lie below
-// the block), then the blocked back substitution; the launch queue is bounded as in launch_blocked_nb.
-template <int NB>
-hipError_t launch_tiled_nb(const BandArgs& a, const BlkArgs& w, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
-    const int kv = a.kl + a.ku, RC = 256 / NB, ntile = (kv + RC - 1) / RC, nct = (kv + TCT - 1) / TCT;
-    hipError_t err = hipMemsetAsync(w.ju, 0, sizeof(int) * G, st);
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    for (auto& e : ev) if (err == hipSuccess) err = hipEventCreateWithFlags(&e, hipEventDisableTiming);
-    int step = 0;
-    for (int j0 = 0; j0 < a.n && err == hipSuccess; j0 += NB, ++step) {
-        if (step % 64 == 0 && step >= 128) err = hipEventSynchronize(ev[(step / 64) & 1]);
-        if (err != hipSuccess) break;
-        launch_tiled_panel<NB>(a, w, G, st, j0);
-        hipLaunchKernelGGL(band_row_kernel<NB>, dim3(ntile + 1, G), dim3(256), 0, st, a, w, j0, ntile, INT_MAX);
-        const int below = std::min(a.kl + NB, a.n - j0) - NB;           // rows of L21; none in a last, short block
-        if (below > 0) {
-            const int nrt = (below + TRT - 1) / TRT;
-            hipLaunchKernelGGL(band_trail_kernel<NB>, dim3((nct + 1) * nrt, G), dim3(TRT), 0, st, a, w, j0, nct, nrt, INT_MAX);
-        }
-        if (step % 64 == 63) { err = hipGetLastError(); if (err == hipSuccess) err = hipEventRecord(ev[(step / 64) & 1], st); }
-    }
-    if (err == hipSuccess) {
-        if (kv <= 256) hipLaunchKernelGGL((band_back_blk_kernel<256>), dim3(G), dim3(256), 0, st, a, out, ldo, slots, perm);
-        else hipLaunchKernelGGL((band_back_blk_kernel<1024>), dim3(G), dim3(1024), 0, st, a, out, ldo, slots, perm);
-        err = hipGetLastError();
-    }
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    return err;
-}
-
-hipError_t launch_tiled(const BandArgs& a, const BlkArgs& w, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
-    switch (band_tiled_nb(a.kl, a.ku)) {
-    case BNB: return launch_tiled_nb<BNB>(a, w, G, st, out, ldo, slots, perm);
-    case TNB_MID: return launch_tiled_nb<TNB_MID>(a, w, G, st, out, ldo, slots, perm);
-    default: return launch_tiled_nb<TNB_TALL>(a, w, G, st, out, ldo, slots, perm);
     }
 }
 
@@ -904,26 +901,28 @@ band_otrail_kernel(BandArgs a, BlkArgs w, int J0, int nrt)
             }
 }
 
-// The whole wide solve of G matrices on `st`.  w.lw is the tiled method's panel of L (short last blocks), lwo the LW of the
-// outer blocks.  Per inner step the tiled method's launches plus the interchanges on LW, per outer block the two outer
-// launches; the launch queue is bounded as in launch_tiled_nb, counted in inner steps.
+// The whole tiled (lwo == nullptr) or wide solve of G matrices on `st`.  w.lw is the tiled method's panel of L (wide: short
+// last blocks), lwo the LW of the outer blocks.  Per inner step three launches (the trailing update only where rows lie below
+// the block), wide: plus the interchanges on LW; per outer block the two outer launches; then the blocked back substitution.
+// Without lwo no block is `full`: every step runs uncapped over the whole reach kv, and since NBO is a multiple of every NB the
+// steps j0 are 0, NB, 2 NB, ... -- the tiled method is the wide method without an outer block.
 template <int NB>
-hipError_t launch_wide_nb(const BandArgs& a, const BlkArgs& w, c128* lwo, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
+hipError_t launch_tiled_nb(const BandArgs& a, const BlkArgs& w, c128* lwo, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
+    static_assert(NBO % NB == 0, "the inner steps tile an outer block");
     constexpr size_t orow_lds = sizeof(c128) * (NBO * NBO + 2 * NBO * ORC);
     const int kv = a.kl + a.ku, RC = 256 / NB, LH = a.kl + NBO;
     const long LS = (long)LH * NBO;
     // every call, for the device the call runs on: cheap beside the solve, and a refusal ends the solve here
-    hipError_t err = hipFuncSetAttribute((const void*)band_orow_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)orow_lds);
+    hipError_t err = lwo ? hipFuncSetAttribute((const void*)band_orow_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)orow_lds) : hipSuccess;
     if (err == hipSuccess) err = hipMemsetAsync(w.ju, 0, sizeof(int) * G, st);
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    for (auto& e : ev) if (err == hipSuccess) err = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+    StepThrottle th;
+    if (err == hipSuccess) err = th.err;
     int step = 0;
     for (int J0 = 0; J0 < a.n && err == hipSuccess; J0 += NBO) {
         const int HO = std::min(a.kl + NBO, a.n - J0);
-        const bool full = a.n - J0 >= NBO && HO > NBO;
+        const bool full = lwo && a.n - J0 >= NBO && HO > NBO;
         for (int j0 = J0; j0 < std::min(J0 + NBO, a.n) && err == hipSuccess; j0 += NB, ++step) {
-            if (step % 64 == 0 && step >= 128) err = hipEventSynchronize(ev[(step / 64) & 1]);
-            if (err != hipSuccess) break;
+            if ((err = th.before_step(step)) != hipSuccess) break;
             const int d = j0 - J0;
             BlkArgs wi = w;
             if (full) { wi.lw = lwo + d + (long)d * LH; wi.lh = LH; wi.ls = LS; }
@@ -936,12 +935,12 @@ hipError_t launch_wide_nb(const BandArgs& a, const BlkArgs& w, c128* lwo, int G,
                 hipLaunchKernelGGL(band_lw_swap_kernel, dim3(G), dim3(64), 0, st, a, wo, J0, d, NB, std::min(a.kl + NB, a.n - j0));
             }
             hipLaunchKernelGGL(band_row_kernel<NB>, dim3(ntile + 1, G), dim3(256), 0, st, a, wi, j0, ntile, cap);
-            const int below = std::min(a.kl + NB, a.n - j0) - NB;
+            const int below = std::min(a.kl + NB, a.n - j0) - NB;           // rows of L21; none in a last, short block
             if (below > 0) {
                 const int nrt = (below + TRT - 1) / TRT;
                 hipLaunchKernelGGL(band_trail_kernel<NB>, dim3((nct + 1) * nrt, G), dim3(TRT), 0, st, a, wi, j0, nct, nrt, cap);
             }
-            if (step % 64 == 63) { err = hipGetLastError(); if (err == hipSuccess) err = hipEventRecord(ev[(step / 64) & 1], st); }
+            err = th.after_step(step, st);
         }
         if (full && err == hipSuccess) {
             BlkArgs wo = w; wo.lw = lwo; wo.lh = LH; wo.ls = LS;
@@ -951,21 +950,7 @@ hipError_t launch_wide_nb(const BandArgs& a, const BlkArgs& w, c128* lwo, int G,
         }
     }
     if (err == hipSuccess) err = hipGetLastError();
-    if (err == hipSuccess) {
-        if (kv <= 256) hipLaunchKernelGGL((band_back_blk_kernel<256>), dim3(G), dim3(256), 0, st, a, out, ldo, slots, perm);
-        else hipLaunchKernelGGL((band_back_blk_kernel<1024>), dim3(G), dim3(1024), 0, st, a, out, ldo, slots, perm);
-        err = hipGetLastError();
-    }
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    return err;
-}
-
-hipError_t launch_wide(const BandArgs& a, const BlkArgs& w, c128* lwo, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
-    switch (band_tiled_nb(a.kl, a.ku)) {
-    case BNB: return launch_wide_nb<BNB>(a, w, lwo, G, st, out, ldo, slots, perm);
-    case TNB_MID: return launch_wide_nb<TNB_MID>(a, w, lwo, G, st, out, ldo, slots, perm);
-    default: return launch_wide_nb<TNB_TALL>(a, w, lwo, G, st, out, ldo, slots, perm);
-    }
+    return err == hipSuccess ? launch_back_blk(a, G, st, out, ldo, slots, perm) : err;
 }
 
 // ---- the narrow method (maus_band_set_method(ctx, 8)) -------------------------------------------------------
@@ -1182,16 +1167,6 @@ void launch_narrow(const BandArgs& a, int G, hipStream_t st, c128* out, long ldo
     hipLaunchKernelGGL(band_narrow_back_kernel, dim3(G), dim3(64), 0, st, a, out, ldo, slots, perm);
 }
 
-// the elements of the blocked / tiled panel of L per solve, and of the wide method's LW; lw of a workspace of G solves holds
-// the G panels, then the G LW
-size_t band_lw_small(int kl) { return (size_t)(kl + BNB) * BNB; }
-size_t band_lw_outer(int kl) { return (size_t)(kl + NBO) * NBO; }
-
-hipError_t launch_kind(int kind, const BandArgs& a, const BlkArgs& w, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
-    if (kind == 4) return launch_wide(a, w, w.lw + band_lw_small(a.kl) * G, G, st, out, ldo, slots, perm);
-    return kind == 1 ? launch_blocked(a, w, G, st, out, ldo, slots, perm) : launch_tiled(a, w, G, st, out, ldo, slots, perm);
-}
-
 // workgroup size from (kl, ku) alone: one wave for narrow bands, where the barriers of every column dominate
 int band_threads(int kl, int ku) {
     const long w = (long)kl * (kl + ku);
@@ -1214,56 +1189,70 @@ void launch_back(const BandArgs& a, int G, hipStream_t st, c128* out, long ldo, 
     }
 }
 
-// kinds 0 and 8: the two one-launch-per-phase schedules on the same workspace
-void launch_column(int kind, const BandArgs& a, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
-    if (kind == 8) { launch_narrow(a, G, st, out, ldo, slots, perm); return; }
-    launch_factor(a, G, st);
-    launch_back(a, G, st, out, ldo, slots, perm);
+// The solve of G matrices on `st` by the schedule of the plan.  w is read where plan.panel; the LW of the wide method lies
+// behind the G panels of lw.  The one-launch-per-phase schedules (column, narrow) report their errors at the caller's next check.
+hipError_t launch_solve(const BandPlan& plan, const BandArgs& a, const BlkArgs& w, int G, hipStream_t st, c128* out, long ldo,
+                        const int* slots, const int* perm) {
+    switch (plan.kind) {
+    case BK_COLUMN:
+        launch_factor(a, G, st);
+        launch_back(a, G, st, out, ldo, slots, perm);
+        return hipSuccess;
+    case BK_NARROW:
+        launch_narrow(a, G, st, out, ldo, slots, perm);
+        return hipSuccess;
+    case BK_BLOCKED:
+        return plan.nb == BNB ? launch_blocked_nb<BNB>(a, w, G, st, out, ldo, slots, perm)
+                              : launch_blocked_nb<BNB_TALL>(a, w, G, st, out, ldo, slots, perm);
+    default: {
+        c128* lwo = plan.nbo ? w.lw + plan.lw_small * G : nullptr;
+        switch (plan.nb) {
+        case BNB: return launch_tiled_nb<BNB>(a, w, lwo, G, st, out, ldo, slots, perm);
+        case TNB_MID: return launch_tiled_nb<TNB_MID>(a, w, lwo, G, st, out, ldo, slots, perm);
+        default: return launch_tiled_nb<TNB_TALL>(a, w, lwo, G, st, out, ldo, slots, perm);
+        }
+    }
+    }
 }
 
-// algorithmic flops and bytes of G solves: 8 n kl (kl + ku) for the factorisation, 8 n (2 kl + ku) for the
-// solve; the band storage read and written once
+// algorithmic flops of G solves: 8 n kl (kl + ku) for the factorisation, 8 n (2 kl + ku) for the solve
 double band_flops(int n, int kl, int ku, int G) { return 8.0 * G * n * ((double)kl * (kl + ku) + 2.0 * kl + ku); }
-double band_bytes(int n, int ldab, int G) { return 32.0 * G * (double)ldab * n; }
 
-// the blocked method moves the band once per block step over the columns a pivot row can reach (kl + ku of them when every
-// step pivots from the bottom; ku when none does -- the reach is only known on the device, so this is the upper end), and
-// once more in the back substitution
-double band_blocked_bytes(int n, int kl, int ku, int G) {
-    const int nb = band_nb(kl, ku);
-    return 32.0 * G * ((double)(n + nb - 1) / nb) * (kl + nb) * (double)(nb + kl + ku) + 16.0 * G * (double)n * (kl + ku + 1);
+// Bytes of G solves.
+//   column, narrow  the band storage read and written once.
+//   blocked  the band once per block step over the columns a pivot row can reach (kl + ku of them when every step pivots from
+//            the bottom; ku when none does -- the reach is only known on the device, so this is the upper end), and once more
+//            in the back substitution.
+//   tiled    the same upper end of the band per block step, and L21 once per column tile of the trailing update.
+//   wide     that upper end once per outer block step, LW once per column tile of the outer trailing update, and inside the
+//            block the inner steps' share: the block's NBO columns over the slice's rows and L21 once per column tile of the
+//            inner trailing update.  An upper end like the two above.
+double band_bytes(const BandPlan& plan, int n, int kl, int ku, int G) {
+    const int nb = plan.nb;
+    const double back = 16.0 * G * (double)n * (kl + ku + 1);
+    switch (plan.kind) {
+    case BK_BLOCKED:
+        return 32.0 * G * ((double)(n + nb - 1) / nb) * (kl + nb) * (double)(nb + kl + ku) + back;
+    case BK_TILED: {
+        const double steps = (double)(n + nb - 1) / nb, nct = (double)((kl + ku + TCT - 1) / TCT + 1);
+        return G * steps * (32.0 * (kl + nb) * (double)(nb + kl + ku) + 16.0 * (kl + nb) * (double)nb * nct) + back;
+    }
+    case BK_WIDE: {
+        const double outer = (double)(n + NBO - 1) / NBO, inner = (double)(n + nb - 1) / nb;
+        const double octs = (double)((kl + ku + OCT - 1) / OCT), icts = (double)(NBO / TCT + 1);
+        return G * outer * (32.0 * (kl + NBO) * (double)(NBO + kl + ku) + 16.0 * (kl + NBO) * (double)NBO * octs)
+             + G * inner * (32.0 * (kl + nb) * (double)NBO + 16.0 * (kl + nb) * (double)nb * icts) + back;
+    }
+    default:
+        return 32.0 * G * (double)(2 * kl + ku + 1) * n;
+    }
 }
 
-// the tiled method moves the same upper end of the band per block step, and L21 once per column tile of the trailing update
-double band_tiled_bytes(int n, int kl, int ku, int G) {
-    const int nb = band_tiled_nb(kl, ku);
-    const double steps = (double)(n + nb - 1) / nb, nct = (double)((kl + ku + TCT - 1) / TCT + 1);
-    return G * steps * (32.0 * (kl + nb) * (double)(nb + kl + ku) + 16.0 * (kl + nb) * (double)nb * nct) + 16.0 * G * (double)n * (kl + ku + 1);
-}
-
-// the wide method moves that upper end of the band once per outer block step, LW once per column tile of the outer trailing
-// update, and inside the block the inner steps' share: the block's NBO columns over the slice's rows and L21 once per column
-// tile of the inner trailing update.  An upper end like the two above.
-double band_wide_bytes(int n, int kl, int ku, int G) {
-    const int nb = band_tiled_nb(kl, ku);
-    const double outer = (double)(n + NBO - 1) / NBO, inner = (double)(n + nb - 1) / nb;
-    const double octs = (double)((kl + ku + OCT - 1) / OCT), icts = (double)(NBO / TCT + 1);
-    return G * outer * (32.0 * (kl + NBO) * (double)(NBO + kl + ku) + 16.0 * (kl + NBO) * (double)NBO * octs)
-         + G * inner * (32.0 * (kl + nb) * (double)NBO + 16.0 * (kl + nb) * (double)nb * icts) + 16.0 * G * (double)n * (kl + ku + 1);
-}
-
-int band_class(int kind) { return kind == 1 ? KC_BAND_BLOCKED : (kind == 2 ? KC_BAND_TILED : (kind == 4 ? KC_BAND_WIDE : KC_BAND)); }
-double band_kind_bytes(int kind, int n, int kl, int ku, int G) {
-    if (kind == 4) return band_wide_bytes(n, kl, ku, G);
-    return kind == 1 ? band_blocked_bytes(n, kl, ku, G) : (kind == 2 ? band_tiled_bytes(n, kl, ku, G) : band_bytes(n, 2 * kl + ku + 1, G));
-}
-
-// bytes of one solve in the workspace; the blocked and the tiled method (kind 1, 2) add their panel of L ((kl + nb) x nb,
-// nb <= BNB) and their reach, the wide method (kind 4) its LW as well; the narrow method (kind 8) adds nothing
-size_t band_per_solve(int n, int kl, int ku, int kind) {
+// bytes of one solve in the workspace: the band storage, the right-hand side and the pivots; where the plan has a panel, lw
+// and the reach as well
+size_t band_per_solve(const BandPlan& plan, int n, int kl, int ku) {
     const size_t ldab = 2 * (size_t)kl + ku + 1;
-    return sizeof(c128) * (ldab * n + n) + sizeof(int) * (size_t)n
-         + (band_kind_blocked(kind) ? sizeof(c128) * band_lw_small(kl) + sizeof(int) : 0) + (kind == 4 ? sizeof(c128) * band_lw_outer(kl) : 0);
+    return sizeof(c128) * (ldab * n + n) + sizeof(int) * (size_t)n + (plan.panel ? sizeof(c128) * plan.lw + sizeof(int) : 0);
 }
 
 void band_ws_free(maus_ctx* c) {
@@ -1279,10 +1268,9 @@ void band_ws_free(maus_ctx* c) {
 // memory) -- never shrunk; larger batches run in balanced chunks.
 int ensure_band_ws(maus_ctx* c, int want) {
     const int n = c->band_n, ldab = 2 * c->band_kl + c->band_ku + 1;
-    const int kind = band_kind(c->band_method, c->band_kl, c->band_ku);
-    const bool blocked = band_kind_blocked(kind), wide = kind == 4;     // the methods that allocate lw and ju; LW behind lw
-    const size_t per = band_per_solve(n, c->band_kl, c->band_ku, kind);
-    const unsigned long long key = ((unsigned long long)n << 32) | ((unsigned long long)blocked << 31) | ((unsigned long long)wide << 30) | (unsigned)ldab;
+    const BandPlan plan = band_plan(c->band_method, c->band_kl, c->band_ku);
+    const size_t per = band_per_solve(plan, n, c->band_kl, c->band_ku);
+    const unsigned long long key = ((unsigned long long)n << 32) | ((unsigned long long)plan.panel << 31) | ((unsigned long long)(plan.nbo != 0) << 30) | (unsigned)ldab;
     const bool same = c->band_ab && c->band_ws_key == key;
     if (same && (c->band_g >= want || c->band_at_limit)) return 0;
     size_t fr = 0, tot = 0;
@@ -1307,8 +1295,8 @@ int ensure_band_ws(maus_ctx* c, int want) {
     HIPCHK(c, hipMalloc((void**)&c->band_ipiv, sizeof(int) * (size_t)n * G));
     HIPCHK(c, hipMalloc((void**)&c->band_info, sizeof(int) * G));
     HIPCHK(c, hipMalloc((void**)&c->band_flags, sizeof(int) * G));
-    if (blocked) {
-        HIPCHK(c, hipMalloc((void**)&c->band_lw, sizeof(c128) * (band_lw_small(c->band_kl) + (wide ? band_lw_outer(c->band_kl) : 0)) * G));
+    if (plan.panel) {
+        HIPCHK(c, hipMalloc((void**)&c->band_lw, sizeof(c128) * plan.lw * G));
         HIPCHK(c, hipMalloc((void**)&c->band_ju, sizeof(int) * G));
     }
     c->band_g = G; c->band_ws_key = key; c->band_allocs++;
@@ -1323,10 +1311,9 @@ BandArgs band_args(maus_ctx* c) {
     return a;
 }
 
-BlkArgs blk_args(maus_ctx* c) {
-    BlkArgs w; w.lw = c->band_lw; w.ju = c->band_ju;
-    const int nb = band_kind_nb(band_kind(c->band_method, c->band_kl, c->band_ku), c->band_kl, c->band_ku);
-    w.lh = c->band_kl + nb; w.ls = (long)w.lh * nb;
+BlkArgs blk_args(const BandPlan& plan, int kl, c128* lw, int* ju) {
+    BlkArgs w; w.lw = lw; w.ju = ju;
+    w.lh = kl + plan.nb; w.ls = (long)w.lh * plan.nb;
     return w;
 }
 
@@ -1413,22 +1400,21 @@ int maus_band_solve(maus_ctx* c, const int* slots, int count, const double* shif
     const int Gmax = (count + nchunks - 1) / nchunks;
     std::vector<int> h_info(Gmax), h_flags(Gmax);
     const BandArgs a = band_args(c);
-    const int kind = band_kind(c->band_method, a.kl, a.ku);
-    const BlkArgs w = blk_args(c);
+    const BandPlan plan = band_plan(c->band_method, a.kl, a.ku);
+    const BlkArgs w = blk_args(plan, a.kl, c->band_lw, c->band_ju);
     for (int off = 0; off < count; off += Gmax) {
         const int G = std::min(Gmax, count - off);
         if (maus_h2d(c, c->d_slots, slots + off, sizeof(int) * G, c->st)) return -1;
         if (maus_h2d(c, c->d_c1, shift + 2 * (size_t)off, sizeof(c128) * G, c->st)) return -1;
         if (maus_h2d(c, c->d_r1, psi + off, sizeof(double) * G, c->st)) return -1;
         {
-            ProfScope ps(c, band_class(kind), band_flops(a.n, a.kl, a.ku, G), band_kind_bytes(kind, a.n, a.kl, a.ku, G));
+            ProfScope ps(c, plan.cls, band_flops(a.n, a.kl, a.ku, G), band_bytes(plan, a.n, a.kl, a.ku, G));
             HIPCHK(c, hipMemsetAsync(a.info, 0, sizeof(int) * G, c->st));
             HIPCHK(c, hipMemsetAsync(a.flags, 0, sizeof(int) * G, c->st));
             HIPCHK(c, hipMemsetAsync(a.ab, 0, sizeof(c128) * (size_t)a.ldab * a.n * G, c->st));
             hipLaunchKernelGGL(band_build_csr_kernel, dim3((a.n + 255) / 256, G), dim3(256), 0, c->st, a, c->Acsr.ptr, c->Acsr.idx,
                                c->Acsr.val, c->band_perm, c->band_iperm, c->d_c1, c->d_r1, rhs_mode, c->X, c->ldp, c->d_slots, c->b);
-            if (band_kind_blocked(kind)) HIPCHK(c, launch_kind(kind, a, w, G, c->st, c->W, c->ldp, c->d_slots, c->band_perm));
-            else launch_column(kind, a, G, c->st, c->W, c->ldp, c->d_slots, c->band_perm);
+            HIPCHK(c, launch_solve(plan, a, w, G, c->st, c->W, c->ldp, c->d_slots, c->band_perm));
         }
         if (maus_d2h(c, h_info.data(), a.info, sizeof(int) * G, c->st)) return -1;
         if (maus_d2h(c, h_flags.data(), a.flags, sizeof(int) * G, c->st)) return -1;
@@ -1443,7 +1429,7 @@ int maus_band_workspace_allocs(maus_ctx* c) { return c ? c->band_allocs : -1; }
 
 int maus_band_set_method(maus_ctx* c, int method) {
     if (!c) return -1;
-    if (method != 4 && method != 8 && (method < 0 || method > 2))
+    if (!band_method_ok(method))
         FAIL(c, "maus_band_set_method: method must be 0 (column), 1 (blocked), 2 (tiled), 4 (wide) or 8 (narrow)");
     c->band_method = method;                                            // the workspace follows at its next use (ensure_band_ws)
     return 0;
@@ -1454,15 +1440,25 @@ int maus_band_get_method(maus_ctx* c) { return c ? c->band_method : -1; }
 int maus_band_kernel_for(maus_ctx* c, int n, int kl, int ku, int* nb_out) {
     if (!c) return -1;
     if (n <= 0 || kl < 0 || ku < 0) FAIL(c, "maus_band_kernel_for: bad sizes");
-    const int kind = band_kind(c->band_method, kl, ku);
-    if (nb_out) *nb_out = band_kind_nb(kind, kl, ku);
-    return kind;
+    const BandPlan plan = band_plan(c->band_method, kl, ku);
+    if (nb_out) *nb_out = plan.nb;
+    return plan.kind;
 }
 
 int maus_band_outer_nb(maus_ctx* c, int n, int kl, int ku) {
     if (!c) return -1;
     if (n <= 0 || kl < 0 || ku < 0) FAIL(c, "maus_band_outer_nb: bad sizes");
-    return band_kind(c->band_method, kl, ku) == 4 ? NBO : 0;
+    return band_plan(c->band_method, kl, ku).nbo;
+}
+
+int maus_band_plan(int method, int n, int kl, int ku, int32_t* kind, int32_t* nb, int32_t* outer_nb, int64_t* ws_bytes_per_solve) {
+    if (!band_method_ok(method) || n < 0 || kl < 0 || ku < 0) return -1;
+    const BandPlan plan = band_plan(method, kl, ku);
+    if (kind) *kind = plan.kind;
+    if (nb) *nb = plan.nb;
+    if (outer_nb) *outer_nb = plan.nbo;
+    if (ws_bytes_per_solve) *ws_bytes_per_solve = (int64_t)band_per_solve(plan, n, kl, ku);
+    return 0;
 }
 
 int maus_band_lu_host(maus_ctx* c, int count, int n, int kl, int ku, const double* ab, const double* b, double* x_out,
@@ -1477,26 +1473,22 @@ int maus_band_lu_host(maus_ctx* c, int count, int n, int kl, int ku, const doubl
     auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
     const size_t o_ab = take(abb * count), o_x = take(xb * count), o_o = take(xb * count), o_p = take(ib * count),
                  o_i = take(sizeof(int) * count), o_f = take(sizeof(int) * count);
-    const int kind = band_kind(c->band_method, kl, ku);
-    const bool blocked = band_kind_blocked(kind);
-    BlkArgs w; w.lw = nullptr; w.ju = nullptr; w.lh = kl + band_kind_nb(kind, kl, ku); w.ls = (long)w.lh * band_kind_nb(kind, kl, ku);
-    const size_t o_l = take(blocked ? sizeof(c128) * (band_lw_small(kl) + (kind == 4 ? band_lw_outer(kl) : 0)) * count : 0), o_j = take(blocked ? sizeof(int) * count : 0);
+    const BandPlan plan = band_plan(c->band_method, kl, ku);
+    const size_t o_l = take(sizeof(c128) * plan.lw * count), o_j = take(plan.panel ? sizeof(int) * count : 0);
     if (ensure_scratch(c, off)) return -1;
     char* base = (char*)c->scratch;
     a.ab = (c128*)(base + o_ab); a.x = (c128*)(base + o_x); a.ipiv = (int*)(base + o_p); a.info = (int*)(base + o_i); a.flags = (int*)(base + o_f);
     c128* out = (c128*)(base + o_o);
-    if (blocked) { w.lw = (c128*)(base + o_l); w.ju = (int*)(base + o_j); }
+    const BlkArgs w = blk_args(plan, kl, plan.panel ? (c128*)(base + o_l) : nullptr, plan.panel ? (int*)(base + o_j) : nullptr);
     if (maus_stage_h2d(c, a.ab, ab, abb * count, c->st)) return -1;
     if (maus_stage_h2d(c, a.x, b, xb * count, c->st)) return -1;
     HIPCHK(c, hipMemsetAsync(a.info, 0, sizeof(int) * count, c->st));
     HIPCHK(c, hipMemsetAsync(a.flags, 0, sizeof(int) * count, c->st));
     {
-        ProfScope ps(c, band_class(kind), band_flops(n, kl, ku, count), band_kind_bytes(kind, n, kl, ku, count));
+        ProfScope ps(c, plan.cls, band_flops(n, kl, ku, count), band_bytes(plan, n, kl, ku, count));
         hipLaunchKernelGGL(band_scan_kernel, dim3(64, count), dim3(256), 0, c->st, a);
-        if (blocked) {
-            hipLaunchKernelGGL(band_zero_fill_kernel, dim3(64, count), dim3(256), 0, c->st, a);
-            HIPCHK(c, launch_kind(kind, a, w, count, c->st, out, n, nullptr, nullptr));
-        } else launch_column(kind, a, count, c->st, out, n, nullptr, nullptr);
+        if (plan.panel) hipLaunchKernelGGL(band_zero_fill_kernel, dim3(64, count), dim3(256), 0, c->st, a);
+        HIPCHK(c, launch_solve(plan, a, w, count, c->st, out, n, nullptr, nullptr));
     }
     std::vector<int> h_info(count), h_flags(count);
     if (maus_stage_d2h(c, x_out, out, xb * count, c->st)) return -1;

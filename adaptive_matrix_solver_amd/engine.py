@@ -28,6 +28,7 @@ import weakref
 import numpy as np
 
 from . import _cabi
+from .band import DIRECT_METHOD
 from .candstore import C_NP, C_PY, EXACT, F_NP, F_PY, MISSING, CandidateStore, HistoryRecord
 from ._cabi import KIND_EIG, KIND_LINEAR, KIND_SVD, PERT_MT19937, PERT_NONE, PERT_UNIFORM, POP_U, POP_W, POP_X
 
@@ -237,7 +238,7 @@ def tridiagonal_eigenvalues(ctx, d, e):
     return np.sort(sla.eigvalsh_tridiagonal(d, e))
 
 
-SPARSE_DIRECT_MODES = ("auto", "dense", "band", "blocked", "tiled", "narrow", "wide")
+SPARSE_DIRECT_MODES = ("auto", "dense") + tuple(DIRECT_METHOD)
 
 
 def sparse_direct_mode(mode):
@@ -475,7 +476,7 @@ class DeviceEngine:
 
     def uses_band(self, n: int) -> bool:
         """Whether a sparse n x n matrix takes the band solve (sparse_direct; 'auto': above maus_lu_max_n())."""
-        if self.sparse_direct in ("band", "blocked", "tiled", "narrow", "wide"):
+        if self.sparse_direct in DIRECT_METHOD:
             return True
         if self.sparse_direct == "dense":
             return False
@@ -497,14 +498,8 @@ class DeviceEngine:
         pay neither the ordering nor the host copy of the pattern."""
         if not self._band_ready:
             perm, kl, ku = self.band_shape(self._bound)
-            if self.sparse_direct == "blocked":  # the only modes that touch the method: contexts without it keep working
-                self.ctx.band_set_method(1)
-            elif self.sparse_direct == "tiled":
-                self.ctx.band_set_method(2)
-            elif self.sparse_direct == "wide":
-                self.ctx.band_set_method(4)
-            elif self.sparse_direct == "narrow":
-                self.ctx.band_set_method(8)
+            if DIRECT_METHOD.get(self.sparse_direct):   # 'band' does not touch the method: contexts without it keep working
+                self.ctx.band_set_method(DIRECT_METHOD[self.sparse_direct])
             self.ctx.band_prepare(perm)
             self._band_ready = True
 

@@ -30,6 +30,7 @@ import numpy as np
 
 from . import _cabi
 from ._cabi import POP_U, POP_X
+from .band import DIRECT_METHOD, band_bytes_per_solve, band_order
 from .candstore import C_NP as _C_NP, C_PY as _C_PY, EXACT as _EXACT, F_NP as _F_NP, F_PY as _F_PY, HREF as _HREF, MISSING as _MISSING
 from .engine import DIRECT, GMRES, DeviceEngine, _advance_numpy_stream, sparse_direct_mode, sparse_eigsh_mode, sparse_gmres_mode
 
@@ -198,19 +199,13 @@ class InverseIterateSolver:
             elif getattr(ctx, "gmres_method", None) is not None and ctx.gmres_method() != _cabi.GMRES_DEFAULT:
                 ctx.gmres_set_method(_cabi.GMRES_DEFAULT)
             # direct solves above maus_lu_max_n() (or with sparse_direct='band'): the band LU of csrc/band.hip
-            band = self.sparse_direct in ("band", "blocked", "tiled", "narrow", "wide") or (self.sparse_direct == "auto" and n > ctx.lu_max_n())
+            band = self.sparse_direct in DIRECT_METHOD or (self.sparse_direct == "auto" and n > ctx.lu_max_n())
             if band:
-                from .band import band_order
-                # the context is shared by every InverseIterateSolver: each solve states its method ('blocked', 'tiled',
-                # 'wide' and 'narrow' are opt-in)
-                if self.sparse_direct == "blocked":
-                    ctx.band_set_method(_cabi.BAND_BLOCKED)
-                elif self.sparse_direct == "tiled":
-                    ctx.band_set_method(_cabi.BAND_TILED)
-                elif self.sparse_direct == "wide":
-                    ctx.band_set_method(_cabi.BAND_WIDE)
-                elif self.sparse_direct == "narrow":
-                    ctx.band_set_method(_cabi.BAND_NARROW)
+                # the context is shared by every InverseIterateSolver: each solve states its method (every one but the
+                # column kernel's is opt-in); contexts without the call keep working under 'band' and 'auto'
+                method = DIRECT_METHOD.get(self.sparse_direct, _cabi.BAND_COLUMN)
+                if method != _cabi.BAND_COLUMN:
+                    ctx.band_set_method(method)
                 elif getattr(ctx, "band_method", None) is not None and ctx.band_method() != _cabi.BAND_COLUMN:
                     ctx.band_set_method(_cabi.BAND_COLUMN)
                 ctx.band_prepare(band_order(A_sp)[0])
@@ -1425,7 +1420,6 @@ class MAUS_Solver:
     def _check_band_fits(self):
         """A sparse eigenvalue / linear problem on the band path: n <= maus_sparse_max_n() and one band solve in at
         most 1/16 of the device's total HBM -- a rule of the matrix and the device, never of free memory or the batch."""
-        from .band import band_bytes_per_solve
         n = self.N_rows
         ctx = self.engine.ctx
         max_n = ctx.sparse_max_n()
@@ -1433,8 +1427,7 @@ class MAUS_Solver:
             raise NotImplementedError(f"sparse eigenvalue / linear problems need n <= {max_n}: n = {n}")
         perm, kl, ku = self.engine.band_shape(self.M)
         direct = getattr(self.engine, "sparse_direct", None)
-        per = band_bytes_per_solve(n, kl, ku, blocked=direct == "blocked", tiled=direct == "tiled", wide=direct == "wide",
-                                   narrow=direct == "narrow")
+        per = band_bytes_per_solve(n, kl, ku, method=DIRECT_METHOD.get(direct, 0))
         hbm = int(ctx.device_info()["hbm_total"])
         if per * 16 > hbm:
             raise NotImplementedError(f"sparse eigenvalue / linear problem too wide for the band solve: n = {n}, kl = {kl}, "

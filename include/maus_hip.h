@@ -132,7 +132,11 @@ int maus_matrix_is_sparse(maus_ctx* ctx);
  * maus_band_kernel_for: what (n, kl, ku) runs under the current method: returns 0 (column kernel), 1 (blocked), 2 (tiled),
  *   4 (wide) or 8 (narrow); nb_out (may be NULL): the block width (wide: of the inner steps), 1 for the column kernel and
  *   for narrow.
- * maus_band_outer_nb: the width of the outer block (64) where (n, kl, ku) runs wide under the current method, 0 elsewhere. */
+ * maus_band_outer_nb: the width of the outer block (64) where (n, kl, ku) runs wide under the current method, 0 elsewhere.
+ * maus_band_plan: the same answers for any `method`, without a context and without opening a device: kind and nb as
+ *   maus_band_kernel_for, outer_nb as maus_band_outer_nb, ws_bytes_per_solve the workspace bytes of one solve (what
+ *   maus_band_reserve allocates per solve).  Every out pointer may be NULL.  Returns 0, or -1 for a method that
+ *   maus_band_set_method refuses or a negative size. */
 int maus_sparse_max_n(void);
 int maus_band_prepare(maus_ctx* ctx, const int32_t* perm, int n, int* kl_out, int* ku_out);
 int maus_band_reserve(maus_ctx* ctx, int count, int* capacity_out);
@@ -145,6 +149,8 @@ int maus_band_set_method(maus_ctx* ctx, int method);
 int maus_band_get_method(maus_ctx* ctx);
 int maus_band_kernel_for(maus_ctx* ctx, int n, int kl, int ku, int* nb_out);
 int maus_band_outer_nb(maus_ctx* ctx, int n, int kl, int ku);
+int maus_band_plan(int method, int n, int kl, int ku, int32_t* kind, int32_t* nb, int32_t* outer_nb,
+                   int64_t* ws_bytes_per_solve);
 
 /* Upload b (AMS:146, 275). */
 int maus_set_rhs(maus_ctx* ctx, const double* b_c128, int n);

@@ -6,7 +6,7 @@ import random
 import numpy as np
 import pytest
 
-from adaptive_matrix_solver_amd.band import band_bytes_per_solve, band_order, runs_blocked
+from adaptive_matrix_solver_amd.band import band_bytes_per_solve, band_order, kernel_for, runs_blocked
 from test_band_host import FakeBandContext, _diag, _linear, five_point
 
 
@@ -27,7 +27,7 @@ class FakeBlockedContext(FakeBandContext):
         return self.method
 
     def band_kernel_for(self, n, kl, ku):
-        return (1, 16 if kl + 16 <= 1024 else 8) if self.method == 1 and runs_blocked(kl, ku) else (0, 1)
+        return kernel_for(self.method, kl, ku)
 
     def band_prepare(self, perm):
         self.log.append(("prepare",))
