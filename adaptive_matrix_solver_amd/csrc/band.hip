@@ -37,6 +37,64 @@ struct BandArgs {
 
 __device__ __forceinline__ long bix(const BandArgs& a, int g) { return (long)g * a.ldab * a.n; }
 
+// ---- pieces that several kernels share: each rule is stated here, once ----------------------------------------------------
+// Pivot across the workgroup: from each thread's first maximum (best, bidx) the index of the first maximum of all, the lowest
+// index among equals, INT_MAX where none is finite.  One barrier (LDS_ONLY: lds_barrier()); s_best / s_idx are free after the next.
+template <int NW, bool LDS_ONLY>
+__device__ __forceinline__ int block_argmax(double best, int bidx, double (&s_best)[NW], int (&s_idx)[NW], int lane, int wave) {
+    wave_argmax(best, bidx);
+    if (lane == 0) { s_best[wave] = best; s_idx[wave] = bidx; }
+    if constexpr (LDS_ONLY) lds_barrier(); else __syncthreads();
+    double m = s_best[0]; int p = s_idx[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) {
+        if (s_best[w] > m) { m = s_best[w]; p = s_idx[w]; }
+        else if (s_best[w] == m) p = min(p, s_idx[w]);
+    }
+    return p;
+}
+
+__device__ __forceinline__ double lane_bcast(double v, int l) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+__device__ __forceinline__ c128 lane_bcast(c128 v, int l) { return cmake(lane_bcast(v.x, l), lane_bcast(v.y, l)); }
+
+// A block row keeps 2 NB elements of a column: slots 0 .. NB - 1 its rows j0 .. j0 + NB - 1, slot NB + jj the pivot row of
+// column jj where that row lies below the block's jb rows; pivot rows that coincide share the first such slot.  Thread
+// tid < NB writes the pivot row s_pr[tid] (relative to j0) and the slot s_sl[tid] of column tid; ip: ipiv of column j0.
+template <int NB>
+__device__ __forceinline__ void pivot_slots(const int* ip, int j0, int jb, int tid, int (&s_pr)[NB], int (&s_sl)[NB]) {
+    if (tid >= NB) return;
+    int pr = tid, sl = tid;
+    if (tid < jb) {
+        pr = ip[tid] - 1 - j0;
+        sl = pr;
+        if (pr >= jb) {
+            sl = NB + tid;
+            for (int k = tid - 1; k >= 0; --k) if (ip[k] - 1 - j0 == pr) sl = NB + k;
+        }
+    }
+    s_pr[tid] = pr; s_sl[tid] = sl;
+}
+
+// L11 of a block step out of lw into LDS: NB x NB, column-major, strictly lower, zero elsewhere and from row jb on
+template <int NB, int NT>
+__device__ __forceinline__ void load_l11(c128* s_l11, const c128* lw, int lh, int jb, int tid) {
+    for (int e = tid; e < NB * NB; e += NT) {
+        const int r = e % NB, k = e / NB;
+        s_l11[e] = (k < r && r < jb) ? lw[r + (long)k * lh] : cmake(0.0, 0.0);
+    }
+}
+
+// U12 = L11^-1 A12 on columns in LDS, row r of column q at s_v[q * ld + r], owned by thread (q, r): one barrier per column of L11
+template <int NB>
+__device__ __forceinline__ void solve_l11(c128* s_v, int ld, const c128* s_l11, int jb, int ncol, int q, int r) {
+    for (int k = 0; k + 1 < jb; ++k) {
+        if (q < ncol && r > k && r < jb) cfms(s_v[q * ld + r], s_l11[r + k * NB], s_v[q * ld + k]);
+        __syncthreads();
+    }
+}
+
 // H_k = A[perm][:, perm] - lam_k I + psi_k I into zeroed band storage, one thread per row of the permuted matrix; the
 // diagonal is (a - lam) + psi in NumPy's rounding order, with a = 0 where A stores none (as build_h_csr_kernel).  The permuted
 // right-hand side goes to x.  flags |= 1 on any non-finite value.
@@ -123,15 +181,7 @@ band_factor_kernel(BandArgs a)
             const double v = cabs1(at(kv + p, j));
             if (v > best) { best = v; bidx = p; }                        // NaN never wins (izamax)
         }
-        wave_argmax(best, bidx);
-        if (lane == 0) { s_best[wave] = best; s_idx[wave] = bidx; }
-        __syncthreads();
-        double m = s_best[0]; int jp = s_idx[0];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) {
-            if (s_best[w] > m) { m = s_best[w]; jp = s_idx[w]; }
-            else if (s_best[w] == m) jp = min(jp, s_idx[w]);
-        }
+        int jp = block_argmax<NW, false>(best, bidx, s_best, s_idx, lane, wave);
         if (jp == INT_MAX) jp = 0;
         const c128 piv = at(kv + jp, j), top = at(kv, j);
         if (tid == 0) ipiv[j] = j + jp + 1;                              // LAPACK's 1-based row
@@ -280,15 +330,7 @@ band_panel_kernel(BandArgs a, BlkArgs w, int j0)
                     if (v > best) { best = v; bidx = r; }               // NaN never wins (izamax)
                 }
             });
-            wave_argmax(best, bidx);
-            if (lane == 0) { s_best[wave] = best; s_idx[wave] = bidx; }
-            lds_barrier();
-            double mx = s_best[0]; int pr = s_idx[0];
-#pragma unroll
-            for (int v = 1; v < NW; ++v) {
-                if (s_best[v] > mx) { mx = s_best[v]; pr = s_idx[v]; }
-                else if (s_best[v] == mx) pr = min(pr, s_idx[v]);
-            }
+            int pr = block_argmax<NW, true>(best, bidx, s_best, s_idx, lane, wave);
             if (pr == INT_MAX) pr = jj;
             static_for<RP>([&](auto mc) {
                 constexpr int m = decltype(mc)::value;
@@ -376,10 +418,7 @@ band_update_kernel(BandArgs a, BlkArgs w, int j0, int ntile)
         for (int r = tid; r < H; r += NT) s_v[q * lh + r] = (j0 + r >= l0) ? p[j0 + r] : cmake(0.0, 0.0);
     }
     if (tid < NB) s_pr[tid] = tid < jb ? a.ipiv[(long)g * n + j0 + tid] - 1 - j0 : tid;
-    if (tid < NB * NB) {
-        const int r = tid % NB, k = tid / NB;
-        s_l11[tid] = (k < r && r < jb) ? lw[r + (long)k * lh] : cmake(0.0, 0.0);
-    }
+    load_l11<NB, NT>(s_l11, lw, lh, jb, tid);
     __syncthreads();
     if (tid < ncol)
         for (int jj = 0; jj < jb; ++jj) {
@@ -389,10 +428,7 @@ band_update_kernel(BandArgs a, BlkArgs w, int j0, int ntile)
     __syncthreads();
     {
         const int q = tid / NB, r = tid % NB;
-        for (int k = 0; k + 1 < jb; ++k) {
-            if (q < ncol && r > k && r < jb) cfms(s_v[q * lh + r], s_l11[r + k * NB], s_v[q * lh + k]);
-            __syncthreads();
-        }
+        solve_l11<NB>(s_v, lh, s_l11, jb, ncol, q, r);
         if (q < ncol && r < jb && j0 + r >= lo(q)) col(q)[j0 + r] = s_v[q * lh + r];
     }
     for (int r = jb + tid; r < H; r += NT) {                            // rows below the block: jb = NB here
@@ -474,29 +510,6 @@ hipError_t launch_back_blk(const BandArgs& a, int G, hipStream_t st, c128* out, 
     if (a.kl + a.ku <= 256) hipLaunchKernelGGL((band_back_blk_kernel<256>), dim3(G), dim3(256), 0, st, a, out, ldo, slots, perm);
     else hipLaunchKernelGGL((band_back_blk_kernel<1024>), dim3(G), dim3(1024), 0, st, a, out, ldo, slots, perm);
     return hipGetLastError();
-}
-
-// The whole blocked solve of G matrices on `st`: n / NB block steps of two launches each, then the back substitution.
-template <int NB>
-hipError_t launch_blocked_nb(const BandArgs& a, const BlkArgs& w, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
-    const int kv = a.kl + a.ku, H = a.kl + NB, ntile = (kv + BTC - 1) / BTC;
-    const size_t lds = sizeof(c128) * (size_t)w.lh * BTC;
-    // every call, for the device the call runs on: cheap beside the solve, and a refusal ends the solve here
-    hipError_t err = hipFuncSetAttribute((const void*)band_update_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (err == hipSuccess) err = hipMemsetAsync(w.ju, 0, sizeof(int) * G, st);
-    StepThrottle th;
-    if (err == hipSuccess) err = th.err;
-    int step = 0;
-    for (int j0 = 0; j0 < a.n && err == hipSuccess; j0 += NB, ++step) {
-        if ((err = th.before_step(step)) != hipSuccess) break;
-        if (H <= 256) hipLaunchKernelGGL((band_panel_kernel<256, 1, NB>), dim3(G), dim3(256), 0, st, a, w, j0);
-        else if (H <= 512) hipLaunchKernelGGL((band_panel_kernel<512, 1, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
-        else if (H <= 1024) hipLaunchKernelGGL((band_panel_kernel<512, 2, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
-        else hipLaunchKernelGGL((band_panel_kernel<512, 3, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
-        hipLaunchKernelGGL(band_update_kernel<NB>, dim3(ntile + 1, G), dim3(256), lds, st, a, w, j0, ntile);
-        err = th.after_step(step, st);
-    }
-    return err == hipSuccess ? launch_back_blk(a, G, st, out, ldo, slots, perm) : err;
 }
 
 // ---- the tiled method (maus_band_set_method(ctx, 2)) --------------------------------------------------------
@@ -582,9 +595,8 @@ BandPlan band_plan(int method, int kl, int ku) {
 }
 
 // Block row of block step j0: workgroup (t, g) takes the 256 / NB columns from c0 right of the panel of matrix g, workgroup
-// (ntile, g) its right-hand side.  A column keeps 2 NB elements in LDS: slots 0 .. NB - 1 its rows j0 .. j0 + NB - 1, slot
-// NB + jj the pivot row of column jj where that row lies below the block (pivot rows that coincide share the first slot).
-// Rows above a column's first stored row are read as zero and not written, as band_update_kernel.
+// (ntile, g) its right-hand side.  A column keeps 2 NB elements in LDS, in the slots of pivot_slots.  Rows above a column's
+// first stored row are read as zero and not written, as band_update_kernel.
 template <int NB>
 __global__ void __launch_bounds__(256)
 band_row_kernel(BandArgs a, BlkArgs w, int j0, int ntile, int cap)
@@ -608,23 +620,8 @@ band_row_kernel(BandArgs a, BlkArgs w, int j0, int ntile, int cap)
     const c128* lw = w.lw + (long)g * w.ls;
     auto col = [&](int q) -> c128* { return rhs ? a.x + (long)g * n : ab + (long)(c0 + q) * ldab + kv - (c0 + q); };
     auto lo = [&](int q) { return rhs ? 0 : c0 + q - kv; };
-    if (tid < NB) {
-        const int* ip = a.ipiv + (long)g * n + j0;
-        int pr = tid, sl = tid;
-        if (tid < jb) {
-            pr = ip[tid] - 1 - j0;
-            sl = pr;
-            if (pr >= jb) {
-                sl = NB + tid;
-                for (int k = tid - 1; k >= 0; --k) if (ip[k] - 1 - j0 == pr) sl = NB + k;
-            }
-        }
-        s_pr[tid] = pr; s_sl[tid] = sl;
-    }
-    if (tid < NB * NB) {
-        const int r = tid % NB, k = tid / NB;
-        s_l11[tid] = (k < r && r < jb) ? lw[r + (long)k * lh] : cmake(0.0, 0.0);
-    }
+    pivot_slots<NB>(a.ipiv + (long)g * n + j0, j0, jb, tid, s_pr, s_sl);
+    load_l11<NB, NT>(s_l11, lw, lh, jb, tid);
     __syncthreads();
     for (int e = tid; e < ncol * SL; e += NT) {
         const int q = e / SL, s = e % SL;
@@ -640,10 +637,7 @@ band_row_kernel(BandArgs a, BlkArgs w, int j0, int ntile, int cap)
         }
     __syncthreads();
     const int q = tid / NB, r = tid % NB;
-    for (int k = 0; k + 1 < jb; ++k) {
-        if (q < ncol && r > k && r < jb) cfms(s_v[q * SL + r], s_l11[r + k * NB], s_v[q * SL + k]);
-        __syncthreads();
-    }
+    solve_l11<NB>(s_v, SL, s_l11, jb, ncol, q, r);
     if (q < ncol && r < jb) {
         if (j0 + r >= lo(q)) col(q)[j0 + r] = s_v[q * SL + r];
         const int pr = s_pr[r];
@@ -757,14 +751,9 @@ band_lw_swap_kernel(BandArgs a, BlkArgs w, int J0, int d, int nb, int hin)
     }
 }
 
-__device__ __forceinline__ double lane_bcast(double v, int l) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-
 // Outer block row of the block at J0 (a full one: NBO columns, rows below): workgroup (t, g) takes the ORC columns from c0
-// right of the block of matrix g.  Slots as band_row_kernel: 0 .. NBO - 1 the rows J0 .. J0 + NBO - 1 of a column, NBO + jj
-// the pivot row of column jj where it lies below the block.  Rows above a column's first stored row are read as zero and
-// not written.
+// right of the block of matrix g.  The slots of pivot_slots with jb = NB = NBO.  Rows above a column's first stored row are
+// read as zero and not written.
 __global__ void __launch_bounds__(256)
 band_orow_kernel(BandArgs a, BlkArgs w, int J0)
 {
@@ -783,20 +772,8 @@ band_orow_kernel(BandArgs a, BlkArgs w, int J0)
     const c128* lw = w.lw + (long)g * w.ls;
     auto col = [&](int q) -> c128* { return ab + (long)(c0 + q) * ldab + kv - (c0 + q); };
     auto lo = [&](int q) { return c0 + q - kv; };
-    if (tid < NBO) {
-        const int* ip = a.ipiv + (long)g * n + J0;
-        const int pr = ip[tid] - 1 - J0;
-        int sl = pr;
-        if (pr >= NBO) {
-            sl = NBO + tid;
-            for (int k = tid - 1; k >= 0; --k) if (ip[k] - 1 - J0 == pr) sl = NBO + k;
-        }
-        s_pr[tid] = pr; s_sl[tid] = sl;
-    }
-    for (int e = tid; e < NBO * NBO; e += 256) {
-        const int r = e % NBO, k = e / NBO;
-        s_l11[e] = k < r ? lw[r + (long)k * lh] : cmake(0.0, 0.0);
-    }
+    pivot_slots<NBO>(a.ipiv + (long)g * n + J0, J0, NBO, tid, s_pr, s_sl);
+    load_l11<NBO, 256>(s_l11, lw, lh, NBO, tid);
     __syncthreads();
     for (int e = tid; e < SL * ORC; e += 256) {
         const int q = e / SL, s = e % SL;
@@ -816,7 +793,7 @@ band_orow_kernel(BandArgs a, BlkArgs w, int J0)
     c128 v0 = s_v[(mine ? r : 0) * ORC + wv], v1 = s_v[(mine ? r : 0) * ORC + wv + 4];
     for (int k = 0; k + 1 < NBO; ++k) {
         const c128 l = s_l11[(mine ? r : 0) + k * NBO];                 // zero for r <= k
-        const c128 u0 = cmake(lane_bcast(v0.x, k), lane_bcast(v0.y, k)), u1 = cmake(lane_bcast(v1.x, k), lane_bcast(v1.y, k));
+        const c128 u0 = lane_bcast(v0, k), u1 = lane_bcast(v1, k);
         if (mine && r > k) { cfms(v0, l, u0); cfms(v1, l, u1); }
     }
 #pragma unroll
@@ -899,6 +876,29 @@ band_otrail_kernel(BandArgs a, BlkArgs w, int J0, int nrt)
                 const int q = cb * 16 + lk + 4 * i;
                 if (rok[rb] && q < ncol) cm[J0 + rr[rb] + (long)(c0 + q) * ldc] = cmake(cre[rb][cb][i], cim[rb][cb][i]);
             }
+}
+
+// The whole blocked solve of G matrices on `st`: n / NB block steps of two launches each, then the back substitution.
+template <int NB>
+hipError_t launch_blocked_nb(const BandArgs& a, const BlkArgs& w, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
+    const int kv = a.kl + a.ku, H = a.kl + NB, ntile = (kv + BTC - 1) / BTC;
+    const size_t lds = sizeof(c128) * (size_t)w.lh * BTC;
+    // every call, for the device the call runs on: cheap beside the solve, and a refusal ends the solve here
+    hipError_t err = hipFuncSetAttribute((const void*)band_update_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    if (err == hipSuccess) err = hipMemsetAsync(w.ju, 0, sizeof(int) * G, st);
+    StepThrottle th;
+    if (err == hipSuccess) err = th.err;
+    int step = 0;
+    for (int j0 = 0; j0 < a.n && err == hipSuccess; j0 += NB, ++step) {
+        if ((err = th.before_step(step)) != hipSuccess) break;
+        if (H <= 256) hipLaunchKernelGGL((band_panel_kernel<256, 1, NB>), dim3(G), dim3(256), 0, st, a, w, j0);
+        else if (H <= 512) hipLaunchKernelGGL((band_panel_kernel<512, 1, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
+        else if (H <= 1024) hipLaunchKernelGGL((band_panel_kernel<512, 2, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
+        else hipLaunchKernelGGL((band_panel_kernel<512, 3, NB>), dim3(G), dim3(512), 0, st, a, w, j0);
+        hipLaunchKernelGGL(band_update_kernel<NB>, dim3(ntile + 1, G), dim3(256), lds, st, a, w, j0, ntile);
+        err = th.after_step(step, st);
+    }
+    return err == hipSuccess ? launch_back_blk(a, G, st, out, ldo, slots, perm) : err;
 }
 
 // The whole tiled (lwo == nullptr) or wide solve of G matrices on `st`.  w.lw is the tiled method's panel of L (wide: short
@@ -1052,8 +1052,7 @@ band_narrow_factor_kernel(BandArgs a)
             wave_argmax(best, bidx);
             int jp = __builtin_amdgcn_readfirstlane(bidx);
             if (jp == INT_MAX) jp = 0;
-            const c128 piv = cmake(lane_bcast(cand.x, jp), lane_bcast(cand.y, jp));
-            const c128 top = cmake(lane_bcast(cand.x, 0), lane_bcast(cand.y, 0));
+            const c128 piv = lane_bcast(cand, jp), top = lane_bcast(cand, 0);
             if (lane == (j & (NAR_CH - 1))) pv = j + jp + 1;            // LAPACK's 1-based row
             if (piv.x == 0.0 && piv.y == 0.0) {
                 if (info == 0) info = j + 1;
