@@ -27,6 +27,7 @@ SYMBOLS = [
     "maus_sparse_max_n", "maus_band_prepare", "maus_band_reserve", "maus_band_solve", "maus_band_lu_host", "maus_band_workspace_allocs",
     "maus_band_set_method", "maus_band_get_method", "maus_band_kernel_for", "maus_band_outer_nb", "maus_band_plan",
     "maus_gmres_set_method", "maus_gmres_get_method", "maus_gmres_kernel_for",
+    "maus_few_rows_set_method", "maus_few_rows_get_method", "maus_few_rows_kernel_for", "maus_few_rows_plan", "maus_few_rows_workspace_allocs",
     "maus_device_count", "maus_comm_unique_id", "maus_comm_init", "maus_comm_destroy", "maus_comm_info",
     "maus_comm_allgather_records", "maus_comm_allgather_rows", "maus_comm_bcast", "maus_comm_bcast_eigvecs", "maus_comm_set_matrix", "maus_comm_stats",
 ]
@@ -41,6 +42,7 @@ KC_NAMES = ["zgemm", "lu_panel", "trsm", "laswp", "build_h", "backsolve", "vecto
 BAND_COLUMN, BAND_BLOCKED, BAND_TILED, BAND_WIDE, BAND_NARROW = (      # maus_band_set_method: 0, 1, 2, 4, 8 (no 3, 5, 6, 7)
     DIRECT_METHOD[m] for m in ("band", "blocked", "tiled", "wide", "narrow"))
 GMRES_DEFAULT, GMRES_WIDE = 0, 1                     # maus_gmres_set_method
+FEW_ROWS_DEFAULT, FEW_ROWS_SPLITK = 0, 1             # maus_few_rows_set_method
 SPMM_SCHEDULES = {0: None, 1: "rows", 2: "wave"}     # maus_matrix_is_sparse: dense / lane per row / wave per row
 
 
@@ -142,6 +144,11 @@ def load_library():
         "maus_gmres_set_method": ([vp, C.c_int], C.c_int),
         "maus_gmres_get_method": ([vp], C.c_int),
         "maus_gmres_kernel_for": ([vp, C.c_int, C.c_int], C.c_int),
+        "maus_few_rows_set_method": ([vp, C.c_int, C.c_int], C.c_int),
+        "maus_few_rows_get_method": ([vp], C.c_int),
+        "maus_few_rows_kernel_for": ([vp] + [C.c_int] * 6 + [C.POINTER(C.c_int)], C.c_int),
+        "maus_few_rows_plan": ([C.c_int] * 8 + [C.POINTER(C.c_int)], C.c_int),
+        "maus_few_rows_workspace_allocs": ([vp], C.c_int),
         "maus_band_outer_nb": ([vp, C.c_int, C.c_int, C.c_int], C.c_int),
         "maus_band_plan": ([C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p, i32p, C.POINTER(C.c_int64)], C.c_int),
         "maus_device_count": ([], C.c_int),
@@ -670,6 +677,25 @@ class Context:
         self._ck(min(k, 0), "maus_gmres_kernel_for")
         return int(k)
 
+    def few_rows_set_method(self, method, slices=0):
+        """Dense population products of at most 32 rows (A X, A^H u, conj(X) V, Gram blocks): FEW_ROWS_DEFAULT, or FEW_ROWS_SPLITK
+        (K cut into slices over the whole device, joined in a fixed order; csrc/zgemm.hip).  `slices` 0: the library's rule;
+        1..32 force that many (tests, timing).  Kept across matrices."""
+        self._ck(self.lib.maus_few_rows_set_method(self.h, int(method), int(slices)), "maus_few_rows_set_method")
+
+    def few_rows_method(self) -> int:
+        return int(self.lib.maus_few_rows_get_method(self.h))
+
+    def few_rows_kernel_for(self, M, N, K, b_layout=1, conj_a=False, conj_b=False):
+        """(kernel, S) of an M x N x K product under the current method: (0, 1) the default kernels, (1, S) split-K."""
+        S = C.c_int()
+        k = self.lib.maus_few_rows_kernel_for(self.h, int(M), int(N), int(K), int(b_layout), int(bool(conj_a)), int(bool(conj_b)), C.byref(S))
+        self._ck(min(k, 0), "maus_few_rows_kernel_for")
+        return int(k), int(S.value)
+
+    def few_rows_workspace_allocs(self) -> int:
+        return int(self.lib.maus_few_rows_workspace_allocs(self.h))
+
     def band_lu(self, ab, b, kl, ku, method=None):
         """zgbtrf + zgbtrs on the device: ab[count, 2kl+ku+1, n] in LAPACK's band layout (SciPy's `ab`), b[count, n] ->
         (x[count, n], ipiv[count, n] 0-based as SciPy returns it, status[count]).  `method`: for this call only."""
@@ -775,6 +801,17 @@ def band_plan(method, n, kl, ku):
     if load_library().maus_band_plan(int(method), int(n), int(kl), int(ku), C.byref(kind), C.byref(nb), C.byref(nbo), C.byref(per)) != 0:
         raise MausHipError(f"maus_band_plan: bad method or sizes ({method}, {n}, {kl}, {ku})")
     return int(kind.value), int(nb.value), int(nbo.value), int(per.value)
+
+
+def few_rows_plan(method, slices, M, N, K, b_layout=1, conj_a=False, conj_b=False):
+    """(kernel, S) of an M x N x K population product under (method, slices) (maus_few_rows_plan): (0, 1) the default kernels,
+    (1, S) split-K.  Needs neither a context nor a device."""
+    S = C.c_int()
+    k = load_library().maus_few_rows_plan(int(method), int(slices), int(M), int(N), int(K), int(b_layout), int(bool(conj_a)),
+                                          int(bool(conj_b)), C.byref(S))
+    if k < 0:
+        raise MausHipError(f"maus_few_rows_plan: bad method, slices or sizes ({method}, {slices}, {M}, {N}, {K}, {b_layout})")
+    return int(k), int(S.value)
 
 
 def comm_unique_id() -> bytes:

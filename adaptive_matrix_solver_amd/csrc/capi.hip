@@ -261,7 +261,7 @@ int maus_ctx_destroy(maus_ctx* c) {
     (void)hipStreamSynchronize(c->st);
     (void)maus_comm_destroy(c);
     void* ptrs[] = {c->A, c->b, c->V, c->X, c->U, c->W, c->Y, c->d_slots, c->d_i1, c->d_i2, c->d_c1, c->d_c2, c->d_r1, c->d_r2,
-                    c->H, c->ipiv, c->perm, c->ident, c->mw_sync, c->info, c->flags, c->Upert, c->scratch, c->hq, c->htau, c->hz, c->S};
+                    c->H, c->ipiv, c->perm, c->ident, c->mw_sync, c->info, c->flags, c->Upert, c->scratch, c->hq, c->htau, c->hz, c->S, c->few_ws};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     maus_csr_free(c->Acsr); maus_csr_free(c->AHcsr);
     maus_band_drop(c);
@@ -627,15 +627,15 @@ int maus_hist_get(maus_ctx* c, const int64_t* indices, int count, int len, doubl
 }
 
 // Y[slot] = A @ X[slot] for all listed slots:  C[count, rows] = Xg[count, cols] * A^T  (A as [n][k])
-static void matvec_into_Y(maus_ctx* c, const c128* src, int count) {
+static int matvec_into_Y(maus_ctx* c, const c128* src, int count) {
     if (c->csr) {                                        // sparse matrix: the CSR product, same rows in and out (spmm.hip)
         ProfScope ps(c, KC_SPMM, 8.0 * count * c->Acsr.nnz, 12.0 * c->Acsr.nnz * ((count + 7) / 8) + 32.0 * count * c->rows);
         maus_spmm_launch(c->st, c->Acsr, c->csr_sched, src, c->ldp, c->Y, c->ldp, c->d_slots, c->d_slots, count);
-        return;
+        return 0;
     }
     ProfScope ps(c, KC_GEMM, 8.0 * count * c->rows * c->cols, 16.0 * ((double)c->rows * c->cols + 2.0 * count * c->ldp));
-    maus_zgemm_launch_idx(c->st, count, c->rows, c->cols, src, c->ldp, 0, c->A, c->cols, 0, c->Y, c->ldp, 0,
-                          1.0, 0, 1, /*blay*/1, false, false, c->d_slots, c->d_slots);
+    return maus_zgemm_launch_few(c, count, c->rows, c->cols, src, c->ldp, 0, c->A, c->cols, 0, c->Y, c->ldp, 0,
+                                 1.0, 0, 1, /*blay*/1, false, false, c->d_slots, c->d_slots);
 }
 
 // Y = A X for the rows of `slots` that do not hold it already (stamps: av_*).  The rows whose product an earlier call left in Y
@@ -645,12 +645,12 @@ static void matvec_into_Y(maus_ctx* c, const c128* src, int count) {
 static int matvec_missing_into_Y(maus_ctx* c, const int* slots, int count) {
     std::vector<int> need;
     for (int k = 0; k < count; ++k) if (!av_has(c, slots[k])) need.push_back(slots[k]);
-    if ((int)need.size() == count || !av_family(c, count, c->cols)) { matvec_into_Y(c, c->X, count); return 0; }
+    if ((int)need.size() == count || !av_family(c, count, c->cols)) { return matvec_into_Y(c, c->X, count); }
     if (need.empty()) return 0;
     for (int k = 0; k < count && need.size() < 33; ++k) if (av_has(c, slots[k])) need.push_back(slots[k]);
-    if (need.size() < 33) { matvec_into_Y(c, c->X, count); return 0; }      // (cannot happen with count > 32; kept for the invariant)
+    if (need.size() < 33) { return matvec_into_Y(c, c->X, count); }      // (cannot happen with count > 32; kept for the invariant)
     if (upload_slots(c, need.data(), (int)need.size())) return -1;
-    matvec_into_Y(c, c->X, (int)need.size());
+    if (matvec_into_Y(c, c->X, (int)need.size())) return -1;
     return upload_slots(c, slots, count);
 }
 
@@ -1064,7 +1064,7 @@ int maus_residual(maus_ctx* c, int kind, const int* slots, int count, const doub
         if (kind == MAUS_LINEAR && (!c->b || c->bn != c->rows)) FAIL(c, "maus_residual: rhs b not set");
         if (kind == MAUS_EIG && !lam) FAIL(c, "maus_residual: lambda missing");
         if (lam) { if (maus_h2d(c, c->d_c1, lam, sizeof(c128) * count, c->st)) return -1; }
-        matvec_into_Y(c, c->X, count);
+        if (matvec_into_Y(c, c->X, count)) return -1;
         { ProfScope ps(c, KC_VEC, 0, 32.0 * count * c->rows);
           maus_launch_residual(c->st, kind, c->X, c->Y, c->ldp, c->d_slots, count, c->rows, lam ? c->d_c1 : nullptr, c->b, c->d_r1, c->d_i1); }
         av_mark(c, slots, count);                        // Y = A X of these rows stands until somebody writes X or Y
@@ -1072,7 +1072,7 @@ int maus_residual(maus_ctx* c, int kind, const int* slots, int count, const doub
         if (!lam) FAIL(c, "maus_residual: sigma missing");
         if (maus_h2d(c, c->d_c1, lam, sizeof(c128) * count, c->st)) return -1;
         // ||A v - s u||  : Y = X * A^T  (count x rows)
-        matvec_into_Y(c, c->X, count);
+        if (matvec_into_Y(c, c->X, count)) return -1;
         maus_launch_svd_resid(c->st, c->Y, c->U, c->ldp, c->d_slots, count, c->rows, c->d_c1, c->d_r1, 0, c->d_i1);
         // ||A^H u - s v||: W = U * conj(A)  (count x cols), B = conj(A) as [k=rows][n=cols] -- or, when the power step of this
         // loop body has left exactly that product in S (same u, same kernel, same bits), no product at all (round 4)
@@ -1081,8 +1081,8 @@ int maus_residual(maus_ctx* c, int kind, const int* slots, int count, const doub
             maus_spmm_launch(c->st, c->AHcsr, c->csr_sched, c->U, c->ldp, c->W, c->ldp, c->d_slots, c->d_slots, count);
         } else if (!have_ahu) {
             ProfScope ps(c, KC_GEMM, 8.0 * count * c->rows * c->cols, 16.0 * (double)c->rows * c->cols);
-            maus_zgemm_launch_idx(c->st, count, c->cols, c->rows, c->U, c->ldp, 0, c->A, c->cols, 0, c->W, c->ldp, 0,
-                                  1.0, 0, 1, 0, false, true, c->d_slots, c->d_slots);
+            if (maus_zgemm_launch_few(c, count, c->cols, c->rows, c->U, c->ldp, 0, c->A, c->cols, 0, c->W, c->ldp, 0,
+                                      1.0, 0, 1, 0, false, true, c->d_slots, c->d_slots)) return -1;
         }
         maus_launch_svd_resid(c->st, have_ahu ? c->S : c->W, c->X, c->ldp, c->d_slots, count, c->cols, c->d_c1, c->d_r1, 1, c->d_i1);
         av_mark(c, slots, count);                        // Y = A X of these rows stands until somebody writes X or Y
@@ -1124,8 +1124,8 @@ int maus_svd_power_propose(maus_ctx* c, const int* slots, int count, double* nor
         maus_spmm_launch(c->st, c->AHcsr, c->csr_sched, c->Y, c->ldp, c->S, c->ldp, c->d_slots, c->d_slots, count);
     } else
     { ProfScope ps(c, KC_GEMM, 8.0 * count * c->rows * c->cols, 16.0 * (double)c->rows * c->cols);
-      maus_zgemm_launch_idx(c->st, count, c->cols, c->rows, c->Y, c->ldp, 0, c->A, c->cols, 0, c->S, c->ldp, 0,
-                            1.0, 0, 1, 0, false, true, c->d_slots, c->d_slots); }
+      if (maus_zgemm_launch_few(c, count, c->cols, c->rows, c->Y, c->ldp, 0, c->A, c->cols, 0, c->S, c->ldp, 0,
+                                1.0, 0, 1, 0, false, true, c->d_slots, c->d_slots)) return -1; }
     maus_launch_norm_scale(c->st, c->S, c->W, c->ldp, c->d_slots, count, c->cols, c->d_r1, 4, 3);
     if (++c->prop_epoch == 0) { c->prop_epoch = 1; std::fill(c->prop_stamp.begin(), c->prop_stamp.end(), 0u); }
     if (c->prop_stamp.size() < (size_t)c->cap) c->prop_stamp.resize(c->cap, 0u);
@@ -1164,7 +1164,7 @@ int maus_herm_match(maus_ctx* c, const int* slots, int count, int32_t* idx_out, 
     const int n = c->rows;
     // scores: Y[slot][j] = sum_i conj(X[slot][i]) V[i][j]
     { ProfScope ps(c, KC_GEMM, 8.0 * count * n * n, 16.0 * (double)n * n);
-      maus_zgemm_launch_idx(c->st, count, n, n, c->X, c->ldp, 0, c->V, n, 0, c->Y, c->ldp, 0, 1.0, 0, 1, 0, true, false, c->d_slots, c->d_slots); }
+      if (maus_zgemm_launch_few(c, count, n, n, c->X, c->ldp, 0, c->V, n, 0, c->Y, c->ldp, 0, 1.0, 0, 1, 0, true, false, c->d_slots, c->d_slots)) return -1; }
     maus_launch_herm_pick(c->st, c->Y, c->ldp, c->X, c->ldp, c->d_slots, count, c->V, n, c->d_i1, c->d_r1);
     if (maus_d2h(c, idx_out, c->d_i1, sizeof(int) * count, c->st)) return -1;
     if (maus_d2h(c, norm_out, c->d_r1, sizeof(double) * count, c->st)) return -1;
@@ -1187,7 +1187,7 @@ int maus_gram(maus_ctx* c, int which, const int* slots, int count, int len, doub
     c128* R = (c128*)c->scratch; c128* G = R + rows;
     hipLaunchKernelGGL(gather_rows_kernel, dim3(count), dim3(256), 0, c->st, X, c->ldp, c->d_slots, len, R);
     { ProfScope ps(c, KC_GEMM, 8.0 * count * count * len, 16.0 * (2.0 * rows + g));
-      maus_zgemm_launch_idx(c->st, count, count, len, R, len, 0, R, len, 0, G, count, 0, 1.0, 0, 1, 1, true, false, nullptr, nullptr); }
+      if (maus_zgemm_launch_few(c, count, count, len, R, len, 0, R, len, 0, G, count, 0, 1.0, 0, 1, 1, true, false, nullptr, nullptr)) return -1; }
     if (maus_stage_d2h(c, out_c128, G, sizeof(c128) * g, c->st)) return -1;
     HIPCHK(c, hipGetLastError());
     return 0;
@@ -1275,7 +1275,7 @@ int maus_zgemm_host(maus_ctx* c, int M, int N, int K, const double* A, const dou
     if (maus_stage_h2d(c, dA, A, sizeof(c128) * ea, c->st) || maus_stage_h2d(c, dB, B, sizeof(c128) * eb, c->st)
         || maus_stage_h2d(c, dC, C, sizeof(c128) * ec, c->st)) return -1;
     { ProfScope ps(c, KC_GEMM, 8.0 * M * N * K, 16.0 * (ea + eb + 2.0 * ec));
-      maus_zgemm_launch_idx(c->st, M, N, K, dA, K, 0, dB, b_layout ? K : N, 0, dC, N, 0, alpha, beta, 1, b_layout, conj_a != 0, conj_b != 0, nullptr, nullptr); }
+      if (maus_zgemm_launch_few(c, M, N, K, dA, K, 0, dB, b_layout ? K : N, 0, dC, N, 0, alpha, beta, 1, b_layout, conj_a != 0, conj_b != 0, nullptr, nullptr)) return -1; }
     if (maus_stage_d2h(c, C, dC, sizeof(c128) * ec, c->st)) return -1;
     HIPCHK(c, hipGetLastError());
     return 0;

@@ -31,6 +31,11 @@ void maus_zgemm_launch_idx(hipStream_t st, int M, int N, int K, const c128* A, l
                            const c128* B, long ldb, long sB, c128* C, long ldc, long sC,
                            double alpha, int beta, int batch, int blay, bool conja, bool conjb,
                            const int* a_rows, const int* c_rows);
+// zgemm.hip: the same product for the population products of capi.hip, split over K under maus_few_rows_set_method(ctx, 1)
+int maus_zgemm_launch_few(maus_ctx* c, int M, int N, int K, const c128* A, long lda, long sA,
+                          const c128* B, long ldb, long sB, c128* C, long ldc, long sC,
+                          double alpha, int beta, int batch, int blay, bool conja, bool conjb,
+                          const int* a_rows, const int* c_rows);
 void maus_launch_rayleigh_dots(hipStream_t st, const c128* X, const c128* Y, long ld, const int* slots, int count, int n, c128* num, c128* den);
 void maus_launch_relax(hipStream_t st, c128* X, const c128* W, long ld, const int* slots, int count, int n, const c128* alpha, int normalise, double* norm_out);
 void maus_launch_residual(hipStream_t st, int kind, const c128* X, const c128* Y, long ld, const int* slots, int count, int n,
@@ -81,6 +86,9 @@ struct maus_ctx {
     c128* band_lw = nullptr; int* band_ju = nullptr;    // the blocked / tiled / wide method's panel of L (wide: LW behind it) and reach, per solve of the workspace
     MausLanczos lz;
     int gmres_method = 0;                               // 0: one workgroup per candidate, 1: the wide step for CSR matrices (maus_gmres_set_method); kept across matrices
+    // dense population products of at most 32 rows (zgemm.hip, maus_few_rows_set_method): 0 the default kernels, 1 split-K with
+    // `few_slices` slices (0: the rule); the partial-sum slabs, grown on demand and never shrunk; kept across matrices
+    int few_method = 0, few_slices = 0; c128* few_ws = nullptr; size_t few_ws_elems = 0; int few_allocs = 0;
     c128* b = nullptr; int bn = 0;                  // rhs
     c128* V = nullptr; int vn = 0;                  // eigenvectors (Hermitian shortcut)
     c128* hq = nullptr; c128* htau = nullptr; int hqn = 0;   // Householder reflectors of maus_herm_tridiag, until the back-transformation (herm.hip)

@@ -22,7 +22,10 @@
 // accumulators (tools/probe_mfma_f64_v2; AGPR accumulators run at less than half of that),
 // but only if independent waves fill each other's waits: see the launcher for the measured
 // tile / occupancy choice.
-#include "common.h"
+//
+// Population products of at most 32 rows have a split-K form of the 4M kernel behind maus_few_rows_set_method(ctx, 1)
+// (zgemm_slice_kernel / zgemm_join_kernel and maus_zgemm_launch_few below); the default dispatch is unchanged.
+#include "ctx.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -631,6 +634,164 @@ void launch_lu_only(hipStream_t st, int M, int N, int K, const c128* A, long lda
                        M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, alpha, beta, tiles_n, nwg, a_rows, c_rows, rows_stride, tcol);
 }
 
+// ---------------------------------------------------------------------------------------
+// Split-K population products for at most 32 rows (maus_few_rows_set_method(ctx, 1); DESIGN §3 "Few rows").  The 4M kernels above
+// give a product of up to 32 rows ceil(N / 32) workgroups, each walking the whole K alone: M = 15 against 8192 x 8192 occupies
+// one workgroup per CU and reads the operand at a third of the copy rate; a Gram block of 32 rows is ONE workgroup.  Here K is
+// cut into S slices (few_slices below) and every (column tile, slice) is a workgroup of its own: the K-range form of the
+// register-staged 4M kernel -- same LDS images, same fragment reads, the same four real MFMA products per complex one, hence the
+// componentwise bound on the imaginary part -- on a BM x 64 tile, BM = 16 for up to 16 rows (no MFMA on padding rows) and 32
+// above.  An element's partial sum is one MFMA chain over its slice in k order whatever BM is, so a row's bits depend on neither.
+// Slice s of tile t writes its BM x 64 partial sums, all of them, to slab (s, t) of the context's workspace; zgemm_join_kernel,
+// the next launch on the same stream, adds the slabs of an element in the order 0, 1, .., S - 1 and applies the epilogue.  The
+// launch boundary is the only synchronisation: no counters, no flags, no atomics, nothing that waits.
+// ---------------------------------------------------------------------------------------
+constexpr int FEW_BN = 64, FEW_SLAB = 32 * FEW_BN;       // a slab holds 32 x 64 partial sums whatever BM is
+
+template <int BM, int BLAY, bool CONJA, bool CONJB>
+__global__ void __launch_bounds__(256, 4)
+zgemm_slice_kernel(int M, int N, int K, const c128* __restrict__ A, long lda, const c128* __restrict__ B, long ldb,
+                   c128* __restrict__ ws, int q, int r, const int* __restrict__ a_rows)
+{
+    constexpr int BN = FEW_BN, BK = 16, NT = 256, WN = 4;
+    constexpr int WTN = BN / WN, MB = BM / 16;       // 1 x 4 waves, BM x 16 per wave
+    constexpr int A_PER = BM * BK / NT, B_PER = BN * BK / NT;
+    static_assert(A_PER >= 1 && WTN == 16, "tile/threads mismatch");
+    __shared__ c128 smem[BK * BM + BK * BN];         // [k][m] then [k][n], XOR-swizzled as in zgemm_kernel
+    c128* As = smem;
+    c128* Bs = smem + BK * BM;
+
+    // slice s covers the 16-column chunks [s q + min(s, r), (s + 1) q + min(s + 1, r)); the last one also takes K % 16
+    const int s = blockIdx.y, S = gridDim.y, tn = blockIdx.x;
+    const int kb = 16 * (s * q + min(s, r));
+    const int ke = (s + 1 == S) ? K : 16 * ((s + 1) * q + min(s + 1, r));
+    const int n0 = tn * BN;
+    const int tid = threadIdx.x, lane = tid & 63, wn = tid >> 6;
+
+    d4 cre[MB], cim[MB];
+#pragma unroll
+    for (int i = 0; i < MB; ++i) { cre[i] = (d4){0, 0, 0, 0}; cim[i] = (d4){0, 0, 0, 0}; }
+
+    c128 ra[A_PER], rb[B_PER];
+    const bool KEDGE = ((ke - kb) % BK) != 0;
+    const c128* pa[A_PER];
+    const c128* pb[B_PER];
+#pragma unroll
+    for (int i = 0; i < A_PER; ++i) {
+        const int gm = min(tid / BK + i * (NT / BK), M - 1);
+        pa[i] = A + (long)(a_rows ? a_rows[gm] : gm) * lda;
+    }
+#pragma unroll
+    for (int i = 0; i < B_PER; ++i) {
+        if (BLAY == 0) pb[i] = B + (long)min(n0 + tid % BN, N - 1) + (long)(tid / BN + i * (NT / BN)) * ldb;
+        else pb[i] = B + (long)min(n0 + tid / BK + i * (NT / BK), N - 1) * ldb;
+    }
+    int kload = kb;
+    auto load_tiles = [&](int k0) {
+        kload = k0;
+        const int gk = k0 + (tid & (BK - 1));
+#pragma unroll
+        for (int i = 0; i < A_PER; ++i) ra[i] = pa[i][KEDGE ? min(gk, ke - 1) : gk];
+#pragma unroll
+        for (int i = 0; i < B_PER; ++i) {
+            if (BLAY == 0) {
+                const int kr = tid / BN + i * (NT / BN);
+                rb[i] = pb[i][(long)((KEDGE ? min(k0 + kr, ke - 1) : k0 + kr) - kr) * ldb];
+            } else rb[i] = pb[i][KEDGE ? min(gk, ke - 1) : gk];
+        }
+    };
+    auto store_tiles = [&]() {
+#pragma unroll
+        for (int i = 0; i < A_PER; ++i) {
+            const int k = tid & (BK - 1), m = tid / BK + i * (NT / BK);
+            c128 v = ra[i];
+            if (KEDGE && kload + k >= ke) v = cmake(0.0, 0.0);
+            if (CONJA) v.y = -v.y;
+            As[k * BM + (m ^ (k & 7))] = v;
+        }
+#pragma unroll
+        for (int i = 0; i < B_PER; ++i) {
+            const int k = BLAY == 0 ? tid / BN + i * (NT / BN) : (tid & (BK - 1));
+            const int n = BLAY == 0 ? tid % BN : tid / BK + i * (NT / BK);
+            c128 v = rb[i];
+            if (KEDGE && kload + k >= ke) v = cmake(0.0, 0.0);
+            if (CONJB) v.y = -v.y;
+            Bs[k * BN + (n ^ (k & 7))] = v;
+        }
+    };
+    c128 fa[2][MB], fb[2];
+    auto read_frags = [&](int kk, int slot) {
+        const int krow = kk * 4 + (lane >> 4);
+#pragma unroll
+        for (int i = 0; i < MB; ++i) fa[slot][i] = As[krow * BM + ((i * 16 + (lane & 15)) ^ (krow & 7))];
+        fb[slot] = Bs[krow * BN + ((wn * WTN + (lane & 15)) ^ (krow & 7))];
+    };
+
+    const int nkt = (ke - kb + BK - 1) / BK;
+    load_tiles(kb);
+    for (int kt = 0; kt < nkt; ++kt) {
+        __syncthreads();
+        store_tiles();
+        __syncthreads();
+        if (kt + 1 < nkt) load_tiles(kb + (kt + 1) * BK);
+        read_frags(0, 0);
+#pragma unroll
+        for (int kk = 0; kk < BK / 4; ++kk) {
+            if (kk + 1 < BK / 4) read_frags(kk + 1, (kk + 1) & 1);
+            const int sl = kk & 1;
+#pragma unroll
+            for (int i = 0; i < MB; ++i) {
+                cre[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[sl][i].x, fb[sl].x, cre[i], 0, 0, 0);
+                cim[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[sl][i].x, fb[sl].y, cim[i], 0, 0, 0);
+            }
+#pragma unroll
+            for (int i = 0; i < MB; ++i) {
+                cre[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[sl][i].y, fb[sl].y, cre[i], 0, 0, 1);   // BLGP = 1: Cre -= Aim Bim
+                cim[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[sl][i].y, fb[sl].x, cim[i], 0, 0, 0);
+            }
+        }
+    }
+
+    // the whole BM x 64 slab, padding rows and columns included (finite or not, the join reads only rows < M, columns < N)
+    c128* P = ws + ((size_t)s * gridDim.x + tn) * FEW_SLAB;
+#pragma unroll
+    for (int i = 0; i < MB; ++i)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr)
+            P[(i * 16 + (lane >> 4) + 4 * rr) * BN + wn * WTN + (lane & 15)] = cmake(cre[i][rr], cim[i][rr]);
+}
+
+// C[c_rows[m]][n] = alpha * (slab 0 + slab 1 + .. + slab S-1)[m][n] + (beta ? C : 0) for m < M, n < N: one thread per element
+__global__ void __launch_bounds__(256)
+zgemm_join_kernel(int M, int N, int S, int tiles_n, const c128* __restrict__ ws, c128* __restrict__ C, long ldc,
+                  double alpha, int beta, const int* __restrict__ c_rows)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x, m = blockIdx.y;
+    if (n >= N || m >= M) return;
+    const c128* p = ws + (size_t)(n / FEW_BN) * FEW_SLAB + m * FEW_BN + (n % FEW_BN);
+    const size_t step = (size_t)tiles_n * FEW_SLAB;
+    double vr = p[0].x, vi = p[0].y;
+    for (int s = 1; s < S; ++s) { const c128 t = p[s * step]; vr += t.x; vi += t.y; }
+    const long off = (long)(c_rows ? c_rows[m] : m) * ldc + n;
+    c128 cold = cmake(0.0, 0.0);
+    if (beta) cold = C[off];
+    C[off] = cmake(alpha * vr + cold.x, alpha * vi + cold.y);
+}
+
+// The slicing rule, stated once (maus_few_rows_plan / maus_few_rows_kernel_for report it; tests ask them).  S depends on
+// (N, K, layout) only -- never on M, the batch, the slots or the device -- so a candidate's row has the same bits alone and
+// among 32.  Aim: FEW_TARGET_WG workgroups over the ceil(N / 64) column tiles, no slice shorter than FEW_MIN_SLICE, at most 32
+// slices; constants from the sweep of tools/few_rows_rates.py (profiles/few_rows_rates.txt).  The layout does not enter yet.
+constexpr int FEW_TARGET_WG = 1024, FEW_MIN_SLICE = 256, FEW_MAX_S = 32;
+int few_rule(int N, int K, int /*blay*/)
+{
+    const int tiles = (N + FEW_BN - 1) / FEW_BN;
+    int S = FEW_TARGET_WG / tiles;
+    if (S > K / FEW_MIN_SLICE) S = K / FEW_MIN_SLICE;
+    if (S > FEW_MAX_S) S = FEW_MAX_S;
+    return S < 1 ? 1 : S;
+}
+
 // MAUS_LU_TILE=64x64|128x64 (read once per process): the workgroup tile of the large LU trailing updates, for timing one tile
 // against the other in one binary and for comparing their bits.  128x64: every update with M, N >= MAUS_LU_LT_MIN on the DMA
 // path, whatever its K; 64x64: the rule before the 128 x 64 tile (64 x 64 from 1536).  Unset: the rule of maus_zgemm_launch_lu.
@@ -762,3 +923,97 @@ void maus_zgemm_launch(hipStream_t st, int M, int N, int K, const c128* A, long 
 {
     maus_zgemm_launch_idx(st, M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, alpha, beta, batch, blay, conja, conjb, nullptr, nullptr);
 }
+
+// ---- few rows: the split-K method (kernels and rule above) ------------------------------------------------------------------
+// S of a product under (method, forced slices), 0 where the default kernels run.  Host arithmetic only.
+static int few_plan(int method, int forced, int M, int N, int K, int batch, int blay, bool conja, bool conjb)
+{
+    if (method != 1 || M < 1 || M > 32 || N < 1 || K < 1 || batch != 1) return 0;
+    if (blay == 0 && !conja && !conjb) return 0;             // plain products keep the LU family's kernels
+    int S = forced > 0 ? forced : few_rule(N, K, blay);
+    if (S > K / 16) S = K / 16;                              // no slice shorter than 16
+    return S >= 2 ? S : 0;
+}
+
+template <int BM, int BLAY, bool CONJA, bool CONJB>
+static void launch_slices(hipStream_t st, int M, int N, int K, const c128* A, long lda, const c128* B, long ldb, c128* ws,
+                          int tiles_n, int S, const int* a_rows)
+{
+    const int T = K / 16;
+    hipLaunchKernelGGL((zgemm_slice_kernel<BM, BLAY, CONJA, CONJB>), dim3(tiles_n, S), dim3(256), 0, st,
+                       M, N, K, A, lda, B, ldb, ws, T / S, T % S, a_rows);
+}
+
+// The population products of capi.hip go through here.  Split-K when the context's method is 1, M <= 32, batch = 1, the form
+// is a dot-product layout or a conjugated operand, and the rule gives S >= 2; maus_zgemm_launch_idx, unchanged, otherwise.
+// NOT routed here, on purpose: the GMRES products (gmres.hip pads them to 33 rows so that a candidate's iterate does not depend
+// on how many others are still active), every LU, band, sparse (c->csr) and Lanczos path, and maus_herm_match_rows.  The
+// kept-product stamps (capi.hip: av_family) are untouched: products of up to 32 rows leave none under either method.
+int maus_zgemm_launch_few(maus_ctx* c, int M, int N, int K, const c128* A, long lda, long sA,
+                          const c128* B, long ldb, long sB, c128* C, long ldc, long sC,
+                          double alpha, int beta, int batch, int blay, bool conja, bool conjb,
+                          const int* a_rows, const int* c_rows)
+{
+    const int S = few_plan(c->few_method, c->few_slices, M, N, K, batch, blay, conja, conjb);
+    if (S == 0) {
+        maus_zgemm_launch_idx(c->st, M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, alpha, beta, batch, blay, conja, conjb, a_rows, c_rows);
+        return 0;
+    }
+    // workspace: S slabs per column tile, sized from (S, N) alone -- never from ldp or the capacity, which a later
+    // maus_set_matrix / maus_pop_reserve may change.  Grown when a call needs more, never shrunk, freed with the context.
+    const int tiles_n = (N + FEW_BN - 1) / FEW_BN;
+    const size_t need = (size_t)S * tiles_n * FEW_SLAB;
+    if (need > c->few_ws_elems) {
+        HIPCHK(c, hipStreamSynchronize(c->st));              // an earlier join may still read the old one
+        if (c->few_ws) { (void)hipFree(c->few_ws); c->few_ws = nullptr; c->few_ws_elems = 0; }
+        HIPCHK(c, hipMalloc((void**)&c->few_ws, sizeof(c128) * need));
+        c->few_ws_elems = need;
+        ++c->few_allocs;
+    }
+#define SLICES(BL, CA, CB) do { if (M <= 16) launch_slices<16, BL, CA, CB>(c->st, M, N, K, A, lda, B, ldb, c->few_ws, tiles_n, S, a_rows); \
+                                else launch_slices<32, BL, CA, CB>(c->st, M, N, K, A, lda, B, ldb, c->few_ws, tiles_n, S, a_rows); } while (0)
+    if (blay == 0) {
+        if (conja && conjb) SLICES(0, true, true);
+        else if (conja) SLICES(0, true, false);
+        else SLICES(0, false, true);
+    } else {
+        if (conja && conjb) SLICES(1, true, true);
+        else if (conja) SLICES(1, true, false);
+        else if (conjb) SLICES(1, false, true);
+        else SLICES(1, false, false);
+    }
+#undef SLICES
+    hipLaunchKernelGGL(zgemm_join_kernel, dim3((N + 255) / 256, M), dim3(256), 0, c->st, M, N, S, tiles_n, c->few_ws, C, ldc, alpha, beta, c_rows);
+    return 0;
+}
+
+extern "C" {
+
+int maus_few_rows_set_method(maus_ctx* c, int method, int slices) {
+    if (!c) return -1;
+    if (method != 0 && method != 1) FAIL(c, "maus_few_rows_set_method: method must be 0 (default) or 1 (split-K)");
+    if (slices < 0 || slices > 32) FAIL(c, "maus_few_rows_set_method: slices must be 0 (the rule) or 1..32");
+    c->few_method = method;
+    c->few_slices = slices;
+    return 0;
+}
+
+int maus_few_rows_get_method(maus_ctx* c) { return c ? c->few_method : -1; }
+
+int maus_few_rows_plan(int method, int slices, int M, int N, int K, int b_layout, int conj_a, int conj_b, int* slices_out) {
+    if ((method != 0 && method != 1) || slices < 0 || slices > 32 || M < 1 || N < 1 || K < 1 || (b_layout != 0 && b_layout != 1)) return -1;
+    const int S = few_plan(method, slices, M, N, K, 1, b_layout, conj_a != 0, conj_b != 0);
+    if (slices_out) *slices_out = S ? S : 1;
+    return S ? 1 : 0;
+}
+
+int maus_few_rows_kernel_for(maus_ctx* c, int M, int N, int K, int b_layout, int conj_a, int conj_b, int* slices_out) {
+    if (!c) return -1;
+    const int k = maus_few_rows_plan(c->few_method, c->few_slices, M, N, K, b_layout, conj_a, conj_b, slices_out);
+    if (k < 0) FAIL(c, "maus_few_rows_kernel_for: bad sizes or layout");
+    return k;
+}
+
+int maus_few_rows_workspace_allocs(maus_ctx* c) { return c ? c->few_allocs : -1; }
+
+}  // extern "C"

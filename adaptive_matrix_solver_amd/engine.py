@@ -260,6 +260,17 @@ def sparse_gmres_mode(mode):
     return mode
 
 
+FEW_ROWS_MODES = ("auto", "splitk")
+
+
+def few_rows_mode(mode):
+    """The `few_rows` keyword: an explicit value, else MAUS_FEW_ROWS, else 'auto'."""
+    mode = mode if mode is not None else os.environ.get("MAUS_FEW_ROWS", "auto")
+    if mode not in FEW_ROWS_MODES:
+        raise ValueError(f"few_rows must be one of {FEW_ROWS_MODES}, not {mode!r}")
+    return mode
+
+
 SPARSE_EIGSH_MODES = ("auto", "dense", "lanczos")
 
 
@@ -360,7 +371,7 @@ class DeviceEngine:
 
     def __init__(self, device: int = 0, pert_mode: str = "auto", gmres_compat: str = "rtol",
                  comm=None, ctx=None, eigh_mode: str = "auto", sparse_mode=None, sparse_direct=None, sparse_eigsh=None,
-                 sparse_gmres=None):
+                 sparse_gmres=None, few_rows=None):
         self.ctx = ctx if ctx is not None else _cabi.Context(device)
         cap_blas_threads()
         # Hermitian eigendecomposition (AMS:161), once per matrix: 'host' = scipy.linalg.eigh, the reference's call, (lambda, V)
@@ -387,6 +398,12 @@ class DeviceEngine:
         # that a few candidates at large n occupy the whole device (opt-in, 'auto' never picks it; x agrees to rounding, not
         # bit for bit).  MAUS_SPARSE_GMRES sets the default.  Told to the context when a sparse matrix is bound.
         self.sparse_gmres = sparse_gmres_mode(sparse_gmres)
+        # dense population products of at most 32 candidates (DESIGN §3 "Few rows"): 'auto' = the kernels as ever, bit for
+        # bit; 'splitk' = K cut into slices over the whole device and joined in a fixed order (opt-in, 'auto' never picks it;
+        # agrees to rounding, not bit for bit).  MAUS_FEW_ROWS sets the default.  Told to the context here, once.
+        self.few_rows = few_rows_mode(few_rows)
+        if self.few_rows == "splitk":           # the only mode that touches the method: contexts without it keep working
+            self.ctx.few_rows_set_method(_cabi.FEW_ROWS_SPLITK)
         # sparse Hermitian shortcut (AMS:186-216): 'dense' = one scipy.linalg.eigh of A.toarray() per matrix, 'lanczos' =
         # thick-restart Lanczos on the CSR matrix on the device, 'auto' the first up to maus_lu_max_n() and the second above.
         # MAUS_SPARSE_EIGSH sets the default.

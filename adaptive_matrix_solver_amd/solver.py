@@ -32,7 +32,7 @@ from . import _cabi
 from ._cabi import POP_U, POP_X
 from .band import DIRECT_METHOD, band_bytes_per_solve, band_order
 from .candstore import C_NP as _C_NP, C_PY as _C_PY, EXACT as _EXACT, F_NP as _F_NP, F_PY as _F_PY, HREF as _HREF, MISSING as _MISSING
-from .engine import DIRECT, GMRES, DeviceEngine, _advance_numpy_stream, sparse_direct_mode, sparse_eigsh_mode, sparse_gmres_mode
+from .engine import DIRECT, GMRES, DeviceEngine, _advance_numpy_stream, few_rows_mode, sparse_direct_mode, sparse_eigsh_mode, sparse_gmres_mode
 
 
 class ProblemType(Enum):                     # AMS:10-13
@@ -161,7 +161,8 @@ class InverseIterateSolver:
     _engine = None          # private context: every call uploads its own A_target
 
     def __init__(self, N, base_psi_epsilon, max_attempts, preferred_method="direct_solve", is_sparse=False,
-                 gmres_compat="rtol", pert_mode="uniform", sparse_mode=None, sparse_direct=None, sparse_gmres=None):
+                 gmres_compat="rtol", pert_mode="uniform", sparse_mode=None, sparse_direct=None, sparse_gmres=None,
+                 few_rows=None):
         self.N = N
         self.base_psi_epsilon = base_psi_epsilon
         self.max_attempts = max_attempts
@@ -173,6 +174,7 @@ class InverseIterateSolver:
         self.sparse_mode = _sparse_mode(sparse_mode)
         self.sparse_direct = sparse_direct_mode(sparse_direct)
         self.sparse_gmres = sparse_gmres_mode(sparse_gmres)
+        self.few_rows = few_rows_mode(few_rows)
         self.last_trace = []
 
     @classmethod
@@ -187,6 +189,11 @@ class InverseIterateSolver:
             _reject_sparse("sparse matrices")
         ctx = self._ctx()
         n = self.N
+        # the context is shared by every InverseIterateSolver: each solve states the few-rows method ('splitk' is opt-in)
+        if self.few_rows == "splitk":
+            ctx.few_rows_set_method(_cabi.FEW_ROWS_SPLITK)
+        elif getattr(ctx, "few_rows_method", None) is not None and ctx.few_rows_method() != _cabi.FEW_ROWS_DEFAULT:
+            ctx.few_rows_set_method(_cabi.FEW_ROWS_DEFAULT)
         if sparse:
             # AMS:46-47, 55-56: H = A_target + psi*I, no random term; the direct solve densifies H on the device (spsolve's
             # NaNs on a singular H land in the same ValueError -> retry branch as the LU's info > 0)
@@ -764,7 +771,8 @@ class MAUS_Solver:
                  global_convergence_tol=1e-8, *, device=0, pert_mode="auto", gmres_compat="rtol",
                  record_history=None, comm=None, quiet=False, engine=None, gram_min=8, cond_exact_max=1024,
                  diag_info=None, eigh_mode="auto", sparse_mode=None, sparse_direct=None, sparse_eigsh=None,
-                 sparse_hermitian_check=None, sparse_gmres=None):
+                 sparse_hermitian_check=None, sparse_gmres=None, few_rows=None):
+        few_rows = few_rows_mode(few_rows)
         sparse_mode = _sparse_mode(sparse_mode)
         sparse_direct = sparse_direct_mode(sparse_direct)
         sparse_eigsh = sparse_eigsh_mode(sparse_eigsh)
@@ -792,7 +800,8 @@ class MAUS_Solver:
         self.engine = engine if engine is not None else DeviceEngine(device=device, pert_mode=pert_mode,
                                                                      gmres_compat=gmres_compat, comm=comm, eigh_mode=eigh_mode,
                                                                      sparse_mode=sparse_mode, sparse_direct=sparse_direct,
-                                                                     sparse_eigsh=sparse_eigsh, sparse_gmres=sparse_gmres)
+                                                                     sparse_eigsh=sparse_eigsh, sparse_gmres=sparse_gmres,
+                                                                     few_rows=few_rows)
         # `diag_info`: start-up diagnostics of the same matrix taken from an earlier solver (bench side runs)
         if diag_info is not None:
             self.diag_info = dict(diag_info)

@@ -377,6 +377,32 @@ int maus_gmres_pert(maus_ctx* ctx, const int* slots, int count, const double* sh
 int maus_gmres_set_method(maus_ctx* ctx, int method);
 int maus_gmres_get_method(maus_ctx* ctx);
 int maus_gmres_kernel_for(maus_ctx* ctx, int n, int csr);
+/* Dense population products of at most 32 rows: A X of the Rayleigh quotient and the residuals (AMS:264-268, 295-301), the
+ * score row conj(X) V of the Hermitian shortcut (AMS:165-175), the two products of the SVD power step (AMS:227-255) and the Gram
+ * block of the converged candidates (AMS:432-451).  By default such a product runs ceil(N / 32) workgroups, each walking the whole
+ * K alone; from 33 rows on other kernels fill the device.
+ *   maus_few_rows_set_method  0 (the default): those kernels, bit for bit.  1 (split-K): K is cut into S slices, every (column
+ *                          tile, slice) is a workgroup that writes its partial sums to a workspace of the context, and a second
+ *                          launch adds the slices of an element in the order 0 .. S - 1 and applies alpha / beta.  Same four real
+ *                          products per complex one, so the same componentwise bound, with other rounding than method 0; two runs
+ *                          give the same bits (no atomics, nothing waits).  S depends on (N, K, layout) only, so a candidate's
+ *                          row does not depend on how many others are multiplied with it.  `slices` 0: the library's rule;
+ *                          1..32: that many slices (tests, timing), reduced so that none is shorter than 16; 1 is the default
+ *                          kernels.  Applies to products with M <= 32 in dot-product layout or with a conjugated operand; plain
+ *                          products, 33 rows and more, CSR-bound matrices, the GMRES products (padded to 33 rows so that an
+ *                          iterate does not depend on the batch), the LU, band and Lanczos paths and maus_herm_match_rows never
+ *                          take it.  Kept across matrices.  Anything else than 0 / 1, or slices outside 0..32: an error.
+ *   maus_few_rows_get_method  the current method.
+ *   maus_few_rows_kernel_for  what an M x N x K product of that form runs under the current method: 0 the default kernels
+ *                          (slices_out = 1), 1 split-K with S in slices_out.  Host arithmetic, no launch.
+ *   maus_few_rows_plan     the same for a given (method, slices), without a context or a device; -1 for bad arguments.
+ *   maus_few_rows_workspace_allocs  how often the partial-sum workspace was (re)allocated: S * ceil(N / 64) * 32 * 64 complex
+ *                          numbers, sized from the call's (S, N) alone, grown on demand, never shrunk. */
+int maus_few_rows_set_method(maus_ctx* ctx, int method, int slices);
+int maus_few_rows_get_method(maus_ctx* ctx);
+int maus_few_rows_kernel_for(maus_ctx* ctx, int M, int N, int K, int b_layout, int conj_a, int conj_b, int* slices_out);
+int maus_few_rows_plan(int method, int slices, int M, int N, int K, int b_layout, int conj_a, int conj_b, int* slices_out);
+int maus_few_rows_workspace_allocs(maus_ctx* ctx);
 /* AMS:67-72 gate: ok[i]=1 iff all 1/diag(H_k) finite and all |diag(H_k)| > 1e-12 */
 int maus_jacobi_check(maus_ctx* ctx, int count, const double* shift_c128, const double* psi, int32_t* ok);
 
