@@ -28,6 +28,7 @@ SYMBOLS = [
     "maus_band_set_method", "maus_band_get_method", "maus_band_kernel_for", "maus_band_outer_nb", "maus_band_plan",
     "maus_gmres_set_method", "maus_gmres_get_method", "maus_gmres_kernel_for",
     "maus_few_rows_set_method", "maus_few_rows_get_method", "maus_few_rows_kernel_for", "maus_few_rows_plan", "maus_few_rows_workspace_allocs",
+    "maus_spmm_set_method", "maus_spmm_get_method", "maus_spmm_kernel_for", "maus_spmm_plan", "maus_spmm_sell_info",
     "maus_device_count", "maus_comm_unique_id", "maus_comm_init", "maus_comm_destroy", "maus_comm_info",
     "maus_comm_allgather_records", "maus_comm_allgather_rows", "maus_comm_bcast", "maus_comm_bcast_eigvecs", "maus_comm_set_matrix", "maus_comm_stats",
 ]
@@ -44,6 +45,8 @@ BAND_COLUMN, BAND_BLOCKED, BAND_TILED, BAND_WIDE, BAND_NARROW = (      # maus_ba
 GMRES_DEFAULT, GMRES_WIDE = 0, 1                     # maus_gmres_set_method
 FEW_ROWS_DEFAULT, FEW_ROWS_SPLITK = 0, 1             # maus_few_rows_set_method
 SPMM_SCHEDULES = {0: None, 1: "rows", 2: "wave"}     # maus_matrix_is_sparse: dense / lane per row / wave per row
+SPMM_CSR, SPMM_SELL = 0, 1                           # maus_spmm_set_method
+SPMM_KERNEL_NONE, SPMM_KERNEL_ROWS, SPMM_KERNEL_WAVE, SPMM_KERNEL_SELL = 0, 1, 2, 3   # maus_spmm_kernel_for / maus_spmm_plan
 
 
 
@@ -149,6 +152,11 @@ def load_library():
         "maus_few_rows_kernel_for": ([vp] + [C.c_int] * 6 + [C.POINTER(C.c_int)], C.c_int),
         "maus_few_rows_plan": ([C.c_int] * 8 + [C.POINTER(C.c_int)], C.c_int),
         "maus_few_rows_workspace_allocs": ([vp], C.c_int),
+        "maus_spmm_set_method": ([vp, C.c_int, C.c_int], C.c_int),
+        "maus_spmm_get_method": ([vp], C.c_int),
+        "maus_spmm_kernel_for": ([vp, C.c_int], C.c_int),
+        "maus_spmm_plan": ([C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, ip], C.c_int),
+        "maus_spmm_sell_info": ([vp, C.c_int, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
         "maus_band_outer_nb": ([vp, C.c_int, C.c_int, C.c_int], C.c_int),
         "maus_band_plan": ([C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p, i32p, C.POINTER(C.c_int64)], C.c_int),
         "maus_device_count": ([], C.c_int),
@@ -696,6 +704,29 @@ class Context:
     def few_rows_workspace_allocs(self) -> int:
         return int(self.lib.maus_few_rows_workspace_allocs(self.h))
 
+    def spmm_set_method(self, method, fill_cap_percent=0):
+        """Products with a CSR-bound matrix: SPMM_CSR (the default), or SPMM_SELL (the lane-per-row kernel on a sliced-ELL copy of
+        every operand whose padded size stays within `fill_cap_percent` of nnz; the CSR kernel's bits; csrc/spmm.hip).
+        `fill_cap_percent` 0: the library's 200; 100..1000000 for tests and timing.  Kept across matrices; with a CSR matrix
+        bound the copies are built or freed at once."""
+        self._ck(self.lib.maus_spmm_set_method(self.h, int(method), int(fill_cap_percent)), "maus_spmm_set_method")
+
+    def spmm_method(self) -> int:
+        return int(self.lib.maus_spmm_get_method(self.h))
+
+    def spmm_kernel_for(self, adjoint=False) -> int:
+        """What a product with the bound matrix (adjoint: with A^H) runs under the current method: SPMM_KERNEL_NONE (no CSR
+        matrix), SPMM_KERNEL_ROWS, SPMM_KERNEL_WAVE or SPMM_KERNEL_SELL."""
+        k = self.lib.maus_spmm_kernel_for(self.h, int(bool(adjoint)))
+        self._ck(min(k, 0), "maus_spmm_kernel_for")
+        return int(k)
+
+    def spmm_sell_info(self, adjoint=False):
+        """(slices, padded slots, bytes) of the resident sliced-ELL copy of A (adjoint: of A^H); zeros without one."""
+        ns, padded, by = C.c_int(), C.c_int64(), C.c_int64()
+        self._ck(self.lib.maus_spmm_sell_info(self.h, int(bool(adjoint)), C.byref(ns), C.byref(padded), C.byref(by)), "maus_spmm_sell_info")
+        return int(ns.value), int(padded.value), int(by.value)
+
     def band_lu(self, ab, b, kl, ku, method=None):
         """zgbtrf + zgbtrs on the device: ab[count, 2kl+ku+1, n] in LAPACK's band layout (SciPy's `ab`), b[count, n] ->
         (x[count, n], ipiv[count, n] 0-based as SciPy returns it, status[count]).  `method`: for this call only."""
@@ -812,6 +843,15 @@ def few_rows_plan(method, slices, M, N, K, b_layout=1, conj_a=False, conj_b=Fals
     if k < 0:
         raise MausHipError(f"maus_few_rows_plan: bad method, slices or sizes ({method}, {slices}, {M}, {N}, {K}, {b_layout})")
     return int(k), int(S.value)
+
+
+def spmm_plan(method, fill_cap_percent, rows, nnz, padded) -> int:
+    """The kernel of an operand with `rows` rows, nnz entries and `padded` sliced-ELL slots under (method, fill_cap_percent)
+    (maus_spmm_plan): SPMM_KERNEL_ROWS, SPMM_KERNEL_WAVE or SPMM_KERNEL_SELL.  Needs neither a context nor a device."""
+    kind = C.c_int()
+    if load_library().maus_spmm_plan(int(method), int(fill_cap_percent), int(rows), int(nnz), int(padded), C.byref(kind)) != 0:
+        raise MausHipError(f"maus_spmm_plan: bad method, cap or sizes ({method}, {fill_cap_percent}, {rows}, {nnz}, {padded})")
+    return int(kind.value)
 
 
 def comm_unique_id() -> bytes:

@@ -629,7 +629,7 @@ int maus_hist_get(maus_ctx* c, const int64_t* indices, int count, int len, doubl
 // Y[slot] = A @ X[slot] for all listed slots:  C[count, rows] = Xg[count, cols] * A^T  (A as [n][k])
 static int matvec_into_Y(maus_ctx* c, const c128* src, int count) {
     if (c->csr) {                                        // sparse matrix: the CSR product, same rows in and out (spmm.hip)
-        ProfScope ps(c, KC_SPMM, 8.0 * count * c->Acsr.nnz, 12.0 * c->Acsr.nnz * ((count + 7) / 8) + 32.0 * count * c->rows);
+        ProfScope ps(c, KC_SPMM, 8.0 * count * c->Acsr.nnz, maus_spmm_operand_bytes(c->Acsr) * ((count + 7) / 8) + 32.0 * count * c->rows);
         maus_spmm_launch(c->st, c->Acsr, c->csr_sched, src, c->ldp, c->Y, c->ldp, c->d_slots, c->d_slots, count);
         return 0;
     }
@@ -1077,7 +1077,7 @@ int maus_residual(maus_ctx* c, int kind, const int* slots, int count, const doub
         // ||A^H u - s v||: W = U * conj(A)  (count x cols), B = conj(A) as [k=rows][n=cols] -- or, when the power step of this
         // loop body has left exactly that product in S (same u, same kernel, same bits), no product at all (round 4)
         if (!have_ahu && c->csr) {
-            ProfScope ps(c, KC_SPMM, 8.0 * count * c->AHcsr.nnz, 12.0 * c->AHcsr.nnz * ((count + 7) / 8) + 32.0 * count * c->cols);
+            ProfScope ps(c, KC_SPMM, 8.0 * count * c->AHcsr.nnz, maus_spmm_operand_bytes(c->AHcsr) * ((count + 7) / 8) + 32.0 * count * c->cols);
             maus_spmm_launch(c->st, c->AHcsr, c->csr_sched, c->U, c->ldp, c->W, c->ldp, c->d_slots, c->d_slots, count);
         } else if (!have_ahu) {
             ProfScope ps(c, KC_GEMM, 8.0 * count * c->rows * c->cols, 16.0 * (double)c->rows * c->cols);
@@ -1120,7 +1120,7 @@ int maus_svd_power_propose(maus_ctx* c, const int* slots, int count, double* nor
         c->Scap = c->cap;
     }
     if (c->csr) {
-        ProfScope ps(c, KC_SPMM, 8.0 * count * c->AHcsr.nnz, 12.0 * c->AHcsr.nnz * ((count + 7) / 8) + 32.0 * count * c->cols);
+        ProfScope ps(c, KC_SPMM, 8.0 * count * c->AHcsr.nnz, maus_spmm_operand_bytes(c->AHcsr) * ((count + 7) / 8) + 32.0 * count * c->cols);
         maus_spmm_launch(c->st, c->AHcsr, c->csr_sched, c->Y, c->ldp, c->S, c->ldp, c->d_slots, c->d_slots, count);
     } else
     { ProfScope ps(c, KC_GEMM, 8.0 * count * c->rows * c->cols, 16.0 * (double)c->rows * c->cols);

@@ -48,6 +48,9 @@ void maus_launch_herm_pick(hipStream_t st, const c128* S, long lds_, c128* X, lo
 enum { MAUS_SPMM_ROWS = 1, MAUS_SPMM_WAVE = 2 };     // SpMM schedules: a lane per row / a wave per row
 void maus_spmm_launch(hipStream_t st, const MausCsr& m, int sched, const c128* B, long ldb, c128* C, long ldc,
                       const int* a_rows, const int* c_rows, int count);
+// operand bytes of one pass over a sparse operand, for the profiling counters: the sliced-ELL copy streams 20 bytes per padded
+// slot where it is resident; the CSR kernels are accounted as ever
+inline double maus_spmm_operand_bytes(const MausCsr& m) { return m.sell.val ? 20.0 * m.sell.padded : 12.0 * m.nnz; }
 void maus_csr_diag_launch(hipStream_t st, const MausCsr& m, int n, c128* d);
 void maus_csr_free(MausCsr& m);
 void maus_build_h_csr(const LuWs& w, const MausCsr& A, const c128* d_shift, const double* d_psi, int rhs_mode,
@@ -77,6 +80,9 @@ struct maus_ctx {
     c128* A = nullptr; int rows = 0, cols = 0;      // problem matrix
     // sparse problem matrix (maus_set_matrix_csr): A and A^H in CSR, the diagonal of A, the SpMM schedule; A stays null
     bool csr = false; MausCsr Acsr, AHcsr; c128* Adiag = nullptr; int csr_sched = 0;
+    // SpMM method (maus_spmm_set_method): 0 the CSR kernels, 1 the sliced-ELL copy (Acsr.sell / AHcsr.sell) for every operand
+    // of the lane-per-row schedule whose padded size stays within spmm_fill_cap percent of nnz (0: 200); kept across matrices
+    int spmm_method = 0, spmm_fill_cap = 0;
     // band solves of a sparse matrix (band.hip): the ordering of maus_band_prepare, the half-bandwidths of A[perm][:, perm], and
     // the batched band workspace (maus_band_reserve); dropped with the CSR operands
     int* band_perm = nullptr; int* band_iperm = nullptr; int band_n = 0, band_kl = -1, band_ku = -1;

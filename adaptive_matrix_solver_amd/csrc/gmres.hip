@@ -1074,7 +1074,7 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
         if (h_nact <= 0) break;
         const int maxcol = h[1], n1 = h[2], n0 = h_nact - n1;
         if (maxcol >= R || (n0 > 0) != (maxcol >= 0)) FAIL(c, "maus_gmres: inconsistent tick summary of the wide step");
-        { ProfScope ps(c, KC_SPMM, 8.0 * h_nact * c->Acsr.nnz, 12.0 * c->Acsr.nnz * ((h_nact + 7) / 8) + 32.0 * h_nact * n);
+        { ProfScope ps(c, KC_SPMM, 8.0 * h_nact * c->Acsr.nnz, maus_spmm_operand_bytes(c->Acsr) * ((h_nact + 7) / 8) + 32.0 * h_nact * n);
           maus_spmm_launch(c->st, c->Acsr, c->csr_sched, a.Vb, n, a.Y, n, zrow, act, h_nact); }
         // bytes: form 64 n per candidate; a Gram-Schmidt column 64 n (w in and out, V[kk - 1], V[kk]), the tail 48 n; finish 32 n;
         // a new cycle 64 n (x += y @ V of the candidates whose inner loop ends is not counted)
@@ -1101,7 +1101,7 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
         if (c->csr) {
             // sparse matrix: every active candidate's product through the CSR operand (rows do not depend on the batch, so the
             // shared first product A x0 of rhs_mode 1 needs no special case)
-            ProfScope ps(c, KC_SPMM, 8.0 * h_nact * c->Acsr.nnz, 12.0 * c->Acsr.nnz * ((h_nact + 7) / 8) + 32.0 * h_nact * n);
+            ProfScope ps(c, KC_SPMM, 8.0 * h_nact * c->Acsr.nnz, maus_spmm_operand_bytes(c->Acsr) * ((h_nact + 7) / 8) + 32.0 * h_nact * n);
             maus_spmm_launch(c->st, c->Acsr, c->csr_sched, a.Vb, n, a.Y, n, zrow, act, h_nact);
         } else
         if (Hdense) {

@@ -307,7 +307,7 @@ int maus_lanczos_extend(maus_ctx* c, int j0, int j1, double tol_abs, double* alp
     if (j0 < 0 || j0 >= j1 || j1 > z.ncv || !alpha_out || !beta_out || !(tol_abs >= 0.0)) FAIL(c, "maus_lanczos_extend: bad arguments");
     const int n = z.n;
     for (int j = j0; j < j1; ++j) {
-        { ProfScope ps(c, KC_SPMM, 8.0 * c->Acsr.nnz, 12.0 * c->Acsr.nnz + 32.0 * n);
+        { ProfScope ps(c, KC_SPMM, 8.0 * c->Acsr.nnz, maus_spmm_operand_bytes(c->Acsr) + 32.0 * n);
           maus_spmm_launch(c->st, c->Acsr, c->csr_sched, z.B, (long)n, z.B, (long)n, z.ident + j, z.ident + j + 1, 1); }
         lz_orthonormalise(c, z.B, j + 1, j + 1, j, tol_abs);
     }

@@ -12,6 +12,10 @@
 // in which order they are gathered never enters the arithmetic, so a row's product is bit-identical alone, among 33 rows or
 // among 256 -- what the kept-product stamps of capi.hip (av_*, ahu_*) rely on.  The schedule is chosen once per matrix from
 // nnz / rows (csr_schedule) and reported by maus_matrix_is_sparse.
+//
+// Under maus_spmm_set_method(ctx, 1) an operand of the short-row schedule is also kept in sliced-ELL form (MausSell, built on the
+// device at bind time) and spmm_sell_kernel reads that copy: the same lane per row, the same operations in the same order, the
+// same bits, with coalesced operand loads and several nonzeros' gathers in flight.  spmm_kind states which operand takes it.
 #include "ctx.h"
 
 namespace {
@@ -47,6 +51,122 @@ spmm_rows_kernel(const int* __restrict__ ptr, const int* __restrict__ idx, const
 #pragma unroll
     for (int g = 0; g < SP_CG; ++g)
         if (g < ng) C[(long)c_rows[k0 + g] * ldc + i] = acc[g];
+}
+
+// The lane-per-row product on the sliced-ELL copy of the operand (MausSell, maus_spmm_set_method(ctx, 1); DESIGN §10 "SpMM on a
+// sliced-ELL copy").  Geometry and index lists are those of spmm_rows_kernel.  Entry p of the 64 rows of a slice is one
+// contiguous run of 64 indices (256 B) and 64 values (1 KB), so a wave's operand load touches 4 + 16 cache lines where the CSR
+// walk touches up to 64 + 64, and the loads of U consecutive entries and their U x ng gathers are issued before the first
+// product needs them.  A lane adds the entries of its own row for p ascending, with cfma, onto a zero accumulator: the CSR
+// kernel's operations in the CSR kernel's order, so the same bits.  A lane stops at its own length; lanes of a wave that are
+// done sit out the rest of the wave's loop, and padding is neither loaded nor multiplied.
+// The three constants can be set from the command line (make EXTRA=-DMAUS_SELL_U=2 ...) for the side-by-side builds of
+// profiles/spmm_sell_variants.txt; the bits do not depend on them.
+#ifndef MAUS_SELL_U
+#define MAUS_SELL_U 4
+#endif
+#ifndef MAUS_SELL_U1
+#define MAUS_SELL_U1 8
+#endif
+#ifndef MAUS_SELL_G1
+#define MAUS_SELL_G1 1
+#endif
+constexpr int SELL_U = MAUS_SELL_U;     // entries in flight per lane, groups of 8 candidates (4: 189 VGPRs, 2 waves per SIMD)
+constexpr int SELL_U_SHORT = 2;         // the same where no row has SELL_U entries (117 VGPRs, 4 waves per SIMD)
+constexpr int SELL_U1 = MAUS_SELL_U1;   // the same for a lone candidate: Lanczos, one row of a population (8: 62 VGPRs, 8 waves per SIMD)
+constexpr bool SELL_G1 = MAUS_SELL_G1;  // a lone candidate runs the instantiation with a group of 1
+
+// W consecutive entries of the lane's row from entry p on: W index / value loads, then W x ng gathers, then the products for
+// p ascending
+template <int CG, int W>
+__device__ __forceinline__ void sell_chunk(c128 (&acc)[CG], const c128* const (&b)[CG], int ng,
+                                           const int* __restrict__ ji, const c128* __restrict__ av, int p)
+{
+    int j[W];
+    c128 a[W], x[W][CG];
+#pragma unroll
+    for (int u = 0; u < W; ++u) {
+        j[u] = ji[(long)(p + u) * MAUS_WAVE];
+        a[u] = av[(long)(p + u) * MAUS_WAVE];
+    }
+#pragma unroll
+    for (int u = 0; u < W; ++u)
+#pragma unroll
+        for (int g = 0; g < CG; ++g)
+            if (g < ng) x[u][g] = b[g][j[u]];
+#pragma unroll
+    for (int u = 0; u < W; ++u)
+#pragma unroll
+        for (int g = 0; g < CG; ++g)
+            if (g < ng) cfma(acc[g], a[u], x[u][g]);
+}
+
+template <int CG, int U>
+__global__ void __launch_bounds__(SP_BT)
+spmm_sell_kernel(const long* __restrict__ off, const int* __restrict__ len, const int* __restrict__ idx, const c128* __restrict__ val,
+                 int nrows, const c128* __restrict__ B, long ldb, c128* __restrict__ C, long ldc,
+                 const int* __restrict__ a_rows, const int* __restrict__ c_rows, int count)
+{
+    const int i = blockIdx.x * SP_BT + threadIdx.x;
+    const int k0 = blockIdx.y * CG;
+    if (i >= nrows) return;
+    const int ng = min(CG, count - k0);
+    const c128* b[CG];
+    c128 acc[CG];
+#pragma unroll
+    for (int g = 0; g < CG; ++g) {
+        b[g] = B + (long)a_rows[k0 + (g < ng ? g : 0)] * ldb;
+        acc[g] = cmake(0.0, 0.0);
+    }
+    const long base = off[i / MAUS_WAVE] + (i % MAUS_WAVE);
+    const int* __restrict__ ji = idx + base;
+    const c128* __restrict__ av = val + base;
+    const int n = len[i];
+    int p = 0;
+    for (; p + U <= n; p += U) sell_chunk<CG, U>(acc, b, ng, ji, av, p);
+    // the row's last n % U entries, in chunks of 4, 2, 1: still p ascending
+    if constexpr (U > 4) if (p + 4 <= n) { sell_chunk<CG, 4>(acc, b, ng, ji, av, p); p += 4; }
+    if constexpr (U > 2) if (p + 2 <= n) { sell_chunk<CG, 2>(acc, b, ng, ji, av, p); p += 2; }
+    if (p < n) sell_chunk<CG, 1>(acc, b, ng, ji, av, p);
+#pragma unroll
+    for (int g = 0; g < CG; ++g)
+        if (g < ng) C[(long)c_rows[k0 + g] * ldc + i] = acc[g];
+}
+
+// Build of the sliced-ELL copy, step 1: len[r] of every row and, per slice (one wave), the longest of its 64 rows; rows past
+// the end of the matrix count as empty
+__global__ void __launch_bounds__(SP_BT)
+sell_width_kernel(const int* __restrict__ ptr, int nrows, int nslices, int* __restrict__ len, int* __restrict__ width)
+{
+    const int r = blockIdx.x * SP_BT + threadIdx.x;
+    int w = 0;
+    if (r < nrows) { w = ptr[r + 1] - ptr[r]; len[r] = w; }
+#pragma unroll
+    for (int o = MAUS_WAVE / 2; o > 0; o >>= 1) w = max(w, __shfl_xor(w, o, MAUS_WAVE));
+    if (r % MAUS_WAVE == 0 && r / MAUS_WAVE < nslices) width[r / MAUS_WAVE] = w;
+}
+
+// step 3 (step 2, the exclusive scan of 64 w_s into off, runs on the host): a thread per row copies its entries in CSR order and
+// writes the rest of its lane of the slice as (index 0, value 0); one writer per slot, no atomics
+__global__ void __launch_bounds__(SP_BT)
+sell_fill_kernel(const int* __restrict__ ptr, const int* __restrict__ idx, const c128* __restrict__ val, int nrows, int nslices,
+                 const long* __restrict__ off, int* __restrict__ sidx, c128* __restrict__ sval)
+{
+    const int r = blockIdx.x * SP_BT + threadIdx.x;
+    const int s = r / MAUS_WAVE;
+    if (s >= nslices) return;
+    const long base = off[s] + (r % MAUS_WAVE);
+    const int w = (int)((off[s + 1] - off[s]) / MAUS_WAVE);
+    const int p0 = r < nrows ? ptr[r] : 0;
+    const int n = r < nrows ? ptr[r + 1] - p0 : 0;
+    for (int p = 0; p < n; ++p) {
+        sidx[base + (long)p * MAUS_WAVE] = idx[p0 + p];
+        sval[base + (long)p * MAUS_WAVE] = val[p0 + p];
+    }
+    for (int p = n; p < w; ++p) {
+        sidx[base + (long)p * MAUS_WAVE] = 0;
+        sval[base + (long)p * MAUS_WAVE] = cmake(0.0, 0.0);
+    }
 }
 
 // long rows: one wave per row, lanes over the row's nonzeros, the partial sums joined by a fixed tree
@@ -101,7 +221,18 @@ void maus_spmm_launch(hipStream_t st, const MausCsr& m, int sched, const c128* B
                       const int* a_rows, const int* c_rows, int count) {
     if (count <= 0 || m.rows <= 0) return;
     const int groups = (count + SP_CG - 1) / SP_CG;
-    if (sched == MAUS_SPMM_WAVE)
+    const MausSell& s = m.sell;
+    const dim3 rows_grid((m.rows + SP_BT - 1) / SP_BT, groups);
+    if (SELL_G1 && s.val && count == 1)                 // the copy exists only under the lane-per-row schedule of the matrix (spmm_kind)
+        hipLaunchKernelGGL((spmm_sell_kernel<1, SELL_U1>), rows_grid, dim3(SP_BT), 0, st,
+                           s.off, s.len, s.idx, s.val, m.rows, B, ldb, C, ldc, a_rows, c_rows, count);
+    else if (s.val && s.wmax < SELL_U)
+        hipLaunchKernelGGL((spmm_sell_kernel<SP_CG, SELL_U_SHORT>), rows_grid, dim3(SP_BT), 0, st,
+                           s.off, s.len, s.idx, s.val, m.rows, B, ldb, C, ldc, a_rows, c_rows, count);
+    else if (s.val)
+        hipLaunchKernelGGL((spmm_sell_kernel<SP_CG, SELL_U>), rows_grid, dim3(SP_BT), 0, st,
+                           s.off, s.len, s.idx, s.val, m.rows, B, ldb, C, ldc, a_rows, c_rows, count);
+    else if (sched == MAUS_SPMM_WAVE)
         hipLaunchKernelGGL(spmm_wave_kernel, dim3((m.rows + SP_BT / MAUS_WAVE - 1) / (SP_BT / MAUS_WAVE), groups), dim3(SP_BT), 0, st,
                            m.ptr, m.idx, m.val, m.rows, B, ldb, C, ldc, a_rows, c_rows, count);
     else
@@ -113,7 +244,16 @@ void maus_csr_diag_launch(hipStream_t st, const MausCsr& m, int n, c128* d) {
     hipLaunchKernelGGL(csr_diag_kernel, dim3((n + SP_BT - 1) / SP_BT), dim3(SP_BT), 0, st, m.ptr, m.idx, m.val, n, d);
 }
 
+static void sell_free(MausSell& s) {
+    if (s.val) (void)hipFree(s.val);
+    if (s.idx) (void)hipFree(s.idx);
+    if (s.len) (void)hipFree(s.len);
+    if (s.off) (void)hipFree(s.off);
+    s = MausSell();
+}
+
 void maus_csr_free(MausCsr& m) {
+    sell_free(m.sell);
     if (m.ptr) (void)hipFree(m.ptr);
     if (m.idx) (void)hipFree(m.idx);
     if (m.val) (void)hipFree(m.val);
@@ -122,6 +262,57 @@ void maus_csr_free(MausCsr& m) {
 
 // nnz / rows above 32: a lane per row would walk a long row alone while its wave's other lanes wait on theirs
 static int csr_schedule(int rows, long nnz) { return nnz > 32L * rows ? MAUS_SPMM_WAVE : MAUS_SPMM_ROWS; }
+
+// Which kernel an operand runs, stated once (maus_spmm_plan / maus_spmm_kernel_for report it; tests ask them).  `sched` is the
+// schedule of the bound MATRIX, from nnz and the rows of A: the CSR kernels run A and A^H under that one schedule, so it, and
+// not the operand's own nnz / rows, decides whether the sliced-ELL kernel would give the CSR kernel's bits.  Under method 1 an
+// operand of a lane-per-row matrix that stores something and whose padded size stays within the cap takes the copy.  The cap
+// bounds memory (20 bytes per padded slot); it is not a tuned number.
+constexpr int SELL_FILL_CAP = 200, SELL_CAP_MIN = 100, SELL_CAP_MAX = 1000000;
+enum { MAUS_SPMM_SELL = 3 };
+static bool spmm_setting_ok(int method, int cap) {
+    return (method == 0 || method == 1) && (cap == 0 || (cap >= SELL_CAP_MIN && cap <= SELL_CAP_MAX));
+}
+static int spmm_kind(int method, int cap, int sched, long nnz, long padded) {
+    if (method != 1 || sched != MAUS_SPMM_ROWS || nnz <= 0) return sched;
+    // padded <= 64 * cols * slices < 2^53 and cap * nnz < 2^51: exact in double
+    return 100.0 * (double)padded <= (double)(cap ? cap : SELL_FILL_CAP) * (double)nnz ? MAUS_SPMM_SELL : sched;
+}
+
+// The sliced-ELL copy of one bound operand under the context's method: slice widths on the device, their scan on the host
+// (rows / 64 integers down and up), the fill on the device.  Leaves m.sell empty where the rule keeps the operand on CSR.
+static int sell_build_into(maus_ctx* c, const MausCsr& m, MausSell& s, int*& d_width) {
+    const int ns = (m.rows + MAUS_WAVE - 1) / MAUS_WAVE, blocks = (ns * MAUS_WAVE + SP_BT - 1) / SP_BT;
+    HIPCHK(c, hipMalloc((void**)&s.len, sizeof(int) * m.rows));
+    HIPCHK(c, hipMalloc((void**)&d_width, sizeof(int) * ns));
+    hipLaunchKernelGGL(sell_width_kernel, dim3(blocks), dim3(SP_BT), 0, c->st, m.ptr, m.rows, ns, s.len, d_width);
+    std::vector<int> width(ns);
+    if (maus_stage_d2h(c, width.data(), d_width, sizeof(int) * ns, c->st)) return -1;
+    std::vector<long> off((size_t)ns + 1, 0);
+    for (int i = 0; i < ns; ++i) off[i + 1] = off[i] + (long)MAUS_WAVE * width[i];
+    s.slices = ns; s.padded = off[ns]; s.wmax = *std::max_element(width.begin(), width.end());
+    if (spmm_kind(c->spmm_method, c->spmm_fill_cap, c->csr_sched, m.nnz, s.padded) != MAUS_SPMM_SELL) return 1;
+    HIPCHK(c, hipMalloc((void**)&s.off, sizeof(long) * (ns + 1)));
+    HIPCHK(c, hipMalloc((void**)&s.idx, sizeof(int) * s.padded));
+    HIPCHK(c, hipMalloc((void**)&s.val, sizeof(c128) * s.padded));
+    if (maus_stage_h2d(c, s.off, off.data(), sizeof(long) * (ns + 1), c->st)) return -1;
+    hipLaunchKernelGGL(sell_fill_kernel, dim3(blocks), dim3(SP_BT), 0, c->st, m.ptr, m.idx, m.val, m.rows, ns, s.off, s.idx, s.val);
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+static int sell_build(maus_ctx* c, MausCsr& m) {
+    sell_free(m.sell);
+    if (spmm_kind(c->spmm_method, c->spmm_fill_cap, c->csr_sched, m.nnz, 0) != MAUS_SPMM_SELL) return 0;   // no padded size passes
+    MausSell s;
+    int* d_width = nullptr;
+    const int rc = sell_build_into(c, m, s, d_width);
+    if (d_width) (void)hipFree(d_width);
+    if (rc) { sell_free(s); return rc < 0 ? -1 : 0; }
+    m.sell = s;
+    return 0;
+}
 
 // Host-side checks of one CSR operand: indptr starts at 0, never decreases and ends at nnz; column indices lie in
 // [0, cols) and increase strictly inside a row (sorted, no duplicates: the H build scatters one entry per position).
@@ -193,12 +384,60 @@ int maus_set_matrix_csr(maus_ctx* c, int rows, int cols, int64_t nnz,
     c->csr = true;
     HIPCHK(c, hipStreamSynchronize(c->st));
     HIPCHK(c, hipGetLastError());
+    if (sell_build(c, c->Acsr) || sell_build(c, c->AHcsr)) return -1;      // under maus_spmm_set_method(ctx, 1)
     return 0;
 }
 
 int maus_matrix_is_sparse(maus_ctx* c) {
     if (!c) return -1;
     return c->csr ? c->csr_sched : 0;
+}
+
+int maus_spmm_set_method(maus_ctx* c, int method, int fill_cap_percent) {
+    if (!c) return -1;
+    if (!spmm_setting_ok(method, fill_cap_percent))
+        FAIL(c, "maus_spmm_set_method: method must be 0 (CSR) or 1 (sliced ELL), fill_cap_percent 0 (the rule's 200) or 100..1000000");
+    if (method == c->spmm_method && fill_cap_percent == c->spmm_fill_cap) return 0;
+    if (!c->csr) { c->spmm_method = method; c->spmm_fill_cap = fill_cap_percent; return 0; }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->st));                   // products in flight still read the copies
+    const int old_method = c->spmm_method, old_cap = c->spmm_fill_cap;
+    c->spmm_method = method; c->spmm_fill_cap = fill_cap_percent;
+    if (sell_build(c, c->Acsr) || sell_build(c, c->AHcsr)) {
+        // a failed build (device memory) leaves the previous setting: its copies are built again, and where that fails too the
+        // operands run the CSR kernels, which give the same bits
+        const std::string why = c->err;
+        c->spmm_method = old_method; c->spmm_fill_cap = old_cap;
+        if (sell_build(c, c->Acsr) || sell_build(c, c->AHcsr)) { sell_free(c->Acsr.sell); sell_free(c->AHcsr.sell); }
+        c->err = why;
+        return -1;
+    }
+    return 0;
+}
+
+int maus_spmm_get_method(maus_ctx* c) { return c ? c->spmm_method : -1; }
+
+int maus_spmm_plan(int method, int fill_cap_percent, int rows, int64_t nnz, int64_t padded, int* kind_out) {
+    if (!spmm_setting_ok(method, fill_cap_percent) || rows < 1 || nnz < 0 || padded < 0) return -1;
+    if (kind_out) *kind_out = spmm_kind(method, fill_cap_percent, csr_schedule(rows, (long)nnz), (long)nnz, (long)padded);
+    return 0;
+}
+
+int maus_spmm_kernel_for(maus_ctx* c, int adjoint) {
+    if (!c) return -1;
+    if (!c->csr) return 0;
+    return (adjoint ? c->AHcsr : c->Acsr).sell.val ? MAUS_SPMM_SELL : c->csr_sched;
+}
+
+int maus_spmm_sell_info(maus_ctx* c, int adjoint, int* slices, int64_t* padded, int64_t* bytes) {
+    if (!c) return -1;
+    const MausCsr& m = adjoint ? c->AHcsr : c->Acsr;
+    const MausSell& s = m.sell;
+    const bool on = c->csr && s.val;
+    if (slices) *slices = on ? s.slices : 0;
+    if (padded) *padded = on ? s.padded : 0;
+    if (bytes) *bytes = on ? (int64_t)(20 * s.padded + (long)sizeof(int) * m.rows + (long)sizeof(long) * (s.slices + 1)) : 0;
+    return 0;
 }
 
 }  // extern "C"

@@ -271,6 +271,17 @@ def few_rows_mode(mode):
     return mode
 
 
+SPARSE_SPMM_MODES = ("auto", "csr", "sell")
+
+
+def sparse_spmm_mode(mode):
+    """The `sparse_spmm` keyword: an explicit value, else MAUS_SPARSE_SPMM, else 'auto'."""
+    mode = mode if mode is not None else os.environ.get("MAUS_SPARSE_SPMM", "auto")
+    if mode not in SPARSE_SPMM_MODES:
+        raise ValueError(f"sparse_spmm must be one of {SPARSE_SPMM_MODES}, not {mode!r}")
+    return mode
+
+
 SPARSE_EIGSH_MODES = ("auto", "dense", "lanczos")
 
 
@@ -371,7 +382,7 @@ class DeviceEngine:
 
     def __init__(self, device: int = 0, pert_mode: str = "auto", gmres_compat: str = "rtol",
                  comm=None, ctx=None, eigh_mode: str = "auto", sparse_mode=None, sparse_direct=None, sparse_eigsh=None,
-                 sparse_gmres=None, few_rows=None):
+                 sparse_gmres=None, few_rows=None, sparse_spmm=None):
         self.ctx = ctx if ctx is not None else _cabi.Context(device)
         cap_blas_threads()
         # Hermitian eigendecomposition (AMS:161), once per matrix: 'host' = scipy.linalg.eigh, the reference's call, (lambda, V)
@@ -404,6 +415,13 @@ class DeviceEngine:
         self.few_rows = few_rows_mode(few_rows)
         if self.few_rows == "splitk":           # the only mode that touches the method: contexts without it keep working
             self.ctx.few_rows_set_method(_cabi.FEW_ROWS_SPLITK)
+        # products with a sparse matrix (DESIGN §10 "SpMM on a sliced-ELL copy"): 'auto' and 'csr' = the CSR kernels as ever;
+        # 'sell' = the lane-per-row kernel on a sliced-ELL copy of every operand whose padding stays within twice its nnz
+        # (opt-in, 'auto' never picks it; the CSR kernel's bits).  MAUS_SPARSE_SPMM sets the default.  Told to the context
+        # here, once: it is kept across matrices and the copies are built when a sparse matrix is bound.
+        self.sparse_spmm = sparse_spmm_mode(sparse_spmm)
+        if self.sparse_spmm == "sell":          # the only mode that touches the method: contexts without it keep working
+            self.ctx.spmm_set_method(_cabi.SPMM_SELL)
         # sparse Hermitian shortcut (AMS:186-216): 'dense' = one scipy.linalg.eigh of A.toarray() per matrix, 'lanczos' =
         # thick-restart Lanczos on the CSR matrix on the device, 'auto' the first up to maus_lu_max_n() and the second above.
         # MAUS_SPARSE_EIGSH sets the default.

@@ -32,7 +32,7 @@ from . import _cabi
 from ._cabi import POP_U, POP_X
 from .band import DIRECT_METHOD, band_bytes_per_solve, band_order
 from .candstore import C_NP as _C_NP, C_PY as _C_PY, EXACT as _EXACT, F_NP as _F_NP, F_PY as _F_PY, HREF as _HREF, MISSING as _MISSING
-from .engine import DIRECT, GMRES, DeviceEngine, _advance_numpy_stream, few_rows_mode, sparse_direct_mode, sparse_eigsh_mode, sparse_gmres_mode
+from .engine import DIRECT, GMRES, DeviceEngine, _advance_numpy_stream, few_rows_mode, sparse_direct_mode, sparse_eigsh_mode, sparse_gmres_mode, sparse_spmm_mode
 
 
 class ProblemType(Enum):                     # AMS:10-13
@@ -162,7 +162,7 @@ class InverseIterateSolver:
 
     def __init__(self, N, base_psi_epsilon, max_attempts, preferred_method="direct_solve", is_sparse=False,
                  gmres_compat="rtol", pert_mode="uniform", sparse_mode=None, sparse_direct=None, sparse_gmres=None,
-                 few_rows=None):
+                 few_rows=None, sparse_spmm=None):
         self.N = N
         self.base_psi_epsilon = base_psi_epsilon
         self.max_attempts = max_attempts
@@ -175,6 +175,7 @@ class InverseIterateSolver:
         self.sparse_direct = sparse_direct_mode(sparse_direct)
         self.sparse_gmres = sparse_gmres_mode(sparse_gmres)
         self.few_rows = few_rows_mode(few_rows)
+        self.sparse_spmm = sparse_spmm_mode(sparse_spmm)
         self.last_trace = []
 
     @classmethod
@@ -199,6 +200,12 @@ class InverseIterateSolver:
             # NaNs on a singular H land in the same ValueError -> retry branch as the LU's info > 0)
             import scipy.sparse as sp
             A_sp = A_target if _is_sparse(A_target) else sp.csr_matrix(A_target)
+            # the context is shared by every InverseIterateSolver: each solve states the SpMM method ('sell' is opt-in), before
+            # the bind, which builds the sliced-ELL copies under it
+            if self.sparse_spmm == "sell":
+                ctx.spmm_set_method(_cabi.SPMM_SELL)
+            elif getattr(ctx, "spmm_method", None) is not None and ctx.spmm_method() != _cabi.SPMM_CSR:
+                ctx.spmm_set_method(_cabi.SPMM_CSR)
             ctx.set_matrix_csr(A_sp)
             # the context is shared by every InverseIterateSolver: each solve states the GMRES schedule ('wide' is opt-in)
             if self.sparse_gmres == "wide":
@@ -771,8 +778,9 @@ class MAUS_Solver:
                  global_convergence_tol=1e-8, *, device=0, pert_mode="auto", gmres_compat="rtol",
                  record_history=None, comm=None, quiet=False, engine=None, gram_min=8, cond_exact_max=1024,
                  diag_info=None, eigh_mode="auto", sparse_mode=None, sparse_direct=None, sparse_eigsh=None,
-                 sparse_hermitian_check=None, sparse_gmres=None, few_rows=None):
+                 sparse_hermitian_check=None, sparse_gmres=None, few_rows=None, sparse_spmm=None):
         few_rows = few_rows_mode(few_rows)
+        sparse_spmm = sparse_spmm_mode(sparse_spmm)
         sparse_mode = _sparse_mode(sparse_mode)
         sparse_direct = sparse_direct_mode(sparse_direct)
         sparse_eigsh = sparse_eigsh_mode(sparse_eigsh)
@@ -801,7 +809,7 @@ class MAUS_Solver:
                                                                      gmres_compat=gmres_compat, comm=comm, eigh_mode=eigh_mode,
                                                                      sparse_mode=sparse_mode, sparse_direct=sparse_direct,
                                                                      sparse_eigsh=sparse_eigsh, sparse_gmres=sparse_gmres,
-                                                                     few_rows=few_rows)
+                                                                     few_rows=few_rows, sparse_spmm=sparse_spmm)
         # `diag_info`: start-up diagnostics of the same matrix taken from an earlier solver (bench side runs)
         if diag_info is not None:
             self.diag_info = dict(diag_info)

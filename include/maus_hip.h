@@ -403,6 +403,38 @@ int maus_few_rows_get_method(maus_ctx* ctx);
 int maus_few_rows_kernel_for(maus_ctx* ctx, int M, int N, int K, int b_layout, int conj_a, int conj_b, int* slices_out);
 int maus_few_rows_plan(int method, int slices, int M, int N, int K, int b_layout, int conj_a, int conj_b, int* slices_out);
 int maus_few_rows_workspace_allocs(maus_ctx* ctx);
+/* Products with a CSR-bound matrix (every one goes through the same launcher: the Rayleigh quotient, the residuals, the SVD power
+ * step, the GMRES products, the Lanczos steps).  The lane-per-row schedule (maus_matrix_is_sparse = 1) can read its operand from a
+ * second, sliced-ELL copy: rows in slices of 64, slice s as wide as its longest row, entry p of row r at off[s] + 64 p + (r & 63),
+ * so that one wave-wide load of the operand is contiguous.  A lane still owns a row and adds its nonzeros in CSR order with the
+ * same fused operations onto a zero accumulator: every output element is the number the CSR kernel gives, bit for bit, padding
+ * is never read, and a row's product stays independent of the batch.  The CSR arrays stay resident beside the copy.
+ *   maus_spmm_set_method   0 (the default): the CSR kernels.  1: the sliced-ELL copy for every operand (A and A^H are judged
+ *                          separately) of a matrix of the lane-per-row schedule with nnz > 0 whose padded size sum(64 w_s) is at
+ *                          most fill_cap_percent / 100 * nnz; every other operand runs the CSR kernels as under 0.  A build that
+ *                          fails (device memory) is an error that leaves the previous method and cap.
+ *                          fill_cap_percent 0: the library's 200 (a cap on memory, 20 bytes per padded slot); 100..1000000 for
+ *                          tests and timing.  Another method or cap is an error that changes and launches nothing.  Kept across
+ *                          matrices: with a CSR matrix bound the copies are built or freed at once, and maus_set_matrix_csr
+ *                          builds them at bind time under method 1; maus_set_matrix, the next bind and maus_ctx_destroy free
+ *                          them.  The build is three steps on the device without atomics (slice widths, their scan, the fill):
+ *                          the same matrix gives the same arrays.
+ *   maus_spmm_get_method   the current method.
+ *   maus_spmm_kernel_for   what a product with the bound matrix (adjoint != 0: with A^H) runs under the current method: 0 no CSR
+ *                          matrix is bound, 1 the lane-per-row CSR kernel, 2 the wave-per-row CSR kernel, 3 the sliced-ELL kernel.
+ *   maus_spmm_plan         the same rule for a (method, fill_cap_percent), a matrix of `rows` rows and nnz entries and an
+ *                          operand of it (A or A^H) with `padded` sliced-ELL slots, without a context or a device: kind_out =
+ *                          1 / 2 / 3 as above.  `rows` is the row count of A for both operands: the schedule belongs to the
+ *                          matrix (maus_matrix_is_sparse, nnz > 32 rows of A: a wave per row), the CSR kernels run A and A^H
+ *                          under it, and only a lane-per-row matrix takes copies.  -1 for bad arguments (method, cap, rows < 1,
+ *                          nnz < 0, padded < 0).
+ *   maus_spmm_sell_info    what is resident for that operand: slices, padded slots, bytes (values, indices, row lengths and
+ *                          slice offsets).  All zeros when the operand has no sliced-ELL copy.  Any of the three may be NULL. */
+int maus_spmm_set_method(maus_ctx* ctx, int method, int fill_cap_percent);
+int maus_spmm_get_method(maus_ctx* ctx);
+int maus_spmm_kernel_for(maus_ctx* ctx, int adjoint);
+int maus_spmm_plan(int method, int fill_cap_percent, int rows, int64_t nnz, int64_t padded, int* kind_out);
+int maus_spmm_sell_info(maus_ctx* ctx, int adjoint, int* slices, int64_t* padded, int64_t* bytes);
 /* AMS:67-72 gate: ok[i]=1 iff all 1/diag(H_k) finite and all |diag(H_k)| > 1e-12 */
 int maus_jacobi_check(maus_ctx* ctx, int count, const double* shift_c128, const double* psi, int32_t* ok);
 
