@@ -24,6 +24,10 @@
 // The post step has two schedules for a CSR-bound matrix (maus_gmres_set_method): by default one workgroup per candidate
 // (gmres_post_kernel with w in registers up to n = 16384, gmres_post_stream_kernel above); under method 1 the wide step further
 // down (the gw_* kernels), which splits n over workgroups and joins every sum from per-piece partials in one fixed order.
+// What the three schedules share is stated once: the rotation (zlartg), the decisions after a residual (resid_decide) and the
+// one-lane Arnoldi tail (arnoldi_tail).  Their reductions are NOT shared: blk_sum and gw_block_sum / gw_join add in different
+// orders, and each schedule's bits are those of its own order.  The vector bodies of the register and the streamed kernel are
+// two texts on purpose (profiles/gmres_share.txt, section 5).
 #include "ctx.h"
 #include <algorithm>
 #include <cstring>
@@ -83,29 +87,114 @@ __device__ __forceinline__ c128 cdiv_np(c128 a, c128 b) {
 }
 
 // LAPACK 3.10+ zlartg, safe-range branches:  [c s; -conj(s) c] [f; g] = [r; 0], c real
-__device__ void zlartg_dev(c128 f, c128 g, double& c, c128& s, c128& r) {
+// By value, every result component a scalar that is assigned once per branch, the call inlined: c, s and r stay in registers
+// (reference parameters cost every calling kernel 24 bytes of scratch per lane, inlined or not).
+struct Rot { double c, sx, sy, rx, ry; };
+__device__ __forceinline__ Rot zlartg(c128 f, c128 g) {
     const double safmin = 2.2250738585072014e-308, rtmin = 1.4916681462400413e-154;
-    if (g.x == 0.0 && g.y == 0.0) { c = 1.0; s = cmake(0.0, 0.0); r = f; return; }
+    Rot o;
+    if (g.x == 0.0 && g.y == 0.0) { o.c = 1.0; o.sx = 0.0; o.sy = 0.0; o.rx = f.x; o.ry = f.y; return o; }
     if (f.x == 0.0 && f.y == 0.0) {
-        c = 0.0;
-        double d;
-        if (g.x == 0.0) d = fabs(g.y); else if (g.y == 0.0) d = fabs(g.x); else d = sqrt(g.x * g.x + g.y * g.y);
-        s = cmake(g.x / d, -g.y / d); r = cmake(d, 0.0); return;
+        const double d = (g.x == 0.0) ? fabs(g.y) : ((g.y == 0.0) ? fabs(g.x) : sqrt(g.x * g.x + g.y * g.y));
+        o.c = 0.0; o.sx = g.x / d; o.sy = -g.y / d; o.rx = d; o.ry = 0.0; return o;
     }
     const double f2 = f.x * f.x + f.y * f.y, g2 = g.x * g.x + g.y * g.y, h2 = f2 + g2;
     const c128 gc_ = cconj(g);
+    c128 sv;
     if (f2 >= h2 * safmin) {
-        c = sqrt(f2 / h2);
-        r = cmake(f.x / c, f.y / c);
+        o.c = sqrt(f2 / h2);
+        o.rx = f.x / o.c; o.ry = f.y / o.c;
         const double rtmax2 = 6.703903964971299e+153;    // 2 * sqrt(safmax/4)
-        if (f2 > rtmin && h2 < rtmax2) { const double d = sqrt(f2 * h2); s = cmul(gc_, cmake(f.x / d, f.y / d)); }
-        else s = cmul(gc_, cmake(r.x / h2, r.y / h2));
+        if (f2 > rtmin && h2 < rtmax2) { const double d = sqrt(f2 * h2); sv = cmul(gc_, cmake(f.x / d, f.y / d)); }
+        else sv = cmul(gc_, cmake(o.rx / h2, o.ry / h2));
     } else {
         const double d = sqrt(f2 * h2);
-        c = f2 / d;
-        if (c >= safmin) r = cmake(f.x / c, f.y / c); else { const double q = h2 / d; r = cmake(f.x * q, f.y * q); }
-        s = cmul(gc_, cmake(f.x / d, f.y / d));
+        o.c = f2 / d;
+        if (o.c >= safmin) { o.rx = f.x / o.c; o.ry = f.y / o.c; } else { const double q = h2 / d; o.rx = f.x * q; o.ry = f.y * q; }
+        sv = cmul(gc_, cmake(f.x / d, f.y / d));
     }
+    o.sx = sv.x; o.sy = sv.y;
+    return o;
+}
+
+// The decisions after a residual r = b - H x of norm rnorm (iterative.py:737-748, 826-838): done with `info`, or a new restart
+// cycle with the cycle count, ptol_max_factor and ptol it starts from.  Pure; the caller stores.
+struct Resid { bool done; int info, cycle; double pmf, ptol; };
+__device__ __forceinline__ Resid resid_decide(const GState& s, double rnorm, int maxiter) {
+    Resid o;
+    o.done = false; o.info = 0;
+    o.pmf = s.pmf; o.ptol = s.ptol; o.cycle = s.cycle;
+    if (!(rnorm == rnorm)) { o.done = true; o.info = maxiter; }              // NaN: can never pass a test
+    else if (s.first) { if (rnorm < s.atol) { o.done = true; o.info = 0; } }
+    else {
+        if (rnorm <= s.atol) { o.done = true; o.info = 0; }
+        else if (s.breakdown) { o.done = true; o.info = maxiter; }
+        else {
+            if (s.presid <= s.ptol) o.pmf = fmax(EPS, 0.25 * o.pmf); else o.pmf = fmin(1.0, 1.5 * o.pmf);
+            o.ptol = s.presid * fmin(o.pmf, s.atol / rnorm);
+            o.cycle += 1;
+            if (o.cycle >= maxiter) { o.done = true; o.info = maxiter; }
+        }
+    }
+    return o;
+}
+
+// The one-lane tail of an Arnoldi step (iterative.py:778-816).  h[0 .. col] holds the Gram-Schmidt coefficients of column col;
+// h1 = ||w|| after them, brk the breakdown verdict.  Applies the earlier rotations, forms the new one, moves S, presid and the
+// counters of GState on and, where the inner loop ends, solves for y[0 .. col] (the caller then adds y @ V[:col + 1] to x) and
+// hands the candidate to phase 1; otherwise to column col + 1.  *end = whether the inner loop ended, stored where the verdict
+// falls and not returned: with the store after the pseudo-solve gmres_post_kernel<32, 512> allocates its registers otherwise
+// and the n = 12288 row is 1 % slower (profiles/gmres_share.txt, section 4).
+__device__ __forceinline__ void arnoldi_tail(GState& s, c128* h, c128* y, int* end, int col, int R, bool brk, double h1) {
+    h[col + 1] = cmake(brk ? 0.0 : h1, 0.0);
+    for (int kk = 0; kk < col; ++kk) {
+        const double c = s.gc[kk]; const c128 sg = s.gs[kk];
+        const c128 n0 = h[kk], n1 = h[kk + 1];
+        c128 a0 = cmake(c * n0.x, c * n0.y); cfma(a0, sg, n1);
+        c128 a1 = cmake(c * n1.x, c * n1.y); cfms(a1, cconj(sg), n0);
+        h[kk] = a0; h[kk + 1] = a1;
+    }
+    const Rot rot = zlartg(h[col], h[col + 1]);
+    const double c = rot.c; const c128 sg = cmake(rot.sx, rot.sy), mag = cmake(rot.rx, rot.ry);
+    s.gc[col] = c; s.gs[col] = sg;
+    h[col] = mag; h[col + 1] = cmake(0.0, 0.0);
+    const c128 Sc = s.S[col];
+    const c128 tmp = cmul(cmake(-sg.x, sg.y), Sc);          // -conj(s) * S[col]
+    s.S[col] = cmake(c * Sc.x, c * Sc.y);
+    s.S[col + 1] = tmp;
+    const double presid = hypot(tmp.x, tmp.y);
+    s.presid = presid;
+    s.inner += 1;
+    for (int j = 0; j <= col + 1; ++j) s.h[col][j] = h[j];
+    if (brk) s.breakdown = 1;
+    const bool end_inner = (presid <= s.ptol) || brk || (col == R - 1);
+    *end = end_inner ? 1 : 0;
+    if (end_inner) {
+        // y = trsv(h^T, S) with the pseudo-solve rules of iterative.py:806-816
+        if (s.h[col][col].x == 0.0 && s.h[col][col].y == 0.0) s.S[col] = cmake(0.0, 0.0);
+        for (int j = 0; j <= col; ++j) y[j] = s.S[j];
+        for (int kk = col; kk > 0; --kk) {
+            if (y[kk].x != 0.0 || y[kk].y != 0.0) {
+                y[kk] = cdiv_np(y[kk], s.h[kk][kk]);
+                const c128 t = y[kk];
+                for (int j = 0; j < kk; ++j) cfms(y[j], t, s.h[kk][j]);
+            }
+        }
+        if (y[0].x != 0.0 || y[0].y != 0.0) y[0] = cdiv_np(y[0], s.h[0][0]);
+        s.phase = 1;
+    } else {
+        s.col = col + 1;
+    }
+}
+
+// diag(H_k)[i] = (diag(A)[i] - lambda_k) + psi_k with the roundings of the build kernels of the direct solve
+__device__ __forceinline__ c128 shifted_diag(c128 d, c128 lam, double ps) {
+    return cmake(__dadd_rn(__dsub_rn(d.x, lam.x), ps), __dadd_rn(__dsub_rn(d.y, lam.y), 0.0));
+}
+// AMS:67-72: a diagonal entry rules the Jacobi scale out unless 1/d is finite and |d| > 1e-12
+__device__ __forceinline__ bool jacobi_bad(c128 d) {
+    const c128 inv = crecip_np(d);
+    return !cfinite(inv) || !(hypot(d.x, d.y) > 1e-12);
 }
 
 __global__ void __launch_bounds__(256)
@@ -124,11 +213,8 @@ jacobi_check_kernel(const c128* __restrict__ dA, int n, const c128* __restrict__
     __syncthreads();
     const c128 lam = shift[g]; const double ps = psi[g];
     bool bad = false;
-    for (int i = threadIdx.x; i < n; i += GT) {
-        const c128 d = cmake(__dadd_rn(__dsub_rn(dA[i].x, lam.x), ps), __dadd_rn(__dsub_rn(dA[i].y, lam.y), 0.0));
-        const c128 inv = crecip_np(d);
-        if (!cfinite(inv) || !(hypot(d.x, d.y) > 1e-12)) bad = true;
-    }
+    for (int i = threadIdx.x; i < n; i += GT)
+        if (jacobi_bad(shifted_diag(dA[i], lam, ps))) bad = true;
     if (bad) atomicOr(&sbad, 1);
     __syncthreads();
     if (threadIdx.x == 0) ok[g] = sbad ? 0 : 1;
@@ -148,12 +234,7 @@ __device__ __forceinline__ const c128* rhs_of(const GArgs& a, int k) {
 }
 __device__ __forceinline__ c128 psolve1(const GArgs& a, int k, int i, c128 v) {
     if (!a.jac[k]) return v;
-    c128 d;
-    if (a.Hd) d = a.Hd[(long)k * a.strideH + (long)i * a.ldh + i];
-    else {
-        const c128 lam = a.shift[k];
-        d = cmake(__dadd_rn(__dsub_rn(a.dA[i].x, lam.x), a.psi[k]), __dadd_rn(__dsub_rn(a.dA[i].y, lam.y), 0.0));
-    }
+    const c128 d = a.Hd ? a.Hd[(long)k * a.strideH + (long)i * a.ldh + i] : shifted_diag(a.dA[i], a.shift[k], a.psi[k]);
     return cmul(crecip_np(d), v);
 }
 
@@ -166,11 +247,8 @@ jacobi_gate_dense_kernel(GArgs a, int* __restrict__ jac) {
     __syncthreads();
     bool bad = false;
     if (jac[k]) {
-        for (int i = threadIdx.x; i < a.n; i += GT) {
-            const c128 d = a.Hd[(long)k * a.strideH + (long)i * a.ldh + i];
-            const c128 inv = crecip_np(d);
-            if (!cfinite(inv) || !(hypot(d.x, d.y) > 1e-12)) bad = true;
-        }
+        for (int i = threadIdx.x; i < a.n; i += GT)
+            if (jacobi_bad(a.Hd[(long)k * a.strideH + (long)i * a.ldh + i])) bad = true;
     }
     if (bad) atomicOr(&sbad, 1);
     __syncthreads();
@@ -246,14 +324,33 @@ gmres_pad_rows_kernel(int* __restrict__ act, int* __restrict__ zrow, int nact, i
     if (p < to) { act[p] = act[0]; zrow[p] = zrow[0]; }
 }
 
-// active list + the row of the basis array each active candidate multiplies next
+// what a tick's kernels of the wide step need of a candidate besides GState: phase and column as the compact kernel found them
+// (the state kernel moves GState on while the finish kernel still needs them), the Hessenberg column under construction, and the
+// state kernel's verdict for the finish kernel
+struct WState {
+    int phase, col, cont, end;        // cont: phase 1 goes on to a new cycle; end: the inner loop ended, x += y @ V[:col+1]
+    double inv, pad;
+    c128 hcol[MAXR + 2];
+    c128 y[MAXR + 1];
+};
+
+// active list + the row of the basis array each active candidate multiplies next; out[0] = active candidates.  WIDE (the wide
+// step): also the tick's (phase, col) of every active candidate into WState, and what the host needs to issue only the launches
+// the tick has work for: out[1] = largest col among those in phase 0 (-1: none), out[2] = candidates in phase 1, out[3] = sum of
+// col over phase 0 (the byte count of the profile class)
+template <bool WIDE>
 __global__ void __launch_bounds__(1024)
 gmres_compact_kernel(const GState* __restrict__ st, int count, int rows_per, int R, int* __restrict__ act,
-                     int* __restrict__ zrow, int* __restrict__ nact) {
+                     int* __restrict__ zrow, WState* __restrict__ ws, int* __restrict__ out) {
     __shared__ int scnt[16];
     __shared__ int sbase;
-    if (threadIdx.x == 0) sbase = 0;
+    __shared__ int smax, sp1, ssum;           // WIDE only
+    if (threadIdx.x == 0) {
+        sbase = 0;
+        if (WIDE) { smax = -1; sp1 = 0; ssum = 0; }
+    }
     __syncthreads();
+    int mx = -1, p1 = 0, sum = 0;
     for (int k0 = 0; k0 < count; k0 += 1024) {
         const int k = k0 + threadIdx.x;
         const bool on = k < count && st[k].phase != 2;
@@ -265,14 +362,26 @@ gmres_compact_kernel(const GState* __restrict__ st, int count, int rows_per, int
         for (int w = 0; w < wave; ++w) off += scnt[w];
         if (on) {
             const int p = off + __popcll(m & ((1ull << lane) - 1ull));
+            const int ph = st[k].phase, col = st[k].col;
             act[p] = k;
-            zrow[p] = k * rows_per + (st[k].phase == 1 ? R + 1 : st[k].col);
+            zrow[p] = k * rows_per + (ph == 1 ? R + 1 : col);
+            if (WIDE) {
+                ws[k].phase = ph; ws[k].col = col; ws[k].cont = 0; ws[k].end = 0;
+                if (ph == 1) p1 += 1; else { mx = max(mx, col); sum += col; }
+            }
         }
         __syncthreads();
         if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < 16; ++w) t += scnt[w]; sbase += t; }
         __syncthreads();
     }
-    if (threadIdx.x == 0) *nact = sbase;
+    if (WIDE) {
+        atomicMax(&smax, mx); atomicAdd(&sp1, p1); atomicAdd(&ssum, sum);     // integers: any order gives the same result
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out[0] = sbase;
+        if (WIDE) { out[1] = smax; out[2] = sp1; out[3] = ssum; }
+    }
 }
 
 // EPT entries of the candidate's vectors per thread of an NT-thread workgroup: 256 threads up to n = 8192, 512 threads (EPT 32,
@@ -311,23 +420,10 @@ gmres_post_kernel(GArgs a, const int* __restrict__ act) {
             }
         }
         const double rnorm = sqrt(blk_sum<NT>(ss, sbuf));
-        bool done = false; int info = 0;
-        double pmf = s.pmf, ptol = s.ptol; int cycle = s.cycle;
-        if (!(rnorm == rnorm)) { done = true; info = a.maxiter; }              // NaN: can never pass a test
-        else if (s.first) { if (rnorm < s.atol) { done = true; info = 0; } }
-        else {
-            if (rnorm <= s.atol) { done = true; info = 0; }
-            else if (s.breakdown) { done = true; info = a.maxiter; }
-            else {
-                if (s.presid <= s.ptol) pmf = fmax(EPS, 0.25 * pmf); else pmf = fmin(1.0, 1.5 * pmf);
-                ptol = s.presid * fmin(pmf, s.atol / rnorm);
-                cycle += 1;
-                if (cycle >= a.maxiter) { done = true; info = a.maxiter; }
-            }
-        }
-        if (done) {
+        const Resid d = resid_decide(s, rnorm, a.maxiter);
+        if (d.done) {
             __syncthreads();
-            if (tid == 0) { s.rnorm = rnorm; s.info = info; s.phase = 2; }
+            if (tid == 0) { s.rnorm = rnorm; s.info = d.info; s.phase = 2; }
             return;
         }
         // V[0] = psolve(r) / ||psolve(r)||
@@ -345,7 +441,7 @@ gmres_post_kernel(GArgs a, const int* __restrict__ act) {
             if (i < n) Vk[i] = cmake(w[e].x * inv, w[e].y * inv);
         }
         if (tid == 0) {
-            s.rnorm = rnorm; s.pmf = pmf; s.ptol = ptol; s.cycle = cycle; s.first = 0;
+            s.rnorm = rnorm; s.pmf = d.pmf; s.ptol = d.ptol; s.cycle = d.cycle; s.first = 0;
             for (int j = 0; j <= R; ++j) s.S[j] = cmake(0.0, 0.0);
             s.S[0] = cmake(tmp, 0.0);
             s.col = 0; s.breakdown = 0; s.phase = 0;
@@ -404,48 +500,7 @@ gmres_post_kernel(GArgs a, const int* __restrict__ act) {
             if (i < n) vn[i] = cmake(w[e].x * inv, w[e].y * inv);
         }
     }
-    if (tid == 0) {
-        // Hessenberg column: previous rotations, new rotation, rhs S, ptol test
-        s_h[col + 1] = cmake(brk ? 0.0 : h1, 0.0);
-        for (int kk = 0; kk < col; ++kk) {
-            const double c = s.gc[kk]; const c128 sg = s.gs[kk];
-            const c128 n0 = s_h[kk], n1 = s_h[kk + 1];
-            c128 a0 = cmake(c * n0.x, c * n0.y); cfma(a0, sg, n1);
-            c128 a1 = cmake(c * n1.x, c * n1.y); cfms(a1, cconj(sg), n0);
-            s_h[kk] = a0; s_h[kk + 1] = a1;
-        }
-        double c; c128 sg, mag;
-        zlartg_dev(s_h[col], s_h[col + 1], c, sg, mag);
-        s.gc[col] = c; s.gs[col] = sg;
-        s_h[col] = mag; s_h[col + 1] = cmake(0.0, 0.0);
-        const c128 Sc = s.S[col];
-        const c128 tmp = cmul(cmake(-sg.x, sg.y), Sc);          // -conj(s) * S[col]
-        s.S[col] = cmake(c * Sc.x, c * Sc.y);
-        s.S[col + 1] = tmp;
-        const double presid = hypot(tmp.x, tmp.y);
-        s.presid = presid;
-        s.inner += 1;
-        for (int j = 0; j <= col + 1; ++j) s.h[col][j] = s_h[j];
-        if (brk) s.breakdown = 1;
-        const bool end_inner = (presid <= s.ptol) || brk || (col == R - 1);
-        s_flag[0] = end_inner ? 1 : 0;
-        if (end_inner) {
-            // y = trsv(h^T, S) with the pseudo-solve rules of iterative.py:806-816
-            if (s.h[col][col].x == 0.0 && s.h[col][col].y == 0.0) s.S[col] = cmake(0.0, 0.0);
-            for (int j = 0; j <= col; ++j) s_y[j] = s.S[j];
-            for (int kk = col; kk > 0; --kk) {
-                if (s_y[kk].x != 0.0 || s_y[kk].y != 0.0) {
-                    s_y[kk] = cdiv_np(s_y[kk], s.h[kk][kk]);
-                    const c128 t = s_y[kk];
-                    for (int j = 0; j < kk; ++j) cfms(s_y[j], t, s.h[kk][j]);
-                }
-            }
-            if (s_y[0].x != 0.0 || s_y[0].y != 0.0) s_y[0] = cdiv_np(s_y[0], s.h[0][0]);
-            s.phase = 1;
-        } else {
-            s.col = col + 1;
-        }
-    }
+    if (tid == 0) arnoldi_tail(s, s_h, s_y, &s_flag[0], col, R, brk, h1);
     __syncthreads();
     if (s_flag[0]) {                                           // x += y @ V[:col+1]
 #pragma unroll
@@ -463,7 +518,7 @@ gmres_post_kernel(GArgs a, const int* __restrict__ act) {
 // gmres_post_kernel for 16384 < n (CSR matrices only): w is not held in registers but streamed through the basis row it
 // becomes, V[col + 1] (the Arnoldi step) or V[0] (the residual of a new cycle); thread t owns the entries t, t + NT, ... of
 // every vector, as the register kernels do.  Same modified Gram-Schmidt order, state machine and exits; the variant is picked
-// from n alone.
+// from n alone.  The vector loops below are gmres_post_kernel's line for line but for where w lives.
 template <int NT>
 __global__ void __launch_bounds__(NT)
 gmres_post_stream_kernel(GArgs a, const int* __restrict__ act) {
@@ -492,23 +547,10 @@ gmres_post_stream_kernel(GArgs a, const int* __restrict__ act) {
             ss = fma(r.x, r.x, ss); ss = fma(r.y, r.y, ss);
         }
         const double rnorm = sqrt(blk_sum<NT>(ss, sbuf));
-        bool done = false; int info = 0;
-        double pmf = s.pmf, ptol = s.ptol; int cycle = s.cycle;
-        if (!(rnorm == rnorm)) { done = true; info = a.maxiter; }
-        else if (s.first) { if (rnorm < s.atol) { done = true; info = 0; } }
-        else {
-            if (rnorm <= s.atol) { done = true; info = 0; }
-            else if (s.breakdown) { done = true; info = a.maxiter; }
-            else {
-                if (s.presid <= s.ptol) pmf = fmax(EPS, 0.25 * pmf); else pmf = fmin(1.0, 1.5 * pmf);
-                ptol = s.presid * fmin(pmf, s.atol / rnorm);
-                cycle += 1;
-                if (cycle >= a.maxiter) { done = true; info = a.maxiter; }
-            }
-        }
-        if (done) {
+        const Resid d = resid_decide(s, rnorm, a.maxiter);
+        if (d.done) {
             __syncthreads();
-            if (tid == 0) { s.rnorm = rnorm; s.info = info; s.phase = 2; }
+            if (tid == 0) { s.rnorm = rnorm; s.info = d.info; s.phase = 2; }
             return;
         }
         double sv = 0.0;
@@ -521,7 +563,7 @@ gmres_post_stream_kernel(GArgs a, const int* __restrict__ act) {
         const double inv = 1.0 / tmp;
         for (int i = tid; i < n; i += NT) w[i] = cmake(w[i].x * inv, w[i].y * inv);
         if (tid == 0) {
-            s.rnorm = rnorm; s.pmf = pmf; s.ptol = ptol; s.cycle = cycle; s.first = 0;
+            s.rnorm = rnorm; s.pmf = d.pmf; s.ptol = d.ptol; s.cycle = d.cycle; s.first = 0;
             for (int j = 0; j <= R; ++j) s.S[j] = cmake(0.0, 0.0);
             s.S[0] = cmake(tmp, 0.0);
             s.col = 0; s.breakdown = 0; s.phase = 0;
@@ -560,46 +602,7 @@ gmres_post_stream_kernel(GArgs a, const int* __restrict__ act) {
         const double inv = brk ? 1.0 : 1.0 / h1;
         for (int i = tid; i < n; i += NT) w[i] = cmake(w[i].x * inv, w[i].y * inv);
     }
-    if (tid == 0) {
-        s_h[col + 1] = cmake(brk ? 0.0 : h1, 0.0);
-        for (int kk = 0; kk < col; ++kk) {
-            const double c = s.gc[kk]; const c128 sg = s.gs[kk];
-            const c128 n0 = s_h[kk], n1 = s_h[kk + 1];
-            c128 a0 = cmake(c * n0.x, c * n0.y); cfma(a0, sg, n1);
-            c128 a1 = cmake(c * n1.x, c * n1.y); cfms(a1, cconj(sg), n0);
-            s_h[kk] = a0; s_h[kk + 1] = a1;
-        }
-        double c; c128 sg, mag;
-        zlartg_dev(s_h[col], s_h[col + 1], c, sg, mag);
-        s.gc[col] = c; s.gs[col] = sg;
-        s_h[col] = mag; s_h[col + 1] = cmake(0.0, 0.0);
-        const c128 Sc = s.S[col];
-        const c128 tmp = cmul(cmake(-sg.x, sg.y), Sc);
-        s.S[col] = cmake(c * Sc.x, c * Sc.y);
-        s.S[col + 1] = tmp;
-        const double presid = hypot(tmp.x, tmp.y);
-        s.presid = presid;
-        s.inner += 1;
-        for (int j = 0; j <= col + 1; ++j) s.h[col][j] = s_h[j];
-        if (brk) s.breakdown = 1;
-        const bool end_inner = (presid <= s.ptol) || brk || (col == R - 1);
-        s_flag[0] = end_inner ? 1 : 0;
-        if (end_inner) {
-            if (s.h[col][col].x == 0.0 && s.h[col][col].y == 0.0) s.S[col] = cmake(0.0, 0.0);
-            for (int j = 0; j <= col; ++j) s_y[j] = s.S[j];
-            for (int kk = col; kk > 0; --kk) {
-                if (s_y[kk].x != 0.0 || s_y[kk].y != 0.0) {
-                    s_y[kk] = cdiv_np(s_y[kk], s.h[kk][kk]);
-                    const c128 t = s_y[kk];
-                    for (int j = 0; j < kk; ++j) cfms(s_y[j], t, s.h[kk][j]);
-                }
-            }
-            if (s_y[0].x != 0.0 || s_y[0].y != 0.0) s_y[0] = cdiv_np(s_y[0], s.h[0][0]);
-            s.phase = 1;
-        } else {
-            s.col = col + 1;
-        }
-    }
+    if (tid == 0) arnoldi_tail(s, s_h, s_y, &s_flag[0], col, R, brk, h1);
     __syncthreads();
     if (s_flag[0]) {                                           // x += y @ V[:col+1]
         for (int i = tid; i < n; i += NT) {
@@ -622,47 +625,6 @@ constexpr int GW_BT = 256;
 constexpr int GW_E = 2;
 constexpr int GW_SPAN = GW_BT * GW_E;
 
-// what a tick's kernels need of a candidate besides GState: phase and column as the compact kernel found them (the state kernel
-// moves GState on while the finish kernel still needs them), the Hessenberg column under construction, and the state kernel's
-// verdict for the finish kernel
-struct WState {
-    int phase, col, cont, end;        // cont: phase 1 goes on to a new cycle; end: the inner loop ended, x += y @ V[:col+1]
-    double inv, pad;
-    c128 hcol[MAXR + 2];
-    c128 y[MAXR + 1];
-};
-
-// zlartg_dev, operation for operation, with every result component a scalar that is assigned once per branch and the call
-// inlined: the compiler keeps c, s and r in registers (zlartg_dev's reference parameters cost its callers 24 bytes of scratch
-// per lane)
-struct GwRot { double c, sx, sy, rx, ry; };
-__device__ __forceinline__ GwRot gw_zlartg(c128 f, c128 g) {
-    const double safmin = 2.2250738585072014e-308, rtmin = 1.4916681462400413e-154;
-    GwRot o;
-    if (g.x == 0.0 && g.y == 0.0) { o.c = 1.0; o.sx = 0.0; o.sy = 0.0; o.rx = f.x; o.ry = f.y; return o; }
-    if (f.x == 0.0 && f.y == 0.0) {
-        const double d = (g.x == 0.0) ? fabs(g.y) : ((g.y == 0.0) ? fabs(g.x) : sqrt(g.x * g.x + g.y * g.y));
-        o.c = 0.0; o.sx = g.x / d; o.sy = -g.y / d; o.rx = d; o.ry = 0.0; return o;
-    }
-    const double f2 = f.x * f.x + f.y * f.y, g2 = g.x * g.x + g.y * g.y, h2 = f2 + g2;
-    const c128 gc_ = cconj(g);
-    c128 sv;
-    if (f2 >= h2 * safmin) {
-        o.c = sqrt(f2 / h2);
-        o.rx = f.x / o.c; o.ry = f.y / o.c;
-        const double rtmax2 = 6.703903964971299e+153;
-        if (f2 > rtmin && h2 < rtmax2) { const double d = sqrt(f2 * h2); sv = cmul(gc_, cmake(f.x / d, f.y / d)); }
-        else sv = cmul(gc_, cmake(o.rx / h2, o.ry / h2));
-    } else {
-        const double d = sqrt(f2 * h2);
-        o.c = f2 / d;
-        if (o.c >= safmin) { o.rx = f.x / o.c; o.ry = f.y / o.c; } else { const double q = h2 / d; o.rx = f.x * q; o.ry = f.y * q; }
-        sv = cmul(gc_, cmake(f.x / d, f.y / d));
-    }
-    o.sx = sv.x; o.sy = sv.y;
-    return o;
-}
-
 __device__ __forceinline__ c128 gw_block_sum(c128 v, c128* sbuf) {
     const double re = wave_sum_dpp(v.x), im = wave_sum_dpp(v.y);
     if ((threadIdx.x & 63) == 0) sbuf[threadIdx.x >> 6] = cmake(re, im);
@@ -675,43 +637,6 @@ __device__ __forceinline__ c128 gw_join(const c128* __restrict__ part, int np, c
     c128 acc = cmake(0.0, 0.0);
     for (int b = threadIdx.x; b < np; b += GW_BT) acc = cadd(acc, part[b]);
     return gw_block_sum(acc, sbuf);
-}
-
-// gmres_compact_kernel for the wide step: the same lists, the tick's (phase, col) of every active candidate, and what the host
-// needs to issue only the launches the tick has work for: out[0] = active candidates, out[1] = largest col among those in phase 0
-// (-1: none), out[2] = candidates in phase 1, out[3] = sum of col over phase 0 (the byte count of the profile class)
-__global__ void __launch_bounds__(1024)
-gmres_compact_wide_kernel(const GState* __restrict__ st, int count, int rows_per, int R, int* __restrict__ act,
-                          int* __restrict__ zrow, WState* __restrict__ ws, int* __restrict__ out) {
-    __shared__ int scnt[16];
-    __shared__ int sbase, smax, sp1, ssum;
-    if (threadIdx.x == 0) { sbase = 0; smax = -1; sp1 = 0; ssum = 0; }
-    __syncthreads();
-    int mx = -1, p1 = 0, sum = 0;
-    for (int k0 = 0; k0 < count; k0 += 1024) {
-        const int k = k0 + threadIdx.x;
-        const bool on = k < count && st[k].phase != 2;
-        const unsigned long long m = __ballot(on);
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        if (lane == 0) scnt[wave] = __popcll(m);
-        __syncthreads();
-        int off = sbase;
-        for (int w = 0; w < wave; ++w) off += scnt[w];
-        if (on) {
-            const int p = off + __popcll(m & ((1ull << lane) - 1ull));
-            const int ph = st[k].phase, col = st[k].col;
-            act[p] = k;
-            zrow[p] = k * rows_per + (ph == 1 ? R + 1 : col);
-            ws[k].phase = ph; ws[k].col = col; ws[k].cont = 0; ws[k].end = 0;
-            if (ph == 1) p1 += 1; else { mx = max(mx, col); sum += col; }
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < 16; ++w) t += scnt[w]; sbase += t; }
-        __syncthreads();
-    }
-    atomicMax(&smax, mx); atomicAdd(&sp1, p1); atomicAdd(&ssum, sum);     // integers: any order gives the same result
-    __syncthreads();
-    if (threadIdx.x == 0) { out[0] = sbase; out[1] = smax; out[2] = sp1; out[3] = ssum; }
 }
 
 struct WArgs {
@@ -782,22 +707,9 @@ gw_resid_kernel(GArgs a, const int* __restrict__ act, WArgs wa) {
     const double rnorm = sqrt(gw_join(wa.pn + (long)k * wa.np, wa.np, sbuf).x);
     if (threadIdx.x != 0) return;
     GState& s = a.st[k];
-    bool done = false; int info = 0;
-    double pmf = s.pmf, ptol = s.ptol; int cycle = s.cycle;
-    if (!(rnorm == rnorm)) { done = true; info = a.maxiter; }
-    else if (s.first) { if (rnorm < s.atol) { done = true; info = 0; } }
-    else {
-        if (rnorm <= s.atol) { done = true; info = 0; }
-        else if (s.breakdown) { done = true; info = a.maxiter; }
-        else {
-            if (s.presid <= s.ptol) pmf = fmax(EPS, 0.25 * pmf); else pmf = fmin(1.0, 1.5 * pmf);
-            ptol = s.presid * fmin(pmf, s.atol / rnorm);
-            cycle += 1;
-            if (cycle >= a.maxiter) { done = true; info = a.maxiter; }
-        }
-    }
-    if (done) { s.rnorm = rnorm; s.info = info; s.phase = 2; return; }
-    s.rnorm = rnorm; s.pmf = pmf; s.ptol = ptol; s.cycle = cycle; s.first = 0;
+    const Resid d = resid_decide(s, rnorm, a.maxiter);
+    if (d.done) { s.rnorm = rnorm; s.info = d.info; s.phase = 2; return; }
+    s.rnorm = rnorm; s.pmf = d.pmf; s.ptol = d.ptol; s.cycle = d.cycle; s.first = 0;
     W.cont = 1;
 }
 
@@ -889,8 +801,7 @@ gw_mgs_kernel(GArgs a, const int* __restrict__ act, WArgs wa, int kk) {
     }
 }
 
-// State: h0 and h1 from the joined partials, then gmres_post_stream_kernel's scalar tail as it stands (Hessenberg column,
-// rotations, S, presid, end_inner, the triangular solve, the next phase / col) on one lane per candidate
+// State: h0 and h1 from the joined partials, then arnoldi_tail on one lane per candidate, the Hessenberg column and y in WState
 __global__ void __launch_bounds__(GW_BT)
 gw_state_kernel(GArgs a, const int* __restrict__ act, WArgs wa) {
     __shared__ c128 sbuf[GW_BT / 64];
@@ -900,49 +811,10 @@ gw_state_kernel(GArgs a, const int* __restrict__ act, WArgs wa) {
     const c128 nn = gw_join(wa.pn + (long)k * wa.np, wa.np, sbuf);
     if (threadIdx.x != 0) return;
     GState& s = a.st[k];
-    const int col = W.col, R = a.R;
-    c128* s_h = W.hcol; c128* s_y = W.y;
     const double h0 = sqrt(nn.x), h1 = sqrt(nn.y);
     const bool brk = h1 <= EPS * h0;
     W.inv = brk ? 1.0 : 1.0 / h1;
-    s_h[col + 1] = cmake(brk ? 0.0 : h1, 0.0);
-    for (int kk = 0; kk < col; ++kk) {
-        const double c = s.gc[kk]; const c128 sg = s.gs[kk];
-        const c128 n0 = s_h[kk], n1 = s_h[kk + 1];
-        c128 a0 = cmake(c * n0.x, c * n0.y); cfma(a0, sg, n1);
-        c128 a1 = cmake(c * n1.x, c * n1.y); cfms(a1, cconj(sg), n0);
-        s_h[kk] = a0; s_h[kk + 1] = a1;
-    }
-    const GwRot rot = gw_zlartg(s_h[col], s_h[col + 1]);
-    const double c = rot.c; const c128 sg = cmake(rot.sx, rot.sy), mag = cmake(rot.rx, rot.ry);
-    s.gc[col] = c; s.gs[col] = sg;
-    s_h[col] = mag; s_h[col + 1] = cmake(0.0, 0.0);
-    const c128 Sc = s.S[col];
-    const c128 tmp = cmul(cmake(-sg.x, sg.y), Sc);
-    s.S[col] = cmake(c * Sc.x, c * Sc.y);
-    s.S[col + 1] = tmp;
-    const double presid = hypot(tmp.x, tmp.y);
-    s.presid = presid;
-    s.inner += 1;
-    for (int j = 0; j <= col + 1; ++j) s.h[col][j] = s_h[j];
-    if (brk) s.breakdown = 1;
-    const bool end_inner = (presid <= s.ptol) || brk || (col == R - 1);
-    W.end = end_inner ? 1 : 0;
-    if (end_inner) {
-        if (s.h[col][col].x == 0.0 && s.h[col][col].y == 0.0) s.S[col] = cmake(0.0, 0.0);
-        for (int j = 0; j <= col; ++j) s_y[j] = s.S[j];
-        for (int kk = col; kk > 0; --kk) {
-            if (s_y[kk].x != 0.0 || s_y[kk].y != 0.0) {
-                s_y[kk] = cdiv_np(s_y[kk], s.h[kk][kk]);
-                const c128 t = s_y[kk];
-                for (int j = 0; j < kk; ++j) cfms(s_y[j], t, s.h[kk][j]);
-            }
-        }
-        if (s_y[0].x != 0.0 || s_y[0].y != 0.0) s_y[0] = cdiv_np(s_y[0], s.h[0][0]);
-        s.phase = 1;
-    } else {
-        s.col = col + 1;
-    }
+    arnoldi_tail(s, W.hcol, W.y, &W.end, W.col, a.R, brk, h1);
 }
 
 // Finish: V[col + 1] = w * inv, and x += y @ V[:col + 1] where the inner loop ended
@@ -993,6 +865,14 @@ gmres_finish_kernel(GArgs a, c128* __restrict__ W, long ldw, int* __restrict__ i
         inner[k] = s.inner;
         status[k] = (info[k] == 0 && sbad) ? -2 : 0;
     }
+}
+
+// sparse matrix: every active candidate's product through the CSR operand (rows do not depend on the batch, so the shared first
+// product A x0 of rhs_mode 1 needs no special case)
+void csr_product(maus_ctx* c, const GArgs& a, const int* zrow, const int* act, int nact) {
+    const int n = a.n;
+    ProfScope ps(c, KC_SPMM, 8.0 * nact * c->Acsr.nnz, maus_spmm_operand_bytes(c->Acsr) * ((nact + 7) / 8) + 32.0 * nact * n);
+    maus_spmm_launch(c->st, c->Acsr, c->csr_sched, a.Vb, n, a.Y, n, zrow, act, nact);
 }
 
 }  // namespace
@@ -1067,15 +947,14 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
         // one read-back per tick, as below: how many candidates are active, the largest column among those in phase 0 and how
         // many are in phase 1 -- the host issues only the launches this tick has work for
         int h[4] = {0, -1, 0, 0};
-        hipLaunchKernelGGL(gmres_compact_wide_kernel, dim3(1), dim3(1024), 0, c->st, a.st, count, (int)rows_per, R, act, zrow, wa.ws, nact);
+        hipLaunchKernelGGL(gmres_compact_kernel<true>, dim3(1), dim3(1024), 0, c->st, a.st, count, (int)rows_per, R, act, zrow, wa.ws, nact);
         if (maus_d2h(c, h, nact, sizeof(int) * 4, c->st)) return -1;
         HIPCHK(c, hipStreamSynchronize(c->st));
         h_nact = h[0];
         if (h_nact <= 0) break;
         const int maxcol = h[1], n1 = h[2], n0 = h_nact - n1;
         if (maxcol >= R || (n0 > 0) != (maxcol >= 0)) FAIL(c, "maus_gmres: inconsistent tick summary of the wide step");
-        { ProfScope ps(c, KC_SPMM, 8.0 * h_nact * c->Acsr.nnz, maus_spmm_operand_bytes(c->Acsr) * ((h_nact + 7) / 8) + 32.0 * h_nact * n);
-          maus_spmm_launch(c->st, c->Acsr, c->csr_sched, a.Vb, n, a.Y, n, zrow, act, h_nact); }
+        csr_product(c, a, zrow, act, h_nact);
         // bytes: form 64 n per candidate; a Gram-Schmidt column 64 n (w in and out, V[kk - 1], V[kk]), the tail 48 n; finish 32 n;
         // a new cycle 64 n (x += y @ V of the candidates whose inner loop ends is not counted)
         ProfScope ps(c, KC_GMRES_WIDE, 0, (double)n * (64.0 * h_nact + 64.0 * h[3] + 80.0 * n0 + 64.0 * n1));
@@ -1094,17 +973,12 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
         }
     }
     for (long tick = 0; !wide && tick < max_ticks; ++tick) {
-        hipLaunchKernelGGL(gmres_compact_kernel, dim3(1), dim3(1024), 0, c->st, a.st, count, (int)rows_per, R, act, zrow, nact);
+        hipLaunchKernelGGL(gmres_compact_kernel<false>, dim3(1), dim3(1024), 0, c->st, a.st, count, (int)rows_per, R, act, zrow, (WState*)nullptr, nact);
         if (maus_d2h(c, &h_nact, nact, sizeof(int), c->st)) return -1;
         HIPCHK(c, hipStreamSynchronize(c->st));
         if (h_nact <= 0) break;
-        if (c->csr) {
-            // sparse matrix: every active candidate's product through the CSR operand (rows do not depend on the batch, so the
-            // shared first product A x0 of rhs_mode 1 needs no special case)
-            ProfScope ps(c, KC_SPMM, 8.0 * h_nact * c->Acsr.nnz, maus_spmm_operand_bytes(c->Acsr) * ((h_nact + 7) / 8) + 32.0 * h_nact * n);
-            maus_spmm_launch(c->st, c->Acsr, c->csr_sched, a.Vb, n, a.Y, n, zrow, act, h_nact);
-        } else
-        if (Hdense) {
+        if (c->csr) csr_product(c, a, zrow, act, h_nact);
+        else if (Hdense) {
             ProfScope ps(c, KC_VEC, 0, 16.0 * h_nact * (double)n * n);
             hipLaunchKernelGGL(gemv_dense_kernel, dim3((n + 15) / 16, h_nact), dim3(GT), 0, c->st, a, act, zrow);
         } else

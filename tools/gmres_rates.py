@@ -15,7 +15,13 @@ method one warm-up call, then the better of two timed calls.  Per row:
                             the 6.29 TB/s copy rate; under the default schedule and P workgroups it is also GB/s per workgroup
 Then MAUS_Solver linear loop bodies at n = 65536, P = 64 on the GMRES path under both methods.
 
-    python tools/gmres_rates.py [--out profiles/gmres_wide_rates.txt] [--quick]
+--register: instead, the register kernels of the default schedule, one row per instantiation of gmres_post_kernel, in the dense
+shared-matrix mode (diag(linspace(1, 3, n)) + 0.5 G / sqrt(n), P = 256 candidates, one workgroup each) at n = 1024, 4096, 8192
+and 12288, and one row of the dense mode (maus_gmres_pert, materialised H_k: gemv_dense_kernel + post) at n = 1024, P = 32.
+--post FILE writes `row <tab> post ms per solve` of every row, for comparisons between two builds of the library; MAUS_LIB
+names the build to load (default: the tree's).
+
+    python tools/gmres_rates.py [--out profiles/gmres_wide_rates.txt] [--quick] [--register] [--no-loop] [--post FILE]
 """
 import argparse
 import os
@@ -27,6 +33,8 @@ import scipy.sparse as sp
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from adaptive_matrix_solver_amd import _cabi  # noqa: E402
+if os.environ.get("MAUS_LIB"):                               # another build of the library, for before / after comparisons
+    _cabi.LIB_PATH = os.environ["MAUS_LIB"]
 
 COPY = 6.29e12
 BAR = 1.25
@@ -47,18 +55,22 @@ def tridiagonal(n, seed=14):
                     [-1, 0, 1], format="csr")
 
 
-def timed(ctx, method, P, shift, psi, jac):
+def timed(ctx, method, P, shift, psi, jac, dense=False):
     """(post-step profile record, wall seconds, info, inner, ticks) of the better of two timed solves after a warm-up."""
     ctx.gmres_set_method(method)
     klass = "gmres_wide" if method == _cabi.GMRES_WIDE else "vector"
     slots = np.arange(P)
-    ctx.gmres(slots, shift, psi, 0, jac)
+    if dense:
+        solve = lambda: ctx.gmres_pert(slots, shift, psi, 0, jac, _cabi.PERT_NONE, None)[:3]
+    else:
+        solve = lambda: ctx.gmres(slots, shift, psi, 0, jac)
+    solve()
     best = None
     for _ in range(2):
         ctx.profile_enable(False)
         ctx.profile_enable(True)
         t0 = time.perf_counter()
-        info, inner, status = ctx.gmres(slots, shift, psi, 0, jac)
+        info, inner, status = solve()
         wall = time.perf_counter() - t0
         pr = ctx.profile_read()
         assert (status == 0).all(), status
@@ -81,7 +93,33 @@ def launches_per_tick(inner, ticks, restart=20):
     return (total + 6 * resid) / max(1, int(inner) + resid)
 
 
-def row(ctx, name, n, P, out):
+def register_row(ctx, name, n, P, out, post, dense=False):
+    """One row of the --register table: the default schedule alone, post-step (vector class) and wall us per solve."""
+    rng = np.random.default_rng(2)
+    shift = 0.1 * (rng.standard_normal(P) + 1j * rng.standard_normal(P))
+    psi = np.full(P, 1e-3 if dense else 1e-20)
+    jac = np.zeros(P, dtype=np.int32)
+    ps, wall, info, inner, _ = timed(ctx, _cabi.GMRES_DEFAULT, P, shift, psi, jac, dense)
+    line = (f"{name:<22} n {n:>8} P {P:>4} | wall us/solve {1e6 * wall / P:9.3f} | post us/solve {1e3 * ps['ms'] / P:9.3f} | "
+            f"inner {int(inner.min())}..{int(inner.max())} converged {int((info == 0).sum())}/{P}")
+    print(line, flush=True)
+    out.append(line)
+    post.append((f"{name} n {n} P {P}", ps["ms"] / P))
+
+
+def bind_dense(ctx, n, P):
+    rng = np.random.default_rng(n)
+    A = (rng.standard_normal((n, n)) + 1j * rng.standard_normal((n, n))) * (0.5 / np.sqrt(n))
+    A[np.arange(n), np.arange(n)] += np.linspace(1.0, 3.0, n)
+    ctx.set_matrix(A)
+    ctx.pop_reserve(P)
+    rng = np.random.default_rng(1)
+    for k0 in range(0, P, 8):
+        k1 = min(P, k0 + 8)
+        ctx.pop_put(_cabi.POP_X, np.arange(k0, k1), rng.standard_normal((k1 - k0, n)) + 1j * rng.standard_normal((k1 - k0, n)))
+
+
+def row(ctx, name, n, P, out, post):
     rng = np.random.default_rng(2)
     shift = 0.1 * (rng.standard_normal(P) + 1j * rng.standard_normal(P))
     psi = np.full(P, 1e-20)
@@ -100,6 +138,8 @@ def row(ctx, name, n, P, out):
             f"inner {int(inner_w.min())}..{int(inner_w.max())} converged {int((info_w == 0).sum())}/{P} counts {'equal' if same else 'DIFFER'} | bar 1.25: {verdict}")
     print(line, flush=True)
     out.append(line)
+    post.append((f"{name} n {n} P {P} default", ps["ms"] / P))
+    post.append((f"{name} n {n} P {P} wide", pw["ms"] / P))
 
 
 def bind(ctx, A, P):
@@ -143,8 +183,24 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join("profiles", "gmres_wide_rates.txt"))
     ap.add_argument("--quick", action="store_true", help="n = 65536 only (a check of the tool, not the record)")
+    ap.add_argument("--register", action="store_true", help="the register kernels' table instead (dense modes, n <= 12288)")
+    ap.add_argument("--no-loop", action="store_true", help="leave out the MAUS_Solver loop bodies")
+    ap.add_argument("--post", default=None, help="write `row <tab> post ms per solve` of every row to this file")
     a = ap.parse_args()
     ctx = _cabi.Context(0)
+    post = []
+    if a.register:
+        out = [f"# tools/gmres_rates.py --register on {(ctx.device_info()['name'].strip() or 'the device')}: the default schedule's register kernels,",
+               "# one process; wall and post-step ('vector' class) us per solve, the better of two timed calls after a warm-up"]
+        print("\n".join(out), flush=True)
+        for n in (1024, 4096, 8192, 12288):
+            bind_dense(ctx, n, 256)
+            register_row(ctx, "dense shared", n, 256, out, post)
+        bind_dense(ctx, 1024, 32)
+        register_row(ctx, "dense H_k (gemv)", 1024, 32, out, post, dense=True)
+        ctx.close()
+        finish(a, out, post)
+        return
     out = [f"# tools/gmres_rates.py on {(ctx.device_info()['name'].strip() or 'the device')}: default schedule -> wide step (maus_gmres_set_method 0 -> 1), same systems,",
            "# one process; wall and post-step ms per solve (better of two timed calls after a warm-up), stream / wide in brackets;",
            "# TB/s: the wide step's algorithmic bytes over each method's post-step time, and as a share of the 6.29 TB/s copy rate"]
@@ -156,18 +212,26 @@ def main():
         A = make()
         bind(ctx, A, max(Ps))
         for P in Ps:
-            row(ctx, name, A.shape[0], P, out)
+            row(ctx, name, A.shape[0], P, out, post)
     ctx.close()
-    if not a.quick:
+    if not a.quick and not a.no_loop:
         for mode in ("auto", "wide"):
-            rate, post, spmm = loop_rate(mode)
+            rate, post_ms, spmm = loop_rate(mode)
             line = (f"MAUS_Solver linear loop bodies n 65536 P 64, GMRES path, sparse_gmres={mode:<5}: {rate:8.1f} candidate-steps/s, "
-                    f"post step {post:8.2f} ms/body, spmm {spmm:8.2f} ms/body")
+                    f"post step {post_ms:8.2f} ms/body, spmm {spmm:8.2f} ms/body")
             print(line, flush=True)
             out.append(line)
+    finish(a, out, post)
+
+
+def finish(a, out, post):
     os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
     with open(a.out, "w") as f:
         f.write("\n".join(out) + "\n")
+    if a.post:
+        os.makedirs(os.path.dirname(a.post) or ".", exist_ok=True)
+        with open(a.post, "w") as f:
+            f.write("".join(f"{name}\t{ms:.6f}\n" for name, ms in post))
 
 
 if __name__ == "__main__":
