@@ -26,6 +26,7 @@ SYMBOLS = [
     "maus_lanczos_begin", "maus_lanczos_inject", "maus_lanczos_extend", "maus_lanczos_restart", "maus_lanczos_finish", "maus_herm_match_rows", "maus_get_ritz_rows",
     "maus_sparse_max_n", "maus_band_prepare", "maus_band_reserve", "maus_band_solve", "maus_band_lu_host", "maus_band_workspace_allocs",
     "maus_band_set_method", "maus_band_get_method", "maus_band_kernel_for", "maus_band_outer_nb", "maus_band_plan",
+    "maus_band_set_split", "maus_band_get_split", "maus_band_split_plan",
     "maus_gmres_set_method", "maus_gmres_get_method", "maus_gmres_kernel_for",
     "maus_few_rows_set_method", "maus_few_rows_get_method", "maus_few_rows_kernel_for", "maus_few_rows_plan", "maus_few_rows_workspace_allocs",
     "maus_spmm_set_method", "maus_spmm_get_method", "maus_spmm_kernel_for", "maus_spmm_plan", "maus_spmm_sell_info",
@@ -40,6 +41,7 @@ KIND_EIG, KIND_LINEAR, KIND_SVD = 1, 2, 3
 PERT_NONE, PERT_UNIFORM, PERT_MT19937 = 0, 1, 2
 KC_NAMES = ["zgemm", "lu_panel", "trsm", "laswp", "build_h", "backsolve", "vector",
             "zgemm_k128", "zgemm_k64", "zgemm_k32", "zgemm_k16", "spmm", "band", "lanczos", "band_blocked", "band_tiled", "band_wide", "gmres_wide"]
+KC_BAND_SPLIT = len(KC_NAMES)      # band solves by the split method (maus_band_set_split): read as "band_split", behind the named classes
 BAND_COLUMN, BAND_BLOCKED, BAND_TILED, BAND_WIDE, BAND_NARROW = (      # maus_band_set_method: 0, 1, 2, 4, 8 (no 3, 5, 6, 7)
     DIRECT_METHOD[m] for m in ("band", "blocked", "tiled", "wide", "narrow"))
 GMRES_DEFAULT, GMRES_WIDE = 0, 1                     # maus_gmres_set_method
@@ -159,6 +161,9 @@ def load_library():
         "maus_spmm_sell_info": ([vp, C.c_int, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
         "maus_band_outer_nb": ([vp, C.c_int, C.c_int, C.c_int], C.c_int),
         "maus_band_plan": ([C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p, i32p, C.POINTER(C.c_int64)], C.c_int),
+        "maus_band_set_split": ([vp, C.c_int, C.c_int], C.c_int),
+        "maus_band_get_split": ([vp, ip], C.c_int),
+        "maus_band_split_plan": ([C.c_int] * 5 + [i32p] * 6 + [C.POINTER(C.c_int64)], C.c_int),
         "maus_device_count": ([], C.c_int),
         "maus_comm_unique_id": ([C.c_char_p], C.c_int),
         "maus_comm_init": ([vp, C.c_int, C.c_int, C.c_char_p], C.c_int),
@@ -261,7 +266,9 @@ class Context:
         return {"launches": n.value, "ms": ms.value, "flops": fl.value, "bytes": by.value, "union_ms": un.value}
 
     def profile_read(self):
-        return {name: self.profile_read_class(k) for k, name in enumerate(KC_NAMES)}
+        prof = {name: self.profile_read_class(k) for k, name in enumerate(KC_NAMES)}
+        prof["band_split"] = self.profile_read_class(KC_BAND_SPLIT)
+        return prof
 
     def lu_workspace_allocations(self) -> int:
         return int(self.lib.maus_lu_workspace_allocs(self.h))
@@ -656,6 +663,19 @@ class Context:
     def band_method(self) -> int:
         return int(self.lib.maus_band_get_method(self.h))
 
+    def band_set_split(self, on, part_len=0):
+        """The split beside the method (maus_band_set_split): on / off, part_len 0 for the rule or a forced partition length
+        (at least 2 (kl + ku) + 2, checked where a band is solved); kept across matrices."""
+        self._ck(self.lib.maus_band_set_split(self.h, int(bool(on)) if isinstance(on, bool) else int(on), int(part_len)),
+                 "maus_band_set_split")
+
+    def band_split(self):
+        """(on, forced partition length or 0) of maus_band_set_split."""
+        m = C.c_int()
+        on = self.lib.maus_band_get_split(self.h, C.byref(m))
+        self._ck(min(on, 0), "maus_band_get_split")
+        return bool(on), int(m.value)
+
     def band_kernel_for(self, n, kl, ku):
         """(kernel, nb) that an (n, kl, ku) band runs under the current method: (BAND_COLUMN, 1), (BAND_BLOCKED, nb),
         (BAND_TILED, nb), (BAND_WIDE, nb of the inner steps) or (BAND_NARROW, 1)."""
@@ -832,6 +852,16 @@ def band_plan(method, n, kl, ku):
     if load_library().maus_band_plan(int(method), int(n), int(kl), int(ku), C.byref(kind), C.byref(nb), C.byref(nbo), C.byref(per)) != 0:
         raise MausHipError(f"maus_band_plan: bad method or sizes ({method}, {n}, {kl}, {ku})")
     return int(kind.value), int(nb.value), int(nbo.value), int(per.value)
+
+
+def band_split_plan(method, n, kl, ku, part_len=0):
+    """(takes, partition length, partitions, n_red, kl_red, ku_red, bytes of the split's arrays per solve) of an (n, kl, ku)
+    band under `method` and part_len (maus_band_split_plan): needs neither a context nor a device."""
+    v = [C.c_int32() for _ in range(6)]
+    per = C.c_int64()
+    if load_library().maus_band_split_plan(int(method), int(n), int(kl), int(ku), int(part_len), *[C.byref(x) for x in v], C.byref(per)) != 0:
+        raise MausHipError(f"maus_band_split_plan: bad method, sizes or partition length ({method}, {n}, {kl}, {ku}, {part_len})")
+    return (bool(v[0].value),) + tuple(int(x.value) for x in v[1:]) + (int(per.value),)
 
 
 def few_rows_plan(method, slices, M, N, K, b_layout=1, conj_a=False, conj_b=False):

@@ -114,3 +114,53 @@ def band_bytes_per_solve(n: int, kl: int, ku: int, blocked: bool = False, tiled:
     if wide and runs_wide(kl, ku):
         per += 16 * (kl + WIDE_NBO) * WIDE_NBO
     return per
+
+
+# The split beside the method (sparse_split='on', maus_band_set_split; DESIGN §11 "The split method"), restated from
+# csrc/band.hip's split_plan; tests/test_band_split_host.py compares the two over every boundary.
+SPLIT_MAX_KL = NARROW_MAX_KL    # the narrow range without the diagonal case ...
+SPLIT_MAX_W = NARROW_MAX_KV     # ... and n above one partition length
+
+
+def split_len(n: int, kl: int, ku: int) -> int:
+    """The rule's partition length: 64 ceil(sqrt(n w) / 64) with w = kl + ku, at least 2 w + 2."""
+    import math
+    w = kl + ku
+    s = math.isqrt(n * w)
+    if s * s < n * w:
+        s += 1
+    return max((s + 63) // 64 * 64, 2 * w + 2)
+
+
+def _split_m(n: int, kl: int, ku: int, part_len: int) -> int:
+    if part_len and part_len < 2 * (kl + ku) + 2:
+        raise ValueError(f"the partition length must be at least 2 (kl + ku) + 2 = {2 * (kl + ku) + 2}, not {part_len}")
+    return part_len or split_len(n, kl, ku)
+
+
+def runs_split(n: int, kl: int, ku: int, part_len: int = 0) -> bool:
+    """Whether the split takes an (n, kl, ku) band when it is on: 1 <= kl + ku <= 31, kl <= 15 and at least two partitions."""
+    w = kl + ku
+    if w < 1 or kl > SPLIT_MAX_KL or w > SPLIT_MAX_W or n < 1:
+        return False
+    return n > _split_m(n, kl, ku, part_len)
+
+
+def split_shape(n: int, kl: int, ku: int, part_len: int = 0) -> tuple[int, int, int, int]:
+    """(p, n_red, kl_red, ku_red) of a band the split takes: partitions, and the order and half-bandwidths of the reduced
+    system in the separator unknowns."""
+    w = kl + ku
+    m = _split_m(n, kl, ku, part_len)
+    p = (n + m - 1) // m
+    n_red = (p - 1) * w
+    return p, n_red, min(kl + w - 1, n_red - 1), min(ku + w - 1, n_red - 1)
+
+
+def split_bytes_per_solve(n: int, kl: int, ku: int, part_len: int = 0, method: int = 0) -> int:
+    """Device memory the split adds to band_bytes_per_solve for a band it takes (0 for any other): the pivot rows
+    n (2 w + 2), the reduced system's own workspace under `method`, its solution, and three status words."""
+    if not runs_split(n, kl, ku, part_len):
+        return 0
+    w = kl + ku
+    _, n_red, klr, kur = split_shape(n, kl, ku, part_len)
+    return 16 * n * (2 * w + 2) + band_bytes_per_solve(n_red, klr, kur, method=method) + 16 * n_red + 12

@@ -1166,6 +1166,326 @@ void launch_narrow(const BandArgs& a, int G, hipStream_t st, c128* out, long ldo
     hipLaunchKernelGGL(band_narrow_back_kernel, dim3(G), dim3(64), 0, st, a, out, ldo, slots, perm);
 }
 
+// ---- the split method (maus_band_set_split(ctx, 1, part_len), DESIGN §11 "The split method") -----------------------------
+// One narrow band spread over the device: Gaussian elimination with partial pivoting on H Q, where Q lists the interiors of p
+// column partitions first and the separators between them last.  With w = kl + ku, partition i is the columns
+// [i m, min((i + 1) m, n)); all but the last end in a separator S_i of w columns, the rest is the interior I_i = [a_i, b_i].
+// The rows R_i = [i m - ku, (i + 1) m - ku) (cut to [0, n)) are the rows with an entry in I_i; they tile [0, n) and a row of
+// R_i has entries in S_{i-1}, I_i and S_i only.
+//   local    one group of GS lanes per (matrix, partition) eliminates the columns of I_i in ascending order, pivoting among the
+//            rows of R_i not yet used (first maximum of |re| + |im| in row order, a NaN never wins, a zero pivot records the
+//            column, the zero candidate nearest the diagonal leaves and the step goes on without an update).  The live rows (at most w + 1) sit in LDS, one column per lane:
+//            lanes 0 .. w - 1 the columns of S_{i-1} (fill), lanes w .. 2 w the band columns c .. c + w of step c (column c'
+//            in lane w + c' % (w + 1)), lane 2 w + 1 the right-hand side.  The pivot row of column c goes to pr[c][2 w + 2]
+//            (S_{i-1}, then columns c .. c + w, then the right-hand side); the rows left over at the end -- kl, w or ku of
+//            them, with entries in S_{i-1} and S_i only -- go straight into the band storage of the reduced system, in row
+//            order, the leftovers of partition i after those of partition i - 1.
+//   reduced  the leftover rows are a band matrix of order n_red = (p - 1) w in the separator unknowns with half-bandwidths
+//            kl + w - 1 and ku + w - 1 (cut to n_red - 1): launch_solve factors and solves it by the plan the context's
+//            method gives for that band.
+//   back     one group per (matrix, partition) solves I_i in descending order from the stored pivot rows: lane k holds the
+//            coefficient k of the row and the x it multiplies, the 2 w + 1 products are summed by a butterfly over the group
+//            (one fixed order), and the x of the band columns move up one lane per step.
+// Every choice is a function of (n, kl, ku, part_len) alone, and a group works on its own partition only: a system's bits do
+// not depend on the batch or the chunking.
+hipError_t launch_solve(const BandPlan& plan, const BandArgs& a, const BlkArgs& w, int G, hipStream_t st, c128* out, long ldo,
+                        const int* slots, const int* perm);
+size_t band_per_solve(const BandPlan& plan, int n, int kl, int ku);
+double band_flops(int n, int kl, int ku, int G);
+double band_bytes(const BandPlan& plan, int n, int kl, int ku, int G);
+
+constexpr int SPL_MAX_KL = NAR_MAX_KL;
+constexpr int SPL_MAX_W = NAR_MAX_KV;
+constexpr int SPL_NOINFO = 0x7f7f7f7f;                  // linfo after memset 0x7f: no zero pivot in the local phase
+
+struct SplitPlan {
+    bool on = false;                                    // the split takes the band
+    int w = 0, m = 0, p = 0, gs = 0;                    // kl + ku, partition length, partitions, lanes per group
+    int n_red = 0, kl_red = 0, ku_red = 0;
+    BandPlan rplan;                                     // of the reduced system under the context's method
+    size_t bytes = 0;                                   // of the split's arrays per solve
+};
+
+// the rule: m = 64 ceil(sqrt(n w) / 64), at least 2 w + 2 (the local phase's m steps against the reduced system's n w / m)
+int split_len(int n, int kl, int ku) {
+    const long w = kl + ku, nw = (long)n * w;
+    long s = (long)std::sqrt((double)nw);
+    while (s * s < nw) ++s;
+    while (s > 0 && (s - 1) * (s - 1) >= nw) --s;
+    return (int)std::max<long>((s + 63) / 64 * 64, 2 * w + 2);
+}
+
+// mode: the switch; part_len: 0 for the rule.  Returns false for a forced length below 2 w + 2 on a band in range.
+bool split_plan(int method, int mode, int part_len, int n, int kl, int ku, SplitPlan* sp) {
+    *sp = SplitPlan();
+    const int w = kl + ku;
+    if (!mode || w < 1 || kl > SPL_MAX_KL || w > SPL_MAX_W || n < 1) return true;
+    if (part_len && part_len < 2 * w + 2) return false;
+    const int m = part_len ? part_len : split_len(n, kl, ku);
+    if (n <= m) return true;                            // fewer than two partitions
+    sp->on = true; sp->w = w; sp->m = m; sp->p = (n + m - 1) / m;
+    sp->gs = 2 * w + 2 <= 8 ? 8 : (2 * w + 2 <= 16 ? 16 : (2 * w + 2 <= 32 ? 32 : 64));
+    sp->n_red = (sp->p - 1) * w;
+    sp->kl_red = std::min(kl + w - 1, sp->n_red - 1);
+    sp->ku_red = std::min(ku + w - 1, sp->n_red - 1);
+    sp->rplan = band_plan(method, sp->kl_red, sp->ku_red);
+    // pr, the reduced system's band_per_solve, its solution, and info / flags / the local phase's info
+    sp->bytes = sizeof(c128) * (size_t)n * (2 * w + 2) + band_per_solve(sp->rplan, sp->n_red, sp->kl_red, sp->ku_red)
+              + sizeof(c128) * (size_t)sp->n_red + 3 * sizeof(int);
+    return true;
+}
+
+// the split's arrays for G solves: pr[G][n][2 w + 2], the reduced system r (its x: the right-hand side), its solution
+// xs[G][n_red], the local phase's info linfo[G] and the reduced plan's panel
+struct SplitWs { c128* pr; BandArgs r; c128* xs; int* linfo; BlkArgs rw; };
+
+size_t split_carve(const SplitPlan& sp, int n, int G, char* base, SplitWs* ws) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return base + o; };
+    SplitWs s;
+    s.r.n = sp.n_red; s.r.kl = sp.kl_red; s.r.ku = sp.ku_red; s.r.ldab = 2 * sp.kl_red + sp.ku_red + 1;
+    s.pr = (c128*)take(sizeof(c128) * (size_t)n * (2 * sp.w + 2) * G);
+    s.r.ab = (c128*)take(sizeof(c128) * (size_t)s.r.ldab * sp.n_red * G);
+    s.r.x = (c128*)take(sizeof(c128) * (size_t)sp.n_red * G);
+    s.xs = (c128*)take(sizeof(c128) * (size_t)sp.n_red * G);
+    s.r.ipiv = (int*)take(sizeof(int) * (size_t)sp.n_red * G);
+    s.r.info = (int*)take(sizeof(int) * G);
+    s.r.flags = (int*)take(sizeof(int) * G);
+    s.linfo = (int*)take(sizeof(int) * G);
+    s.rw.lw = (c128*)take(sizeof(c128) * sp.rplan.lw * G);
+    s.rw.ju = (int*)take(sp.rplan.panel ? sizeof(int) * G : 0);
+    s.rw.lh = sp.kl_red + sp.rplan.nb; s.rw.ls = (long)s.rw.lh * sp.rplan.nb;
+    if (ws) *ws = s;
+    return off;
+}
+
+struct SplitArgs { c128* pr; int* linfo; int w, m, p; };
+
+// interior columns of partition i, and the longest interior among the NG partitions of a wave (the wave's trip count)
+__device__ __forceinline__ int split_ni(int p, int m, int w, int n, int i) { return i < p - 1 ? m - w : n - (p - 1) * m; }
+template <int NG>
+__device__ __forceinline__ int split_trips(int p, int m, int w, int n, int i0) {
+    int T = 0;
+    for (int q = 0; q < NG; ++q) if (i0 + q < p) T = max(T, split_ni(p, m, w, n, i0 + q));
+    return T;
+}
+
+template <int GS>
+__global__ void __launch_bounds__(64)
+band_split_local_kernel(BandArgs a, BandArgs r, SplitArgs s)
+{
+    constexpr int NG = 64 / GS, RS = GS / 2;
+    __shared__ c128 s_win[NG * RS * GS];
+    __shared__ c128 s_l[NG * RS];
+    __shared__ int s_row[NG * RS];
+    __shared__ int s_pv[NG];
+    const int g = blockIdx.y, grp = threadIdx.x / GS, l = threadIdx.x % GS;
+    const int i = blockIdx.x * NG + grp;
+    const bool act = i < s.p;
+    const int n = a.n, kl = a.kl, ku = a.ku, w = s.w, ldab = a.ldab, m = s.m;
+    const c128* ab = a.ab + bix(a, g);
+    const c128* x = a.x + (long)g * n;
+    int* ipiv = a.ipiv + (long)g * n;
+    c128* pr = s.pr + (long)g * n * (2 * w + 2);
+    const bool hasL = act && i > 0, hasR = act && i < s.p - 1;
+    const int a0 = act ? i * m : 0, ni = act ? split_ni(s.p, m, w, n, i) : 0;
+    const int rs0 = max(a0 - ku, 0), rend = hasR ? a0 + m - ku : n;     // R_i = [rs0, rend)
+    const int T = split_trips<NG>(s.p, m, w, n, blockIdx.x * NG);
+    const bool bandl = l >= w && l <= 2 * w;
+    c128* S = s_win + (long)grp * RS * GS + l;                          // this lane's column: row slot q at S[q * GS]
+    c128* sl = s_l + grp * RS;
+    int* srow = s_row + grp * RS;
+    auto elem = [&](int rr, int cc) -> c128 {
+        return (cc >= 0 && cc < n && rr - cc <= kl && cc - rr <= ku) ? ab[w + rr - cc + (long)cc * ldab] : cmake(0.0, 0.0);
+    };
+    // this lane's element of row rr while it owns band column mc
+    auto rowval = [&](int rr, int mc) -> c128 {
+        if (l < w) return hasL ? elem(rr, a0 - w + l) : cmake(0.0, 0.0);
+        if (l <= 2 * w) return elem(rr, mc);
+        return l == 2 * w + 1 ? x[rr] : cmake(0.0, 0.0);
+    };
+    int mycol = 0;
+    if (bandl) { const int sg = l - w, am = a0 % (w + 1); mycol = a0 + (sg - am + w + 1) % (w + 1); }
+    // the rows above a0 + kl are live before the first step, in slots 0 ..
+    const int ninit = act ? min(a0 + kl, rend) - rs0 : 0;
+    unsigned live = 0;
+    int fs = ninit;                                                     // the free slot the next row enters
+    for (int q = 0; q <= w; ++q) {
+        S[q * GS] = q < ninit ? rowval(rs0 + q, mycol) : cmake(0.0, 0.0);
+        if (l == 0) srow[q] = q < ninit ? rs0 + q : INT_MAX;
+        if (q < ninit) live |= 1u << q;
+    }
+    c128 inc = (ni > 0 && a0 + kl < rend) ? rowval(a0 + kl, mycol) : cmake(0.0, 0.0);   // the row that enters at the first step
+    for (int j = 0; j < T; ++j) {
+        const bool on = j < ni;
+        const int c = a0 + j;
+        const bool pl = on && bandl && mycol == c;                      // the lane of the pivot column
+        if (on) {
+            const int re = c + kl;
+            if (re < rend) { S[fs * GS] = inc; if (l == 0) srow[fs] = re; live |= 1u << fs; }
+            inc = (j + 1 < ni && re + 1 < rend) ? rowval(re + 1, pl ? c + w + 1 : mycol) : cmake(0.0, 0.0);
+        }
+        lds_barrier();
+        if (pl) {
+            double best = -1.0; int bs = -1, brow = INT_MAX;
+            for (int q = 0; q <= w; ++q)
+                if (live >> q & 1) {
+                    const double v = cabs1(S[q * GS]);
+                    const int row = srow[q];
+                    if (v > best || (v == best && row < brow)) { best = v; bs = q; brow = row; }   // NaN never wins (izamax)
+                }
+            if (!(best > 0.0)) {
+                // no pivot: the row that leaves is the zero candidate (any candidate where all are NaN) nearest the diagonal,
+                // the lower of two -- the row zgbtf2 leaves in place
+                int fd = INT_MAX; brow = INT_MAX;
+                for (int q = 0; q <= w; ++q)
+                    if ((live >> q & 1) && (best < 0.0 || cabs1(S[q * GS]) == 0.0)) {
+                        const int row = srow[q], d = abs(row - c);
+                        if (d < fd || (d == fd && row < brow)) { fd = d; bs = q; brow = row; }
+                    }
+            }
+            const c128 piv = S[bs * GS];
+            const bool zp = piv.x == 0.0 && piv.y == 0.0;
+            if (zp) atomicMin(&s.linfo[g], c + 1);
+            const c128 rc = zp ? cmake(0.0, 0.0) : crecip(piv);
+            for (int q = 0; q <= w; ++q) {
+                const bool upd = (live >> q & 1) && q != bs;
+                sl[q] = (upd && !zp) ? cmul(S[q * GS], rc) : cmake(0.0, 0.0);
+                if (q != bs) S[q * GS] = cmake(0.0, 0.0);                          // column c is eliminated: the slot becomes column c + w + 1
+            }
+            s_pv[grp] = bs;
+        }
+        lds_barrier();
+        if (on) {
+            const int bs = s_pv[grp];
+            const c128 u = S[bs * GS];
+            if (l <= 2 * w + 1) pr[(long)c * (2 * w + 2) + (bandl ? w + mycol - c : l)] = u;
+            if (l == 0) ipiv[c] = srow[bs] + 1;                         // 1-based row of H, as LAPACK counts
+            live &= ~(1u << bs);
+            if (!pl)
+                for (int q = 0; q <= w; ++q)
+                    if (live >> q & 1) { c128 v = S[q * GS]; cfms(v, sl[q], u); S[q * GS] = v; }
+            S[bs * GS] = cmake(0.0, 0.0);
+            fs = bs;
+            if (pl) mycol += w + 1;
+        }
+    }
+    lds_barrier();
+    if (!act) return;
+    // the rows left over, in row order, into the reduced system: columns of S_{i-1} at (i - 1) w .., of S_i at i w ..
+    const int rho0 = i == 0 ? 0 : kl + (i - 1) * w, kvr = r.kl + r.ku;
+    c128* rab = r.ab + bix(r, g);
+    int q_red = -1;
+    if (l < w) { if (hasL) q_red = (i - 1) * w + l; }
+    else if (bandl) { if (hasR && mycol < a0 + m) q_red = i * w + mycol - (a0 + m - w); }
+    for (int q = 0; q <= w; ++q) {
+        if (!(live >> q & 1)) continue;
+        int rank = 0;
+        for (int t = 0; t <= w; ++t) if ((live >> t & 1) && srow[t] < srow[q]) ++rank;
+        const int rho = rho0 + rank;
+        if (q_red >= 0) rab[kvr + rho - q_red + (long)q_red * r.ldab] = S[q * GS];
+        else if (l == 2 * w + 1) r.x[(long)g * r.n + rho] = S[q * GS];
+    }
+}
+
+template <int GS>
+__global__ void __launch_bounds__(64)
+band_split_back_kernel(BandArgs a, SplitArgs s, const c128* __restrict__ xs, int n_red, c128* __restrict__ out, long ldo,
+                       const int* __restrict__ slots, const int* __restrict__ perm)
+{
+    constexpr int NG = 64 / GS;
+    const int g = blockIdx.y, grp = threadIdx.x / GS, l = threadIdx.x % GS;
+    const int i = blockIdx.x * NG + grp;
+    const bool act = i < s.p;
+    const int n = a.n, w = s.w, m = s.m;
+    const c128* pr = s.pr + (long)g * n * (2 * w + 2);
+    const c128* xg = xs + (long)g * n_red;
+    c128* o = out + (slots ? (long)slots[g] : (long)g) * ldo;
+    const bool hasL = act && i > 0, hasR = act && i < s.p - 1;
+    const int a0 = act ? i * m : 0, ni = act ? split_ni(s.p, m, w, n, i) : 0, b0 = a0 + ni - 1;
+    const int T = split_trips<NG>(s.p, m, w, n, blockIdx.x * NG);
+    const bool mult = l < 2 * w + 1 && l != w;                          // a coefficient that multiplies an x
+    bool bad = false;
+    // lane k < w: x of column k of S_{i-1}; lane w + d, 1 <= d <= w: x of column c + d, at the start the columns of S_i
+    c128 xv = cmake(0.0, 0.0);
+    if (l < w) { if (hasL) xv = xg[(i - 1) * w + l]; }
+    else if (l > w && l <= 2 * w) { if (hasR) xv = xg[i * w + l - w - 1]; }
+    if (hasR && l < w) {                                                // the separator's own x
+        const c128 v = xg[i * w + l];
+        const int c = a0 + m - w + l;
+        o[perm ? perm[c] : c] = v; bad |= !cfinite(v);
+    }
+    c128 cur = (ni > 0 && l <= 2 * w + 1) ? pr[(long)b0 * (2 * w + 2) + l] : cmake(0.0, 0.0);
+    for (int j = 0; j < T; ++j) {
+        const bool on = j < ni;
+        const int c = b0 - j;
+        const c128 nxt = (j + 1 < ni && l <= 2 * w + 1) ? pr[(long)(c - 1) * (2 * w + 2) + l] : cmake(0.0, 0.0);
+        c128 t = l == 2 * w + 1 ? cur : cmake(0.0, 0.0);
+        if (mult) cfms(t, cur, xv);
+#pragma unroll
+        for (int off = GS / 2; off > 0; off >>= 1) { t.x += __shfl_xor(t.x, off, 64); t.y += __shfl_xor(t.y, off, 64); }
+        const c128 piv = cmake(__shfl(cur.x, grp * GS + w, 64), __shfl(cur.y, grp * GS + w, 64));
+        const c128 xc = cdiv(t, piv);
+        const c128 up = cmake(__shfl_up(xv.x, 1, 64), __shfl_up(xv.y, 1, 64));
+        if (on) {
+            if (l == 0) { o[perm ? perm[c] : c] = xc; bad |= !cfinite(xc); }
+            if (l == w + 1) xv = xc; else if (l > w + 1 && l <= 2 * w) xv = up;
+        }
+        cur = nxt;
+    }
+    if (bad) atomicOr(&a.flags[g], 2);
+}
+
+// The split solve of G matrices on `st`: the reduced system is zeroed, filled by the local phase, solved by its own plan
+// (no slots, no permutation: its x goes to xs), then the back substitution writes everything out.
+hipError_t launch_split(const SplitPlan& sp, const BandArgs& a, const SplitWs& ws, int G, hipStream_t st, c128* out, long ldo,
+                        const int* slots, const int* perm) {
+    const SplitArgs s{ws.pr, ws.linfo, sp.w, sp.m, sp.p};
+    const BandArgs& r = ws.r;
+    hipError_t err = hipMemsetAsync(r.ab, 0, sizeof(c128) * (size_t)r.ldab * r.n * G, st);
+    if (err == hipSuccess) err = hipMemsetAsync(r.info, 0, sizeof(int) * G, st);
+    if (err == hipSuccess) err = hipMemsetAsync(r.flags, 0, sizeof(int) * G, st);
+    if (err == hipSuccess) err = hipMemsetAsync(ws.linfo, 0x7f, sizeof(int) * G, st);
+    if (err != hipSuccess) return err;
+    const int ng = 64 / sp.gs;
+    const dim3 grid((sp.p + ng - 1) / ng, G);
+    switch (sp.gs) {
+    case 8: hipLaunchKernelGGL((band_split_local_kernel<8>), grid, dim3(64), 0, st, a, r, s); break;
+    case 16: hipLaunchKernelGGL((band_split_local_kernel<16>), grid, dim3(64), 0, st, a, r, s); break;
+    case 32: hipLaunchKernelGGL((band_split_local_kernel<32>), grid, dim3(64), 0, st, a, r, s); break;
+    default: hipLaunchKernelGGL((band_split_local_kernel<64>), grid, dim3(64), 0, st, a, r, s); break;
+    }
+    if ((err = hipGetLastError()) != hipSuccess) return err;
+    if ((err = launch_solve(sp.rplan, r, ws.rw, G, st, ws.xs, r.n, nullptr, nullptr)) != hipSuccess) return err;
+    switch (sp.gs) {
+    case 8: hipLaunchKernelGGL((band_split_back_kernel<8>), grid, dim3(64), 0, st, a, s, ws.xs, r.n, out, ldo, slots, perm); break;
+    case 16: hipLaunchKernelGGL((band_split_back_kernel<16>), grid, dim3(64), 0, st, a, s, ws.xs, r.n, out, ldo, slots, perm); break;
+    case 32: hipLaunchKernelGGL((band_split_back_kernel<32>), grid, dim3(64), 0, st, a, s, ws.xs, r.n, out, ldo, slots, perm); break;
+    default: hipLaunchKernelGGL((band_split_back_kernel<64>), grid, dim3(64), 0, st, a, s, ws.xs, r.n, out, ldo, slots, perm); break;
+    }
+    return hipGetLastError();
+}
+
+// band-order column of unknown q of the reduced system
+int split_sep_col(const SplitPlan& sp, int q) { return (q / sp.w + 1) * sp.m - sp.w + q % sp.w; }
+
+// info of the whole solve from the two phases: 1 + the smallest band-order column with a zero pivot, 0 for none
+int split_info(const SplitPlan& sp, int linfo, int rinfo) {
+    int info = linfo == SPL_NOINFO ? 0 : linfo;
+    if (rinfo > 0) { const int c = split_sep_col(sp, rinfo - 1) + 1; info = info ? std::min(info, c) : c; }
+    return info;
+}
+
+// flops of the elimination run: per interior column w rows over 2 w + 2 columns and the row's 2 w + 1 products in the back
+// substitution, plus the reduced system's; bytes: the band read once, pr written and read once, the reduced system's arrays
+double split_flops(const SplitPlan& sp, int n, int G) {
+    return 8.0 * G * (double)n * ((double)sp.w * (2 * sp.w + 2) + 2 * sp.w + 1) + band_flops(sp.n_red, sp.kl_red, sp.ku_red, G);
+}
+double split_bytes_moved(const SplitPlan& sp, int n, int kl, int ku, int G) {
+    return 16.0 * G * (double)n * (2 * kl + ku + 1 + 2) + 32.0 * G * (double)n * (2 * sp.w + 2)
+         + band_bytes(sp.rplan, sp.n_red, sp.kl_red, sp.ku_red, G);
+}
+
 // workgroup size from (kl, ku) alone: one wave for narrow bands, where the barriers of every column dominate
 int band_threads(int kl, int ku) {
     const long w = (long)kl * (kl + ku);
@@ -1255,9 +1575,9 @@ size_t band_per_solve(const BandPlan& plan, int n, int kl, int ku) {
 }
 
 void band_ws_free(maus_ctx* c) {
-    void* ps[] = {c->band_ab, c->band_x, c->band_ipiv, c->band_info, c->band_flags, c->band_lw, c->band_ju};
+    void* ps[] = {c->band_ab, c->band_x, c->band_ipiv, c->band_info, c->band_flags, c->band_lw, c->band_ju, c->band_sws};
     for (void* p : ps) if (p) (void)hipFree(p);
-    c->band_lw = nullptr; c->band_ju = nullptr;
+    c->band_lw = nullptr; c->band_ju = nullptr; c->band_sws = nullptr; c->band_ws_m = 0;
     c->band_ab = nullptr; c->band_x = nullptr; c->band_ipiv = nullptr; c->band_info = nullptr; c->band_flags = nullptr;
     c->band_g = 0; c->band_at_limit = false; c->band_ws_key = 0;
 }
@@ -1268,9 +1588,13 @@ void band_ws_free(maus_ctx* c) {
 int ensure_band_ws(maus_ctx* c, int want) {
     const int n = c->band_n, ldab = 2 * c->band_kl + c->band_ku + 1;
     const BandPlan plan = band_plan(c->band_method, c->band_kl, c->band_ku);
-    const size_t per = band_per_solve(plan, n, c->band_kl, c->band_ku);
-    const unsigned long long key = ((unsigned long long)n << 32) | ((unsigned long long)plan.panel << 31) | ((unsigned long long)(plan.nbo != 0) << 30) | (unsigned)ldab;
-    const bool same = c->band_ab && c->band_ws_key == key;
+    SplitPlan sp;
+    if (!split_plan(c->band_method, c->band_split, c->band_split_len, n, c->band_kl, c->band_ku, &sp))
+        FAIL(c, "band workspace: the partition length of maus_band_set_split is below 2 (kl + ku) + 2 for the bound band");
+    const size_t per = band_per_solve(plan, n, c->band_kl, c->band_ku) + sp.bytes;
+    const unsigned long long key = ((unsigned long long)n << 32) | ((unsigned long long)plan.panel << 31) | ((unsigned long long)(plan.nbo != 0) << 30)
+                                 | ((unsigned long long)sp.on << 29) | ((unsigned long long)sp.rplan.panel << 28) | (unsigned)ldab;
+    const bool same = c->band_ab && c->band_ws_key == key && c->band_ws_m == sp.m;
     if (same && (c->band_g >= want || c->band_at_limit)) return 0;
     size_t fr = 0, tot = 0;
     HIPCHK(c, hipMemGetInfo(&fr, &tot));
@@ -1298,6 +1622,8 @@ int ensure_band_ws(maus_ctx* c, int want) {
         HIPCHK(c, hipMalloc((void**)&c->band_lw, sizeof(c128) * plan.lw * G));
         HIPCHK(c, hipMalloc((void**)&c->band_ju, sizeof(int) * G));
     }
+    if (sp.on) HIPCHK(c, hipMalloc((void**)&c->band_sws, split_carve(sp, n, G, nullptr, nullptr)));
+    c->band_ws_m = sp.m;
     c->band_g = G; c->band_ws_key = key; c->band_allocs++;
     c->band_at_limit = same || G < G_asked || G >= std::min(cap, gmax);
     return 0;
@@ -1323,6 +1649,12 @@ void band_status(int G, const int* info, const int* flags, int32_t* status) {
         else if (flags[g] & 2) status[g] = -2;
         else status[g] = 0;
     }
+}
+
+// the solve of G matrices by the split where its plan takes the band, else by the method's plan
+hipError_t launch_any(const SplitPlan& sp, const SplitWs& ws, const BandPlan& plan, const BandArgs& a, const BlkArgs& w, int G, hipStream_t st,
+                      c128* out, long ldo, const int* slots, const int* perm) {
+    return sp.on ? launch_split(sp, a, ws, G, st, out, ldo, slots, perm) : launch_solve(plan, a, w, G, st, out, ldo, slots, perm);
 }
 
 }  // namespace
@@ -1401,24 +1733,32 @@ int maus_band_solve(maus_ctx* c, const int* slots, int count, const double* shif
     const BandArgs a = band_args(c);
     const BandPlan plan = band_plan(c->band_method, a.kl, a.ku);
     const BlkArgs w = blk_args(plan, a.kl, c->band_lw, c->band_ju);
+    SplitPlan sp;
+    SplitWs ws{};
+    (void)split_plan(c->band_method, c->band_split, c->band_split_len, a.n, a.kl, a.ku, &sp);   // checked by ensure_band_ws
+    if (sp.on) split_carve(sp, a.n, c->band_g, c->band_sws, &ws);
+    std::vector<int> h_rinfo(sp.on ? Gmax : 0);
     for (int off = 0; off < count; off += Gmax) {
         const int G = std::min(Gmax, count - off);
         if (maus_h2d(c, c->d_slots, slots + off, sizeof(int) * G, c->st)) return -1;
         if (maus_h2d(c, c->d_c1, shift + 2 * (size_t)off, sizeof(c128) * G, c->st)) return -1;
         if (maus_h2d(c, c->d_r1, psi + off, sizeof(double) * G, c->st)) return -1;
         {
-            ProfScope ps(c, plan.cls, band_flops(a.n, a.kl, a.ku, G), band_bytes(plan, a.n, a.kl, a.ku, G));
+            ProfScope ps(c, sp.on ? KC_BAND_SPLIT : plan.cls, sp.on ? split_flops(sp, a.n, G) : band_flops(a.n, a.kl, a.ku, G),
+                         sp.on ? split_bytes_moved(sp, a.n, a.kl, a.ku, G) : band_bytes(plan, a.n, a.kl, a.ku, G));
             HIPCHK(c, hipMemsetAsync(a.info, 0, sizeof(int) * G, c->st));
             HIPCHK(c, hipMemsetAsync(a.flags, 0, sizeof(int) * G, c->st));
             HIPCHK(c, hipMemsetAsync(a.ab, 0, sizeof(c128) * (size_t)a.ldab * a.n * G, c->st));
             hipLaunchKernelGGL(band_build_csr_kernel, dim3((a.n + 255) / 256, G), dim3(256), 0, c->st, a, c->Acsr.ptr, c->Acsr.idx,
                                c->Acsr.val, c->band_perm, c->band_iperm, c->d_c1, c->d_r1, rhs_mode, c->X, c->ldp, c->d_slots, c->b);
-            HIPCHK(c, launch_solve(plan, a, w, G, c->st, c->W, c->ldp, c->d_slots, c->band_perm));
+            HIPCHK(c, launch_any(sp, ws, plan, a, w, G, c->st, c->W, c->ldp, c->d_slots, c->band_perm));
         }
-        if (maus_d2h(c, h_info.data(), a.info, sizeof(int) * G, c->st)) return -1;
+        if (maus_d2h(c, h_info.data(), sp.on ? ws.linfo : a.info, sizeof(int) * G, c->st)) return -1;
+        if (sp.on && maus_d2h(c, h_rinfo.data(), ws.r.info, sizeof(int) * G, c->st)) return -1;
         if (maus_d2h(c, h_flags.data(), a.flags, sizeof(int) * G, c->st)) return -1;
         HIPCHK(c, hipStreamSynchronize(c->st));
         HIPCHK(c, hipGetLastError());
+        if (sp.on) for (int g = 0; g < G; ++g) h_info[g] = split_info(sp, h_info[g], h_rinfo[g]);
         band_status(G, h_info.data(), h_flags.data(), status + off);
     }
     return 0;
@@ -1460,6 +1800,35 @@ int maus_band_plan(int method, int n, int kl, int ku, int32_t* kind, int32_t* nb
     return 0;
 }
 
+int maus_band_set_split(maus_ctx* c, int mode, int part_len) {
+    if (!c) return -1;
+    if ((mode != 0 && mode != 1) || part_len < 0)
+        FAIL(c, "maus_band_set_split: mode must be 0 (off) or 1 (on), part_len 0 (the rule) or a partition length");
+    c->band_split = mode; c->band_split_len = part_len;                 // the workspace follows at its next use (ensure_band_ws)
+    return 0;
+}
+
+int maus_band_get_split(maus_ctx* c, int* part_len_out) {
+    if (!c) return -1;
+    if (part_len_out) *part_len_out = c->band_split_len;
+    return c->band_split;
+}
+
+int maus_band_split_plan(int method, int n, int kl, int ku, int part_len, int32_t* takes, int32_t* part_len_out, int32_t* parts,
+                         int32_t* n_red, int32_t* kl_red, int32_t* ku_red, int64_t* ws_bytes_per_solve) {
+    if (!band_method_ok(method) || n < 0 || kl < 0 || ku < 0 || part_len < 0) return -1;
+    SplitPlan sp;
+    if (!split_plan(method, 1, part_len, n, kl, ku, &sp)) return -1;
+    if (takes) *takes = sp.on;
+    if (part_len_out) *part_len_out = sp.m;
+    if (parts) *parts = sp.p;
+    if (n_red) *n_red = sp.n_red;
+    if (kl_red) *kl_red = sp.kl_red;
+    if (ku_red) *ku_red = sp.ku_red;
+    if (ws_bytes_per_solve) *ws_bytes_per_solve = (int64_t)sp.bytes;
+    return 0;
+}
+
 int maus_band_lu_host(maus_ctx* c, int count, int n, int kl, int ku, const double* ab, const double* b, double* x_out,
                       int32_t* ipiv_out, int32_t* info_out) {
     if (!c) return -1;
@@ -1474,28 +1843,44 @@ int maus_band_lu_host(maus_ctx* c, int count, int n, int kl, int ku, const doubl
                  o_i = take(sizeof(int) * count), o_f = take(sizeof(int) * count);
     const BandPlan plan = band_plan(c->band_method, kl, ku);
     const size_t o_l = take(sizeof(c128) * plan.lw * count), o_j = take(plan.panel ? sizeof(int) * count : 0);
+    SplitPlan sp;
+    if (!split_plan(c->band_method, c->band_split, c->band_split_len, n, kl, ku, &sp))
+        FAIL(c, "maus_band_lu_host: the partition length of maus_band_set_split is below 2 (kl + ku) + 2 for this band");
+    const size_t o_s = take(sp.on ? split_carve(sp, n, count, nullptr, nullptr) : 0);
     if (ensure_scratch(c, off)) return -1;
     char* base = (char*)c->scratch;
     a.ab = (c128*)(base + o_ab); a.x = (c128*)(base + o_x); a.ipiv = (int*)(base + o_p); a.info = (int*)(base + o_i); a.flags = (int*)(base + o_f);
     c128* out = (c128*)(base + o_o);
     const BlkArgs w = blk_args(plan, kl, plan.panel ? (c128*)(base + o_l) : nullptr, plan.panel ? (int*)(base + o_j) : nullptr);
+    SplitWs ws{};
+    if (sp.on) split_carve(sp, n, count, base + o_s, &ws);
     if (maus_stage_h2d(c, a.ab, ab, abb * count, c->st)) return -1;
     if (maus_stage_h2d(c, a.x, b, xb * count, c->st)) return -1;
     HIPCHK(c, hipMemsetAsync(a.info, 0, sizeof(int) * count, c->st));
     HIPCHK(c, hipMemsetAsync(a.flags, 0, sizeof(int) * count, c->st));
     {
-        ProfScope ps(c, plan.cls, band_flops(n, kl, ku, count), band_bytes(plan, n, kl, ku, count));
+        ProfScope ps(c, sp.on ? KC_BAND_SPLIT : plan.cls, sp.on ? split_flops(sp, n, count) : band_flops(n, kl, ku, count),
+                     sp.on ? split_bytes_moved(sp, n, kl, ku, count) : band_bytes(plan, n, kl, ku, count));
         hipLaunchKernelGGL(band_scan_kernel, dim3(64, count), dim3(256), 0, c->st, a);
-        if (plan.panel) hipLaunchKernelGGL(band_zero_fill_kernel, dim3(64, count), dim3(256), 0, c->st, a);
-        HIPCHK(c, launch_solve(plan, a, w, count, c->st, out, n, nullptr, nullptr));
+        if (plan.panel && !sp.on) hipLaunchKernelGGL(band_zero_fill_kernel, dim3(64, count), dim3(256), 0, c->st, a);
+        HIPCHK(c, launch_any(sp, ws, plan, a, w, count, c->st, out, n, nullptr, nullptr));
     }
-    std::vector<int> h_info(count), h_flags(count);
+    std::vector<int> h_info(count), h_flags(count), h_rinfo(sp.on ? count : 0), h_ripiv(sp.on && ipiv_out ? (size_t)sp.n_red * count : 0);
     if (maus_stage_d2h(c, x_out, out, xb * count, c->st)) return -1;
     if (ipiv_out && maus_stage_d2h(c, ipiv_out, a.ipiv, ib * count, c->st)) return -1;
-    if (maus_d2h(c, h_info.data(), a.info, sizeof(int) * count, c->st)) return -1;
+    if (!h_ripiv.empty() && maus_stage_d2h(c, h_ripiv.data(), ws.r.ipiv, sizeof(int) * h_ripiv.size(), c->st)) return -1;
+    if (maus_d2h(c, h_info.data(), sp.on ? ws.linfo : a.info, sizeof(int) * count, c->st)) return -1;
+    if (sp.on && maus_d2h(c, h_rinfo.data(), ws.r.info, sizeof(int) * count, c->st)) return -1;
     if (maus_d2h(c, h_flags.data(), a.flags, sizeof(int) * count, c->st)) return -1;
     HIPCHK(c, hipStreamSynchronize(c->st));
     HIPCHK(c, hipGetLastError());
+    if (sp.on) {
+        for (int g = 0; g < count; ++g) h_info[g] = split_info(sp, h_info[g], h_rinfo[g]);
+        // a separator column carries the pivot of its unknown of the reduced system (LAPACK's 1-based row of that system)
+        if (ipiv_out)
+            for (int g = 0; g < count; ++g)
+                for (int q = 0; q < sp.n_red; ++q) ipiv_out[(size_t)g * n + split_sep_col(sp, q)] = h_ripiv[(size_t)g * sp.n_red + q];
+    }
     band_status(count, h_info.data(), h_flags.data(), info_out);
     return 0;
 }

@@ -109,4 +109,4 @@ static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 // kernel classes for the profiling counters (maus_profile_read)
 enum { KC_GEMM = 0, KC_PANEL = 1, KC_TRSM = 2, KC_LASWP = 3, KC_BUILD = 4, KC_BACKSOLVE = 5, KC_VEC = 6,
-       KC_GEMM_K128 = 7, KC_GEMM_K64 = 8, KC_GEMM_K32 = 9, KC_GEMM_K16 = 10, KC_SPMM = 11, KC_BAND = 12, KC_LANCZOS = 13, KC_BAND_BLOCKED = 14, KC_BAND_TILED = 15, KC_BAND_WIDE = 16, KC_GMRES_WIDE = 17, KC_COUNT = 18 };   // 7..10: LU recursion GEMMs by K (<256); 11: CSR products (spmm.hip); 12: band solves (band.hip); 13: Lanczos reorthogonalisation, restart and match (lanczos.hip); 14: band solves by the blocked method (band.hip); 15: band solves by the tiled method (band.hip); 16: band solves by the wide method (band.hip); 17: the wide GMRES post step (gmres.hip)
+       KC_GEMM_K128 = 7, KC_GEMM_K64 = 8, KC_GEMM_K32 = 9, KC_GEMM_K16 = 10, KC_SPMM = 11, KC_BAND = 12, KC_LANCZOS = 13, KC_BAND_BLOCKED = 14, KC_BAND_TILED = 15, KC_BAND_WIDE = 16, KC_GMRES_WIDE = 17, KC_BAND_SPLIT = 18, KC_COUNT = 19 };   // 7..10: LU recursion GEMMs by K (<256); 11: CSR products (spmm.hip); 12: band solves (band.hip); 13: Lanczos reorthogonalisation, restart and match (lanczos.hip); 14: band solves by the blocked method (band.hip); 15: band solves by the tiled method (band.hip); 16: band solves by the wide method (band.hip); 17: the wide GMRES post step (gmres.hip); 18: band solves by the split method (band.hip)

@@ -249,6 +249,17 @@ def sparse_direct_mode(mode):
     return mode
 
 
+SPARSE_SPLIT_MODES = ("off", "on")
+
+
+def sparse_split_mode(mode):
+    """The `sparse_split` keyword: an explicit value, else MAUS_SPARSE_SPLIT, else 'off'."""
+    mode = mode if mode is not None else os.environ.get("MAUS_SPARSE_SPLIT", "off")
+    if mode not in SPARSE_SPLIT_MODES:
+        raise ValueError(f"sparse_split must be one of {SPARSE_SPLIT_MODES}, not {mode!r}")
+    return mode
+
+
 SPARSE_GMRES_MODES = ("auto", "wide")
 
 
@@ -382,7 +393,7 @@ class DeviceEngine:
 
     def __init__(self, device: int = 0, pert_mode: str = "auto", gmres_compat: str = "rtol",
                  comm=None, ctx=None, eigh_mode: str = "auto", sparse_mode=None, sparse_direct=None, sparse_eigsh=None,
-                 sparse_gmres=None, few_rows=None, sparse_spmm=None):
+                 sparse_gmres=None, few_rows=None, sparse_spmm=None, sparse_split=None):
         self.ctx = ctx if ctx is not None else _cabi.Context(device)
         cap_blas_threads()
         # Hermitian eigendecomposition (AMS:161), once per matrix: 'host' = scipy.linalg.eigh, the reference's call, (lambda, V)
@@ -404,6 +415,13 @@ class DeviceEngine:
         # kernel's steps run by one wave per matrix on an LDS ring of columns, for kl <= 15 and kl + ku <= 31 (opt-in too,
         # the column kernel's bits).  MAUS_SPARSE_DIRECT sets the default.  Chosen once per bound matrix (_band).
         self.sparse_direct = sparse_direct_mode(sparse_direct)
+        # a switch beside sparse_direct (DESIGN §11 "The split method"): 'on' spreads one narrow band (1 <= kl + ku <= 31,
+        # kl <= 15, n above one partition length) over the device -- partial pivoting on the matrix with the interiors of
+        # ~sqrt(n / (kl + ku)) column partitions ordered first, the separators between them as a reduced band system that the
+        # method of sparse_direct solves; every other band runs what sparse_direct runs.  Opt-in, 'auto' never picks it; x
+        # agrees to rounding, not bit for bit (another pivot order).  MAUS_SPARSE_SPLIT sets the default.  Told to the
+        # context with the ordering (prepare_band).
+        self.sparse_split = sparse_split_mode(sparse_split)
         # GMRES of a sparse matrix: 'auto' = the post step of csrc/gmres.hip with one workgroup per candidate, as
         # ever; 'wide' = the same step with n split over workgroups of 512 entries and every sum joined in a fixed order, so
         # that a few candidates at large n occupy the whole device (opt-in, 'auto' never picks it; x agrees to rounding, not
@@ -535,6 +553,8 @@ class DeviceEngine:
             perm, kl, ku = self.band_shape(self._bound)
             if DIRECT_METHOD.get(self.sparse_direct):   # 'band' does not touch the method: contexts without it keep working
                 self.ctx.band_set_method(DIRECT_METHOD[self.sparse_direct])
+            if self.sparse_split == "on":               # 'off' does not touch the switch: contexts without it keep working
+                self.ctx.band_set_split(True, 0)
             self.ctx.band_prepare(perm)
             self._band_ready = True
 

@@ -30,9 +30,9 @@ import numpy as np
 
 from . import _cabi
 from ._cabi import POP_U, POP_X
-from .band import DIRECT_METHOD, band_bytes_per_solve, band_order
+from .band import DIRECT_METHOD, band_bytes_per_solve, band_order, split_bytes_per_solve
 from .candstore import C_NP as _C_NP, C_PY as _C_PY, EXACT as _EXACT, F_NP as _F_NP, F_PY as _F_PY, HREF as _HREF, MISSING as _MISSING
-from .engine import DIRECT, GMRES, DeviceEngine, _advance_numpy_stream, few_rows_mode, sparse_direct_mode, sparse_eigsh_mode, sparse_gmres_mode, sparse_spmm_mode
+from .engine import DIRECT, GMRES, DeviceEngine, _advance_numpy_stream, few_rows_mode, sparse_direct_mode, sparse_eigsh_mode, sparse_gmres_mode, sparse_split_mode, sparse_spmm_mode
 
 
 class ProblemType(Enum):                     # AMS:10-13
@@ -162,7 +162,7 @@ class InverseIterateSolver:
 
     def __init__(self, N, base_psi_epsilon, max_attempts, preferred_method="direct_solve", is_sparse=False,
                  gmres_compat="rtol", pert_mode="uniform", sparse_mode=None, sparse_direct=None, sparse_gmres=None,
-                 few_rows=None, sparse_spmm=None):
+                 few_rows=None, sparse_spmm=None, sparse_split=None):
         self.N = N
         self.base_psi_epsilon = base_psi_epsilon
         self.max_attempts = max_attempts
@@ -174,6 +174,7 @@ class InverseIterateSolver:
         self.sparse_mode = _sparse_mode(sparse_mode)
         self.sparse_direct = sparse_direct_mode(sparse_direct)
         self.sparse_gmres = sparse_gmres_mode(sparse_gmres)
+        self.sparse_split = sparse_split_mode(sparse_split)
         self.few_rows = few_rows_mode(few_rows)
         self.sparse_spmm = sparse_spmm_mode(sparse_spmm)
         self.last_trace = []
@@ -222,6 +223,11 @@ class InverseIterateSolver:
                     ctx.band_set_method(method)
                 elif getattr(ctx, "band_method", None) is not None and ctx.band_method() != _cabi.BAND_COLUMN:
                     ctx.band_set_method(_cabi.BAND_COLUMN)
+                # ... and the split beside it ('on' is opt-in)
+                if self.sparse_split == "on":
+                    ctx.band_set_split(True, 0)
+                elif getattr(ctx, "band_split", None) is not None and ctx.band_split()[0]:
+                    ctx.band_set_split(False, 0)
                 ctx.band_prepare(band_order(A_sp)[0])
         else:
             band = False
@@ -778,8 +784,9 @@ class MAUS_Solver:
                  global_convergence_tol=1e-8, *, device=0, pert_mode="auto", gmres_compat="rtol",
                  record_history=None, comm=None, quiet=False, engine=None, gram_min=8, cond_exact_max=1024,
                  diag_info=None, eigh_mode="auto", sparse_mode=None, sparse_direct=None, sparse_eigsh=None,
-                 sparse_hermitian_check=None, sparse_gmres=None, few_rows=None, sparse_spmm=None):
+                 sparse_hermitian_check=None, sparse_gmres=None, few_rows=None, sparse_spmm=None, sparse_split=None):
         few_rows = few_rows_mode(few_rows)
+        sparse_split = sparse_split_mode(sparse_split)
         sparse_spmm = sparse_spmm_mode(sparse_spmm)
         sparse_mode = _sparse_mode(sparse_mode)
         sparse_direct = sparse_direct_mode(sparse_direct)
@@ -809,7 +816,8 @@ class MAUS_Solver:
                                                                      gmres_compat=gmres_compat, comm=comm, eigh_mode=eigh_mode,
                                                                      sparse_mode=sparse_mode, sparse_direct=sparse_direct,
                                                                      sparse_eigsh=sparse_eigsh, sparse_gmres=sparse_gmres,
-                                                                     few_rows=few_rows, sparse_spmm=sparse_spmm)
+                                                                     few_rows=few_rows, sparse_spmm=sparse_spmm,
+                                                                     sparse_split=sparse_split)
         # `diag_info`: start-up diagnostics of the same matrix taken from an earlier solver (bench side runs)
         if diag_info is not None:
             self.diag_info = dict(diag_info)
@@ -1445,6 +1453,8 @@ class MAUS_Solver:
         perm, kl, ku = self.engine.band_shape(self.M)
         direct = getattr(self.engine, "sparse_direct", None)
         per = band_bytes_per_solve(n, kl, ku, method=DIRECT_METHOD.get(direct, 0))
+        if getattr(self.engine, "sparse_split", "off") == "on":         # the split's arrays where it takes the band, else 0
+            per += split_bytes_per_solve(n, kl, ku, method=DIRECT_METHOD.get(direct, 0))
         hbm = int(ctx.device_info()["hbm_total"])
         if per * 16 > hbm:
             raise NotImplementedError(f"sparse eigenvalue / linear problem too wide for the band solve: n = {n}, kl = {kl}, "

@@ -136,7 +136,27 @@ int maus_matrix_is_sparse(maus_ctx* ctx);
  * maus_band_plan: the same answers for any `method`, without a context and without opening a device: kind and nb as
  *   maus_band_kernel_for, outer_nb as maus_band_outer_nb, ws_bytes_per_solve the workspace bytes of one solve (what
  *   maus_band_reserve allocates per solve).  Every out pointer may be NULL.  Returns 0, or -1 for a method that
- *   maus_band_set_method refuses or a negative size. */
+ *   maus_band_set_method refuses or a negative size.
+ * maus_band_set_split: a switch beside the method (DESIGN §11 "The split method"): mode 1 solves a band with
+ *   1 <= kl + ku <= 31, kl <= 15 and n above one partition length by Gaussian elimination with partial pivoting on the
+ *   column-reordered matrix -- the interiors of p column partitions first (one group of lanes per partition, all at once),
+ *   then the (p - 1)(kl + ku) separator columns as a reduced band system that the method's own kernels factor and solve.
+ *   Every other band runs exactly what the method runs.  part_len: 0 for the rule (64 ceil(sqrt(n (kl + ku)) / 64)), else
+ *   the partition length, which must be at least 2 (kl + ku) + 2 -- checked where a band is solved or its workspace sized,
+ *   which then fail.  mode 0 (the default) is the method alone, bit for bit.  A mode other than 0 / 1 or a negative
+ *   part_len is refused and changes nothing.  Same status contract; a positive status is 1 + the smallest band-order column
+ *   with a zero pivot in either phase.  The pivot order differs from zgbtrf's: x agrees to rounding, not bit for bit.
+ *   Under the split, maus_band_lu_host's ipiv_out holds, for an interior column, the 1-based row of the matrix that was its
+ *   pivot row, and for the separator column (i + 1) part_len - (kl + ku) + t of partition i (0 <= t < kl + ku) the
+ *   1-based pivot row, in the reduced system's own row numbering, of its unknown i (kl + ku) + t (zgbtrf's ipiv of that
+ *   system: row kl + (i - 1)(kl + ku) + s of it is the s-th leftover row, in row order, of partition i >= 1; the kl
+ *   leftover rows of partition 0 come first).
+ * maus_band_get_split: returns the mode; part_len_out (may be NULL): the forced partition length, 0 for the rule.
+ * maus_band_split_plan: what the split would do with (n, kl, ku) under `method` and part_len, without a context or a
+ *   device: takes (0 / 1), the partition length, the number of partitions, the reduced system's order and half-bandwidths,
+ *   and the bytes of the split's arrays per solve (what the workspace adds to maus_band_plan's).  Where takes = 0 the rest
+ *   are 0.  Every out pointer may be NULL.  Returns 0, or -1 for a bad method, a negative size, or a part_len below
+ *   2 (kl + ku) + 2 on a band in the split's range. */
 int maus_sparse_max_n(void);
 int maus_band_prepare(maus_ctx* ctx, const int32_t* perm, int n, int* kl_out, int* ku_out);
 int maus_band_reserve(maus_ctx* ctx, int count, int* capacity_out);
@@ -151,6 +171,10 @@ int maus_band_kernel_for(maus_ctx* ctx, int n, int kl, int ku, int* nb_out);
 int maus_band_outer_nb(maus_ctx* ctx, int n, int kl, int ku);
 int maus_band_plan(int method, int n, int kl, int ku, int32_t* kind, int32_t* nb, int32_t* outer_nb,
                    int64_t* ws_bytes_per_solve);
+int maus_band_set_split(maus_ctx* ctx, int mode, int part_len);
+int maus_band_get_split(maus_ctx* ctx, int* part_len_out);
+int maus_band_split_plan(int method, int n, int kl, int ku, int part_len, int32_t* takes, int32_t* part_len_out, int32_t* parts,
+                         int32_t* n_red, int32_t* kl_red, int32_t* ku_red, int64_t* ws_bytes_per_solve);
 
 /* Upload b (AMS:146, 275). */
 int maus_set_rhs(maus_ctx* ctx, const double* b_c128, int n);

@@ -280,7 +280,7 @@ def diagonals(n, k, seed=0):
     return sp.diags([rng.standard_normal(n - abs(o)) + 1j * rng.standard_normal(n - abs(o)) for o in offs], offs, format="csr")
 
 
-def loop_rate_narrow(direct, n=262144, P=64, bodies=3):
+def loop_rate_narrow(direct, n=262144, P=64, bodies=3, split="off"):
     """Candidate-steps per second and band-class ms per body of MAUS_Solver linear loop bodies on a tridiagonal operator
     (diagonal near 4 + i, off-diagonals of modulus <= 1) with every solve a band solve."""
     import random
@@ -293,7 +293,7 @@ def loop_rate_narrow(direct, n=262144, P=64, bodies=3):
     diag = {"is_sparse_init": True, "condition_number": 1e7, "is_singular": False, "is_hermitian": False,
             "is_complex_symmetric": False}
     s = MAUS_Solver(A, ProblemType.SOLVE_LINEAR_SYSTEM, b_vector=b, initial_num_candidates=P, quiet=True, sparse_mode="device",
-                    gmres_compat="scipy-legacy", sparse_direct=direct, diag_info=diag)
+                    gmres_compat="scipy-legacy", sparse_direct=direct, sparse_split=split, diag_info=diag)
     s.loop_body(1)
     ctx = s.engine.ctx
     ctx.profile_enable(False)
@@ -306,7 +306,7 @@ def loop_rate_narrow(direct, n=262144, P=64, bodies=3):
     wall = time.perf_counter() - t0
     pr = ctx.profile_read()
     ctx.profile_enable(False)
-    return steps / wall, pr["band"]["ms"] / bodies
+    return steps / wall, (pr["band"]["ms"] + pr["band_split"]["ms"]) / bodies
 
 
 def main_narrow(args):
@@ -358,16 +358,83 @@ def main_narrow(args):
     flush()
 
 
+def main_split(args):
+    """The split beside the narrow method (the baseline) on the same systems in one process, at the rule's partition length m,
+    at m / 2 and at 2 m."""
+    from adaptive_matrix_solver_amd.band import split_len, split_shape
+    ctx = _cabi.Context(0)
+    info = ctx.device_info()
+    head = (f"{'n':>8} {'kl':>3} {'ku':>3} {'batch':>5} {'narrow ms':>10} {'m':>6} {'p':>5} {'n_red':>6} {'split m/2':>10} {'split m':>10} "
+            f"{'split 2m':>10} {'TB/s at m':>9} {'of 8 TB/s':>9} {'narrow/split':>12} {'1.25x bar':>9}")
+    lines = [f"# band solves, csrc/band.hip, the split (maus_band_set_split) against the narrow method in one process -- {info['name']}, {info['cus']} CUs",
+             "# ms per solve from the 'band_split' / 'band' profile class (HIP events around build + local + reduced + back of one batch),",
+             "# split: the better of two timed calls after one warm-up call, narrow: one timed call after one warm-up call; m = the rule's",
+             "# partition length 64 ceil(sqrt(n (kl + ku)) / 64), p partitions, n_red the order of the reduced system at m; TB/s = the",
+             "# split's arrays read and written once over the time at m; complex normal values on every diagonal, identity ordering;",
+             "# bar: the 1.25x of an opt-in schedule, narrow ms / split ms at m",
+             head]
+
+    def flush():
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+    shapes = [(k, n) for k in (1, 2, 15) for n in (65536, 262144, 1 << 20)]
+    for k, n in shapes:
+        if args.only and f"{k}:{n}" not in args.only.split(","):
+            continue
+        A = diagonals(n, k, k + n)
+        kl, ku = bind(ctx, A, 64, identity=True)
+        assert (kl, ku) == (k, k)
+        m = split_len(n, kl, ku)
+        p, n_red, _, _ = split_shape(n, kl, ku)
+        ctx.band_set_method(_cabi.BAND_NARROW)
+        for P in (1, 64):
+            ctx.band_set_split(False, 0)
+            nar = timed_band(ctx, P, "band", reps=1)[0]["ms"] / P
+            ms = {}
+            for f, mm in (("half", max(m // 2, 2 * (kl + ku) + 2)), ("rule", 0), ("twice", 2 * m)):
+                ctx.band_set_split(True, mm)
+                pr, _ = timed_band(ctx, P, "band_split")
+                ms[f] = pr["ms"] / P
+                if f == "rule":
+                    tb = pr["bytes"] / (pr["ms"] / 1e3) / 1e12
+            ctx.band_set_split(False, 0)
+            up = nar / ms["rule"]
+            lines.append(f"{n:>8} {kl:>3} {ku:>3} {P:>5} {nar:>10.3f} {m:>6} {p:>5} {n_red:>6} {ms['half']:>10.3f} {ms['rule']:>10.3f} "
+                         f"{ms['twice']:>10.3f} {tb:>9.3f} {tb * 1e12 / HBM:>9.2%} {up:>11.2f}x {'met' if up >= 1.25 else 'MISSED':>9}")
+            print(lines[-1], flush=True)
+            flush()
+    ctx.close()                                                # its workspaces would crowd out the solver's own context
+    if not args.only or "loop" in args.only.split(","):
+        lines += ["", "# MAUS_Solver linear loop bodies on a tridiagonal operator at n = 262144, P = 64, direct path (gmres_compat='scipy-legacy':",
+                  "# every solve a band solve), sparse_direct='narrow': 1 untimed + 3 timed bodies; candidate-steps = candidates at the start",
+                  "# of each timed body"]
+        rates = {}
+        for split in ("off", "on"):
+            rates[split], band_ms = loop_rate_narrow("narrow", split=split)
+            lines.append(f"sparse_split={split:<4} {rates[split]:9.1f} candidate-steps/s   (band classes {band_ms:9.1f} ms per body)")
+            print(lines[-1], flush=True)
+        up = rates["on"] / rates["off"]
+        lines.append(f"on / off: {up:.2f}x candidate-steps/s ({'meets' if up >= 1.25 else 'MISSES'} the 1.25x bar)")
+        print(lines[-1], flush=True)
+    flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--table", choices=("blocked", "tiled", "wide", "narrow"), default="blocked")
+    ap.add_argument("--table", choices=("blocked", "tiled", "wide", "narrow", "split"), default="blocked")
     ap.add_argument("--out", default=None)
     ap.add_argument("--sizes", default="128:1,128:64,256:1,256:64,512:1,512:8")
     ap.add_argument("--only", default=None, help="--table tiled / wide: the wide-band rows whose label contains one of these, nothing else; "
                          "--table narrow: the rows k:n (half-bandwidth:size) and 'loop' listed here, nothing else")
     ap.add_argument("--no-column", action="store_true", help="--table tiled: leave the column kernel's minutes out")
+    ap.add_argument("--split", action="store_true", help="the split beside the narrow method (same as --table split); --only as for narrow")
     args = ap.parse_args()
+    if args.split:
+        args.table = "split"
     args.out = args.out or f"profiles/band_{args.table}_rates.txt"
+    if args.table == "split":
+        return main_split(args)
     if args.table == "tiled":
         return main_tiled(args)
     if args.table == "wide":
