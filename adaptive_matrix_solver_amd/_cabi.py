@@ -20,7 +20,7 @@ SYMBOLS = [
     "maus_ctx_create", "maus_ctx_destroy", "maus_last_error", "maus_device_info", "maus_abi_version", "maus_lu_max_n",
     "maus_set_matrix", "maus_set_matrix_csr", "maus_matrix_is_sparse", "maus_set_rhs", "maus_pop_reserve", "maus_pop_capacity", "maus_pop_put", "maus_pop_get", "maus_pop_copy", "maus_pop_device_ptr", "maus_hist_append", "maus_hist_get", "maus_hist_clear", "maus_hist_generation",
     "maus_matvec_rayleigh", "maus_shifted_lu_solve", "maus_lu_reserve", "maus_lu_workspace_allocs", "maus_set_shared_device", "maus_lu_mw_aborts", "maus_relax_normalise", "maus_residual",
-    "maus_svd_power_step", "maus_svd_power_propose", "maus_svd_commit", "maus_set_eigvecs", "maus_herm_match", "maus_herm_tridiag", "maus_herm_release", "maus_herm_tridiag_eig", "maus_herm_tridiag_eigvals", "maus_herm_backtransform", "maus_get_eigvecs", "maus_gmres", "maus_gmres_pert", "maus_jacobi_check",
+    "maus_svd_power_step", "maus_svd_power_propose", "maus_svd_commit", "maus_set_eigvecs", "maus_herm_match", "maus_herm_tridiag", "maus_herm_set_chunk", "maus_herm_chunk_plan", "maus_herm_release", "maus_herm_tridiag_eig", "maus_herm_tridiag_eigvals", "maus_herm_backtransform", "maus_get_eigvecs", "maus_gmres", "maus_gmres_pert", "maus_jacobi_check",
     "maus_profile_union_ms", "maus_gram", "maus_zgemm_host", "maus_lu_solve_host", "maus_timer_start", "maus_timer_stop",
     "maus_profile_enable", "maus_profile_read", "maus_sync", "maus_mt19937_jump",
     "maus_lanczos_begin", "maus_lanczos_inject", "maus_lanczos_extend", "maus_lanczos_restart", "maus_lanczos_finish", "maus_herm_match_rows", "maus_get_ritz_rows",
@@ -113,6 +113,8 @@ def load_library():
         "maus_herm_match": ([vp, vp, C.c_int, vp, vp], C.c_int),
         "maus_herm_tridiag": ([vp, vp, vp], C.c_int),
         "maus_herm_release": ([vp], C.c_int),
+        "maus_herm_set_chunk": ([vp, C.c_int], C.c_int),
+        "maus_herm_chunk_plan": ([C.c_int, C.c_int, C.c_int, ip, ip, ip], C.c_int),
         "maus_herm_backtransform": ([vp, vp, C.c_int], C.c_int),
         "maus_herm_tridiag_eig": ([vp, vp, vp, C.c_int, vp, vp], C.c_int),
         "maus_herm_tridiag_eigvals": ([vp, vp, vp, C.c_int, vp], C.c_int),
@@ -474,6 +476,19 @@ class Context:
         t = max(float(np.max(np.abs(d))) if n else 0.0, float(np.max(np.abs(e))) if n > 1 else 0.0)
         s = 2.0 ** int(np.floor(np.log2(t))) if t > 0.0 else 1.0           # a power of two: the scaling is exact
         return n, d / s, np.ascontiguousarray(e / s if n > 1 else np.zeros(1)), s
+
+    def herm_set_chunk(self, tiles):
+        """Tiles per workgroup of the reduction's matvec: 0 (the rule, the default), 4, 8 or 16 for every column (tests, timing)."""
+        self._ck(self.lib.maus_herm_set_chunk(self.h, int(tiles)), "maus_herm_set_chunk")
+
+    @staticmethod
+    def herm_chunk_plan(n, i, forced=0):
+        """(T, hch, ns) that column i of an order-n reduction launches under `forced` (maus_herm_chunk_plan): block rows of the
+        tile grid, tiles per workgroup, tile workgroups.  Needs neither a context nor a device."""
+        T, hch, ns = C.c_int(0), C.c_int(0), C.c_int(0)
+        if load_library().maus_herm_chunk_plan(int(n), int(i), int(forced), C.byref(T), C.byref(hch), C.byref(ns)) != 0:
+            raise MausHipError(f"maus_herm_chunk_plan: bad order, column or chunk ({n}, {i}, {forced})")
+        return T.value, hch.value, ns.value
 
     def herm_release(self):
         """Hand back the reflector store of herm_tridiag (n x n) when no back-transformation will follow."""

@@ -144,6 +144,19 @@ constexpr int HTB = 64;        // tile edge
 constexpr int HCH_MIN = 4, HCH_MAX = 16;   // tiles per workgroup: chosen per column so that the launch has ~3 workgroups per CU
 constexpr int HW2 = 8;         // waves of a col2 workgroup
 
+// Workgroups of the tile part of col2 for T block rows at hch tiles per workgroup: block row tb has tb / hch + 1 chunks.
+int herm_strips(int T, int hch) { int s = 0; for (int tb = 0; tb < T; ++tb) s += tb / hch + 1; return s; }
+// Tiles per workgroup for a column whose matvec spans T block rows -- the one place that decides it.  forced = 4, 8 or 16
+// (maus_herm_set_chunk) is taken as it is; the rule (forced = 0) takes the largest of 16, 8, 4 that still gives 768 workgroups
+// (T (T + 1) / 2 tiles over ~3 workgroups per CU), and 4 where none does: 4 below n ~ 6600, 8 up to n ~ 9100, 16 above.
+int herm_chunk(int T, int forced) {
+    if (forced) return forced;
+    int hch = HCH_MAX;
+    while (hch > HCH_MIN && herm_strips(T, hch) < 768) hch /= 2;
+    return hch;
+}
+bool herm_chunk_ok(int tiles) { return tiles == 0 || tiles == 4 || tiles == 8 || tiles == 16; }
+
 #define MAUS_DPP_F64(V, CTRL) __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(V), CTRL, 0xf, 0xf, false), \
                                                __builtin_amdgcn_update_dpp(0, __double2loint(V), CTRL, 0xf, 0xf, false))
 // sum over the eight lanes that differ in the low three bits of the lane number; every one of them gets it
@@ -412,6 +425,78 @@ herm_larft_kernel(const c128* __restrict__ G, int nb, const c128* __restrict__ t
     if (ii < nb) for (int c = 0; c < nb; ++c) T[(long)ii * HNB + c] = sT[ii][c];
 }
 
+// Scale of the work copy.  col1 sums |a|^2 unscaled and herm_larfg_scalars takes the square root, so the squares of the entries
+// must neither overflow nor vanish: with entries near 1e+160 the sum is inf and beta = inf / inf, with entries near 1e-170 it
+// is 0 and a reflector that should annihilate x becomes a pure phase.  zheevr scales the matrix for this; here the largest
+// max(|Re a|, |Im a|) over the lower triangle (real parts only on the diagonal, NaN ignored) is found first, and when it lies
+// outside [2^-400, 2^400) the lower triangle is multiplied by the power of two that brings it into [1, 2); d and e are
+// multiplied back at the end.  Both multiplications are exact, and a power-of-two scaling commutes with every operation of
+// the reduction, so Q has the bits of the unscaled reduction done in a wider exponent range.
+// Why 2^+-400: every entry of every trailing matrix is bounded by ||A||_F <= n max|a|, so a column's sum of squares is at
+// most n^3 max^2 < 2^1024 for max < 2^400 and any n that fits a device; at the lower end a column whose entries are 2^-100
+// below the largest of the matrix still squares to normal numbers (2^-1000).  Inside the range nothing is touched: the work
+// copy and the results keep the bits they had before the scaling existed.  One global factor does not help a matrix graded
+// over more than that; zlarfg's own rescaling loop is not restated here.  (tests/herm_cases.py `scaled`.)
+constexpr int HSC_LO = -400, HSC_HI = 400;
+__global__ void __launch_bounds__(256)
+herm_absmax_kernel(const c128* __restrict__ A, int n, double* __restrict__ rowmax)
+{
+    __shared__ double sbuf[4];
+    const int r = blockIdx.x;
+    double m = 0.0;
+    for (int c = threadIdx.x; c <= r; c += 256) {
+        const c128 a = A[(long)r * n + c];
+        m = fmax(m, fabs(a.x));
+        if (c < r) m = fmax(m, fabs(a.y));
+    }
+    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+    if ((threadIdx.x & 63) == 0) sbuf[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) rowmax[r] = fmax(fmax(sbuf[0], sbuf[1]), fmax(sbuf[2], sbuf[3]));
+}
+// scl[0] = the factor for the work copy, scl[1] = its inverse for d and e; both 1 inside the range, for a zero matrix and for inf
+__global__ void __launch_bounds__(256)
+herm_scale_choose_kernel(const double* __restrict__ rowmax, int n, double* __restrict__ scl)
+{
+    __shared__ double sbuf[4];
+    double m = 0.0;
+    for (int r = threadIdx.x; r < n; r += 256) m = fmax(m, rowmax[r]);
+    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+    if ((threadIdx.x & 63) == 0) sbuf[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    m = fmax(fmax(sbuf[0], sbuf[1]), fmax(sbuf[2], sbuf[3]));
+    double f = 1.0, g = 1.0;
+    if (m > 0.0 && m < 1.7976931348623157e308) {
+        const int ex = ilogb(m);                                     // 2^ex <= m < 2^(ex + 1), subnormal m included
+        if (ex < HSC_LO || ex >= HSC_HI) {
+            const int k = max(-1000, min(1000, -ex));                // both powers stay normal numbers
+            f = scalbn(1.0, k); g = scalbn(1.0, -k);
+        }
+    }
+    scl[0] = f; scl[1] = g;
+}
+__global__ void __launch_bounds__(256)
+herm_scale_lower_kernel(c128* __restrict__ Aw, int n, const double* __restrict__ scl)
+{
+    const double f = scl[0];
+    if (f == 1.0) return;
+    const int r = blockIdx.x;
+    for (int c = threadIdx.x; c <= r; c += 256) {
+        c128 a = Aw[(long)r * n + c];
+        a.x *= f; a.y *= f;
+        Aw[(long)r * n + c] = a;
+    }
+}
+__global__ void __launch_bounds__(HT)
+herm_unscale_kernel(double* __restrict__ d, double* __restrict__ e, int n, const double* __restrict__ scl)
+{
+    const double g = scl[1];
+    if (g == 1.0) return;
+    const int k = blockIdx.x * HT + threadIdx.x;
+    if (k < n) { d[k] *= g; e[k] *= g; }
+}
+
 // The work copy as zheevr('L') sees the matrix: only the lower triangle counts.  The upper triangle becomes its mirror image and
 // the diagonal real, so that the full-row matvecs above compute what LAPACK's zhemv('L') computes -- also for an input that
 // is Hermitian only to np.allclose's tolerance (AMS:384: the reference's own test before it calls eigh).
@@ -590,6 +675,27 @@ int maus_herm_release(maus_ctx* c) {
     return 0;
 }
 
+int maus_herm_set_chunk(maus_ctx* c, int tiles) {
+    if (!c) return -1;
+    if (!herm_chunk_ok(tiles)) FAIL(c, "maus_herm_set_chunk: tiles must be 0 (the rule), 4, 8 or 16");
+    c->herm_chunk = tiles;
+    return 0;
+}
+
+int maus_herm_chunk_plan(int n, int i, int forced, int* T_out, int* hch_out, int* ns_out) {
+    if (n < 1 || i < 0 || i >= n || !herm_chunk_ok(forced)) return -1;
+    int T = 0, hch = 0, ns = 0;
+    if (i < n - 1) {                                                // the last column launches col1 alone
+        T = (n + HTB - 1) / HTB - (i + 1) / HTB;
+        hch = herm_chunk(T, forced);
+        ns = herm_strips(T, hch);
+    }
+    if (T_out) *T_out = T;
+    if (hch_out) *hch_out = hch;
+    if (ns_out) *ns_out = ns;
+    return 0;
+}
+
 int maus_herm_tridiag(maus_ctx* c, double* d_out, double* e_out) {
     if (!c->A || c->rows != c->cols) FAIL(c, "maus_herm_tridiag: square matrix required (maus_set_matrix)");
     if (!d_out || (!e_out && c->rows > 1)) FAIL(c, "maus_herm_tridiag: null output");
@@ -598,12 +704,11 @@ int maus_herm_tridiag(maus_ctx* c, double* d_out, double* e_out) {
     herm_free(c);
     const size_t nn = (size_t)n * n;
     c128 *Aw = nullptr, *PV = nullptr, *PW = nullptr, *P2 = nullptr, *Q2 = nullptr, *col = nullptr, *PU = nullptr, *PZ = nullptr, *t = nullptr, *cpart = nullptr;
-    double *part = nullptr, *d = nullptr, *e = nullptr;
+    double *part = nullptr, *d = nullptr, *e = nullptr, *rowmax = nullptr, *scl = nullptr;
     const int nparts_max = (n + HR - 1) / HR;
     const int nbk = (n + HTB - 1) / HTB, nch_max = (nbk + HCH_MIN - 1) / HCH_MIN;      // tile grid of the matvec
-    auto strips = [](int T, int hch) { int s = 0; for (int tb = 0; tb < T; ++tb) s += tb / hch + 1; return s; };   // workgroups for T block rows
     auto cleanup = [&]() {
-        void* ps[] = {Aw, PV, PW, P2, Q2, col, PU, PZ, t, cpart, part, d, e};
+        void* ps[] = {Aw, PV, PW, P2, Q2, col, PU, PZ, t, cpart, part, d, e, rowmax, scl};
         for (void* p : ps) if (p) (void)hipFree(p);
     };
 #define HERM_ALLOC(ptr, bytes) do { if (hipMalloc((void**)&(ptr), (bytes)) != hipSuccess) { (void)hipGetLastError(); cleanup(); herm_free(c); \
@@ -616,10 +721,14 @@ int maus_herm_tridiag(maus_ctx* c, double* d_out, double* e_out) {
     HERM_ALLOC(P2, sizeof(c128) * (size_t)2 * HNB * n);
     HERM_ALLOC(Q2, sizeof(c128) * (size_t)2 * HNB * n);
     HERM_ALLOC(col, sizeof(c128) * n);
+    // PU and cpart are sized for 4 tiles per workgroup, the most chunks per block row (ceil(nbk / 4)) and the most workgroups
+    // (herm_strips(nbk, 4)): 8 and 16, by the rule or forced (maus_herm_set_chunk), use a prefix of both.
     HERM_ALLOC(PU, sizeof(c128) * (size_t)nch_max * n);
     HERM_ALLOC(PZ, sizeof(c128) * (size_t)nbk * n);
     HERM_ALLOC(t, sizeof(c128) * 2 * HNB);
-    HERM_ALLOC(cpart, sizeof(c128) * (size_t)strips(nbk, HCH_MIN));
+    HERM_ALLOC(cpart, sizeof(c128) * (size_t)herm_strips(nbk, HCH_MIN));
+    HERM_ALLOC(rowmax, sizeof(double) * n);
+    HERM_ALLOC(scl, sizeof(double) * 2);
     HERM_ALLOC(part, sizeof(double) * nparts_max);
     HERM_ALLOC(d, sizeof(double) * n);
     HERM_ALLOC(e, sizeof(double) * n);
@@ -628,7 +737,12 @@ int maus_herm_tridiag(maus_ctx* c, double* d_out, double* e_out) {
     clk.lap("tridiag: allocations");
     hipStream_t st = c->st;
     hipError_t err = hipMemcpyAsync(Aw, c->A, sizeof(c128) * nn, hipMemcpyDeviceToDevice, st);
-    if (err == hipSuccess) hipLaunchKernelGGL(herm_mirror_lower_kernel, dim3((n + 31) / 32, (n + 31) / 32), dim3(256), 0, st, Aw, n);
+    if (err == hipSuccess) {
+        hipLaunchKernelGGL(herm_absmax_kernel, dim3(n), dim3(256), 0, st, Aw, n, rowmax);
+        hipLaunchKernelGGL(herm_scale_choose_kernel, dim3(1), dim3(256), 0, st, rowmax, n, scl);
+        hipLaunchKernelGGL(herm_scale_lower_kernel, dim3(n), dim3(256), 0, st, Aw, n, scl);
+        hipLaunchKernelGGL(herm_mirror_lower_kernel, dim3((n + 31) / 32, (n + 31) / 32), dim3(256), 0, st, Aw, n);
+    }
     if (err == hipSuccess) err = hipMemsetAsync(c->htau, 0, sizeof(c128) * n, st);
     if (err == hipSuccess) err = hipMemsetAsync(c->hq, 0, sizeof(c128) * nn, st);
     if (err == hipSuccess) err = hipMemsetAsync(e, 0, sizeof(double) * n, st);
@@ -646,9 +760,7 @@ int maus_herm_tridiag(maus_ctx* c, double* d_out, double* e_out) {
             hipLaunchKernelGGL(herm_col1_kernel, dim3(np1), dim3(256), 0, st, Aw, n, i, j, PV, PW, col, part, d);
             if (mp <= 0) continue;
             const int T = nbk - (i + 1) / HTB;                              // block rows of the tile grid that hold rows > i
-            int hch = HCH_MAX;                                              // T (T + 1) / 2 tiles over ~768 workgroups
-            while (hch > HCH_MIN && strips(T, hch) < 768) hch /= 2;
-            const int ns = strips(T, hch);
+            const int hch = herm_chunk(T, c->herm_chunk), ns = herm_strips(T, hch);
             hipLaunchKernelGGL(herm_col2_kernel, dim3(ns + 2 * j), dim3(64 * HW2), 0, st, Aw, n, i, j, ns, hch, col, part, np1, PV, PW, c->hq, c->htau, e,
                                PU, PZ, cpart, t);
             hipLaunchKernelGGL(herm_col3_kernel, dim3(T), dim3(256), 0, st, PV, PW, n, i, j, PU, PZ, t, c->htau, cpart, ns, hch);
@@ -671,6 +783,7 @@ int maus_herm_tridiag(maus_ctx* c, double* d_out, double* e_out) {
         if (err == hipSuccess) err = hipEventRecord(ev[panel & 1], st);
     }
     for (auto& x : ev) if (x) (void)hipEventDestroy(x);
+    if (err == hipSuccess) hipLaunchKernelGGL(herm_unscale_kernel, dim3((n + HT - 1) / HT), dim3(HT), 0, st, d, e, n, scl);
     if (err == hipSuccess && (maus_stage_d2h(c, d_out, d, sizeof(double) * n, st)
                               || (n > 1 && maus_stage_d2h(c, e_out, e, sizeof(double) * (n - 1), st)))) { cleanup(); herm_free(c); return -1; }
     if (err == hipSuccess) err = hipStreamSynchronize(st);

@@ -292,7 +292,9 @@ int maus_herm_match(maus_ctx* ctx, const int* slots, int count, int32_t* idx_out
  * reduction and the back-transformation on the device, once per matrix:
  *   maus_herm_tridiag        A = Q T Q^H of the context's (Hermitian) matrix, zhetrd('L') semantics and reflector
  *                            conventions; d_out[n] / e_out[n-1]: diagonal / subdiagonal of the real T.  The reflectors stay
- *                            on the device until the back-transformation.
+ *                            on the device until the back-transformation.  Only the lower triangle and the real part of the
+ *                            diagonal are read.  A matrix whose largest entry lies outside [2^-400, 2^400) is reduced as its
+ *                            multiple by a power of two (exact; d and e are multiplied back), the bound matrix stays as it is.
  *   maus_herm_tridiag_eig    eigenpairs (lambda, Z) of T on the device: bisection on the Sturm count, eigenvectors from the
  *                            twisted factorisation of T - lambda I (the getvec step of dstemr), no reorthogonalisation.
  *                            w_out[n] ascending; Z stays on the device for maus_herm_backtransform(ctx, NULL, 0).
@@ -306,6 +308,17 @@ int maus_herm_match(maus_ctx* ctx, const int* slots, int count, int32_t* idx_out
  *                            eigenvector matrix, as if set by maus_set_eigvecs.
  * The first row of V is real (Q e_1 = e_1), LAPACK's phase convention. */
 int maus_herm_tridiag(maus_ctx* ctx, double* d_out, double* e_out);
+/* Tiles per workgroup (hch) of the reduction's lower-triangle matvec, for tests and timing:
+ *   maus_herm_set_chunk   tiles = 0 (the default): the rule -- per column the largest of 16, 8, 4 that still gives 768 workgroups
+ *                         for the column's T block rows, 4 where none does.  4, 8 or 16: that value for every column.  Anything
+ *                         else is an error that changes nothing.  Kept across matrices.  The results of different values agree to
+ *                         rounding, not bit for bit: the order of summation differs.
+ *   maus_herm_chunk_plan  what column i of an order-n reduction launches under `forced` (0, 4, 8, 16), without a context or a
+ *                         device: T_out = block rows of the 64 x 64 tile grid with rows > i, hch_out = tiles per workgroup,
+ *                         ns_out = tile workgroups = sum_{tb < T} (tb / hch + 1).  All three are 0 for i = n - 1 (no matvec).
+ *                         -1 for n < 1, i outside [0, n) or another `forced`. */
+int maus_herm_set_chunk(maus_ctx* ctx, int tiles);
+int maus_herm_chunk_plan(int n, int i, int forced, int* T_out, int* hch_out, int* ns_out);
 /* Frees the reflector store / eigenvectors of T that maus_herm_tridiag(_eig) keep for maus_herm_backtransform: for callers that
  * only wanted the tridiagonal matrix or its eigenvalues (AMS:559, 567 reporting prologue; singular values of the start-up diagnostics). */
 int maus_herm_release(maus_ctx* ctx);
