@@ -29,6 +29,7 @@ SYMBOLS = [
     "maus_band_set_split", "maus_band_get_split", "maus_band_split_plan",
     "maus_gmres_set_method", "maus_gmres_get_method", "maus_gmres_kernel_for",
     "maus_few_rows_set_method", "maus_few_rows_get_method", "maus_few_rows_kernel_for", "maus_few_rows_plan", "maus_few_rows_workspace_allocs",
+    "maus_zgemm_plan",
     "maus_spmm_set_method", "maus_spmm_get_method", "maus_spmm_kernel_for", "maus_spmm_plan", "maus_spmm_sell_info",
     "maus_device_count", "maus_comm_unique_id", "maus_comm_init", "maus_comm_destroy", "maus_comm_info",
     "maus_comm_allgather_records", "maus_comm_allgather_rows", "maus_comm_bcast", "maus_comm_bcast_eigvecs", "maus_comm_set_matrix", "maus_comm_stats",
@@ -46,6 +47,9 @@ BAND_COLUMN, BAND_BLOCKED, BAND_TILED, BAND_WIDE, BAND_NARROW = (      # maus_ba
     DIRECT_METHOD[m] for m in ("band", "blocked", "tiled", "wide", "narrow"))
 GMRES_DEFAULT, GMRES_WIDE = 0, 1                     # maus_gmres_set_method
 FEW_ROWS_DEFAULT, FEW_ROWS_SPLITK = 0, 1             # maus_few_rows_set_method
+ZGEMM_ROWS, ZGEMM_LU = 0, 1                          # maus_zgemm_plan: the form ...
+LU_TILE_DEFAULT, LU_TILE_64X64, LU_TILE_128X64 = 0, 1, 2   # ... what MAUS_LU_TILE selects ...
+ZGEMM_4M, ZGEMM_3M, ZGEMM_3M_DMA = 0, 1, 2           # ... and the kernel family it returns
 SPMM_SCHEDULES = {0: None, 1: "rows", 2: "wave"}     # maus_matrix_is_sparse: dense / lane per row / wave per row
 SPMM_CSR, SPMM_SELL = 0, 1                           # maus_spmm_set_method
 SPMM_KERNEL_NONE, SPMM_KERNEL_ROWS, SPMM_KERNEL_WAVE, SPMM_KERNEL_SELL = 0, 1, 2, 3   # maus_spmm_kernel_for / maus_spmm_plan
@@ -156,6 +160,7 @@ def load_library():
         "maus_few_rows_kernel_for": ([vp] + [C.c_int] * 6 + [C.POINTER(C.c_int)], C.c_int),
         "maus_few_rows_plan": ([C.c_int] * 8 + [C.POINTER(C.c_int)], C.c_int),
         "maus_few_rows_workspace_allocs": ([vp], C.c_int),
+        "maus_zgemm_plan": ([C.c_int] * 9 + [ip, ip], C.c_int),
         "maus_spmm_set_method": ([vp, C.c_int, C.c_int], C.c_int),
         "maus_spmm_get_method": ([vp], C.c_int),
         "maus_spmm_kernel_for": ([vp, C.c_int], C.c_int),
@@ -888,6 +893,18 @@ def few_rows_plan(method, slices, M, N, K, b_layout=1, conj_a=False, conj_b=Fals
     if k < 0:
         raise MausHipError(f"maus_few_rows_plan: bad method, slices or sizes ({method}, {slices}, {M}, {N}, {K}, {b_layout})")
     return int(k), int(S.value)
+
+
+def zgemm_plan(form, lu_tile, M, N, K, batch=1, b_layout=0, conj_a=False, conj_b=False):
+    """(family, BM, BN) of an M x N x K product on `batch` matrices (maus_zgemm_plan): ZGEMM_4M, ZGEMM_3M or ZGEMM_3M_DMA and the
+    workgroup tile, for the form ZGEMM_ROWS or ZGEMM_LU under the MAUS_LU_TILE mode `lu_tile` (arguments in the C order).  Needs neither a context nor a
+    device."""
+    bm, bn = C.c_int(), C.c_int()
+    fam = load_library().maus_zgemm_plan(int(form), int(lu_tile), int(M), int(N), int(K), int(batch), int(b_layout),
+                                         int(bool(conj_a)), int(bool(conj_b)), C.byref(bm), C.byref(bn))
+    if fam < 0:
+        raise MausHipError(f"maus_zgemm_plan: bad form, tile mode, sizes or layout ({form}, {lu_tile}, {M}, {N}, {K}, {batch}, {b_layout}, {conj_a}, {conj_b})")
+    return int(fam), int(bm.value), int(bn.value)
 
 
 def spmm_plan(method, fill_cap_percent, rows, nnz, padded) -> int:

@@ -11,6 +11,7 @@
 // ---- kernels / drivers implemented in the other translation units ---------------------
 #include "luws.h"
 #include "mtplan.h"
+#include "zgemm.h"
 void maus_lu_factor(const LuWs& w, int nbo);
 void maus_lu_backsolve(const LuWs& w, c128* Wpop, long ldw, const int* d_slots, c128* xout_dense);
 void maus_build_h(const LuWs& w, const c128* A, const c128* d_shift, const double* d_psi, int rhs_mode,
@@ -27,15 +28,6 @@ void maus_build_h_mt(hipStream_t st, const c128* A, int n, int npad, long ldh, l
                      const c128* d_shift, const double* d_psi, int rhs_mode, const c128* X, long ldx, const int* d_slots,
                      const c128* bvec, const uint32_t* states, const int* extra, const int* rpos, int* flags, int tiled);
 int maus_mt_jump_poly(uint64_t J, uint64_t* out312);
-void maus_zgemm_launch_idx(hipStream_t st, int M, int N, int K, const c128* A, long lda, long sA,
-                           const c128* B, long ldb, long sB, c128* C, long ldc, long sC,
-                           double alpha, int beta, int batch, int blay, bool conja, bool conjb,
-                           const int* a_rows, const int* c_rows);
-// zgemm.hip: the same product for the population products of capi.hip, split over K under maus_few_rows_set_method(ctx, 1)
-int maus_zgemm_launch_few(maus_ctx* c, int M, int N, int K, const c128* A, long lda, long sA,
-                          const c128* B, long ldb, long sB, c128* C, long ldc, long sC,
-                          double alpha, int beta, int batch, int blay, bool conja, bool conjb,
-                          const int* a_rows, const int* c_rows);
 void maus_launch_rayleigh_dots(hipStream_t st, const c128* X, const c128* Y, long ld, const int* slots, int count, int n, c128* num, c128* den);
 void maus_launch_relax(hipStream_t st, c128* X, const c128* W, long ld, const int* slots, int count, int n, const c128* alpha, int normalise, double* norm_out);
 void maus_launch_residual(hipStream_t st, int kind, const c128* X, const c128* Y, long ld, const int* slots, int count, int n,

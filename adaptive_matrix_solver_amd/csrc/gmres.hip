@@ -32,11 +32,6 @@
 #include <algorithm>
 #include <cstring>
 
-void maus_zgemm_launch_idx(hipStream_t st, int M, int N, int K, const c128* A, long lda, long sA,
-                           const c128* B, long ldb, long sB, c128* C, long ldc, long sC,
-                           double alpha, int beta, int batch, int blay, bool conja, bool conjb,
-                           const int* a_rows, const int* c_rows);
-
 namespace {
 
 constexpr int MAXR = 20;

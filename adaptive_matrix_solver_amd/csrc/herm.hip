@@ -42,10 +42,6 @@
 #include <cstdio>
 #include <cstdlib>
 
-void maus_zgemm_launch(hipStream_t st, int M, int N, int K, const c128* A, long lda, long sA,
-                       const c128* B, long ldb, long sB, c128* C, long ldc, long sC,
-                       double alpha, int beta, int batch, int blay, bool conja, bool conjb);
-
 namespace {
 
 constexpr int HNB = 64;        // panel width / reflectors per block

@@ -21,23 +21,12 @@
 //     they are loaded; pivot rule = LAPACK izamax (max |re|+|im|, first index wins).
 #include "common.h"
 #include "luws.h"
+#include "zgemm.h"
 #include <cstdio>
 #include <cstdlib>
 #include <climits>
 #include <algorithm>
 #include <type_traits>
-
-void maus_zgemm_launch(hipStream_t st, int M, int N, int K, const c128* A, long lda, long sA,
-                       const c128* B, long ldb, long sB, c128* C, long ldc, long sC,
-                       double alpha, int beta, int batch, int blay, bool conja, bool conjb);
-
-void maus_zgemm_launch_lu(hipStream_t st, int M, int N, int K, const c128* H, const c128* U, c128* Hc, long nrows, long stride,
-                          int acol, int brow, int ccol, int batch, const int* rows, long rows_stride);
-
-void maus_zgemm_launch_rows(hipStream_t st, int M, int N, int K, const c128* A, long lda, long sA,
-                            const c128* B, long ldb, long sB, c128* C, long ldc, long sC,
-                            double alpha, int beta, int batch, int blay, bool conja, bool conjb,
-                            const int* a_rows, const int* c_rows, long rows_stride);
 
 namespace {
 

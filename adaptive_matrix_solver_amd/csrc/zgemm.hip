@@ -20,7 +20,7 @@
 // interleaved (re,im) pair; the next K-tile is prefetched into registers while the
 // current one feeds the MFMAs.  The fp64 matrix pipe sustains 77.9 TFLOP/s with VGPR
 // accumulators (tools/probe_mfma_f64_v2; AGPR accumulators run at less than half of that),
-// but only if independent waves fill each other's waits: see the launcher for the measured
+// but only if independent waves fill each other's waits: see zgemm_plan for the measured
 // tile / occupancy choice.
 //
 // Population products of at most 32 rows have a split-K form of the 4M kernel behind maus_few_rows_set_method(ctx, 1)
@@ -29,6 +29,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #ifndef MAUS_WC
 #define MAUS_WC 8
@@ -44,7 +45,7 @@ namespace {
 struct TCol { int x, y, z; };
 __device__ __forceinline__ long tile_off(long rows, int col) { return ((long)(col >> 6) * rows << 6) + (col & 63); }
 
-template <int BM, int BN, int BK, int WM, int WN, int BLAY, bool CONJA, bool CONJB, bool PIPE, int MINW, bool M3 = false, bool TILED = false>
+template <int BM, int BN, int BK, int WM, int WN, int BLAY, bool CONJA, bool CONJB, int MINW, bool M3 = false, bool TILED = false>
 __global__ void __launch_bounds__(64 * WM * WN, MINW)
 zgemm_kernel(int M, int N, int K,
              const c128* __restrict__ Ag, long lda, long strideA,
@@ -70,7 +71,7 @@ zgemm_kernel(int M, int N, int K,
     static_assert(A_PER * NT == BM * BK && B_PER * NT == BN * BK, "tile/threads mismatch");
 
     constexpr int TILE_S = BK * LDA_S + BK * LDB_S;          // one staged K-tile (A then B), elements
-    __shared__ c128 smem[(PIPE ? 2 : 1) * TILE_S];            // PIPE: double buffered, one barrier per K-tile
+    __shared__ c128 smem[TILE_S];
 
     // XCD-aware block -> tile map: blocks b and b+8 share an XCD (L2); give each XCD a
     // contiguous run of tiles so neighbouring tiles (same A row-panel) hit one L2.
@@ -201,10 +202,10 @@ zgemm_kernel(int M, int N, int K,
         }
     };
 
-    // ---- software-pipelined main loop ---------------------------------------------------------
-    // LDS buffer t&1 holds K-tile t.  While the MFMAs of tile t run: the fragments of the next
-    // k-step are already in flight (register double buffer), tile t+1 moves registers -> LDS, and
-    // tile t+2 is requested from global memory.  One barrier per K-tile.
+    // ---- main loop ------------------------------------------------------------------------------
+    // One LDS buffer, two barriers per K-tile: while the MFMAs of tile t run, the fragments of the next k-step are already in
+    // flight (register double buffer) and tile t+1 is requested from global memory.  Made for >= 2 workgroups per CU: the
+    // bubbles of one workgroup are filled by the independent waves of the others.
     const int nkt = (K + BK - 1) / BK;
     constexpr int KSTEPS = BK / 4;
     c128 fa[2][MB], fb[2][NB];
@@ -252,40 +253,17 @@ zgemm_kernel(int M, int N, int K,
         }
     };
 
-    if (PIPE) {
-        load_tiles(0);
-        store_tiles(0);
-        if (nkt > 1) load_tiles(BK);                         // tile 1 in flight
+    load_tiles(0);
+    for (int kt = 0; kt < nkt; ++kt) {
         __syncthreads();
-        for (int kt = 0; kt < nkt; ++kt) {
-            const int buf = kt & 1;
-            read_frags(buf, 0, 0);
+        store_tiles(0);
+        __syncthreads();
+        if (kt + 1 < nkt) load_tiles((kt + 1) * BK);
+        read_frags(0, 0, 0);
 #pragma unroll
-            for (int kk = 0; kk < KSTEPS; ++kk) {
-                if (kk + 1 < KSTEPS) read_frags(buf, kk + 1, (kk + 1) & 1);     // next k-step's fragments
-                if (kk == 0 && kt + 1 < nkt) store_tiles(buf ^ 1);               // tile t+1: registers -> LDS
-                if (kk == 0 && kt + 2 < nkt) load_tiles((kt + 2) * BK);          // tile t+2: global -> registers
-                __builtin_amdgcn_sched_barrier(0);
-                mfma_group(kk & 1);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            __syncthreads();
-        }
-    } else {
-        // lean form for >= 2 workgroups per CU: one LDS buffer, two barriers per K-tile; the bubbles of
-        // one workgroup are filled by the independent waves of the others
-        load_tiles(0);
-        for (int kt = 0; kt < nkt; ++kt) {
-            __syncthreads();
-            store_tiles(0);
-            __syncthreads();
-            if (kt + 1 < nkt) load_tiles((kt + 1) * BK);
-            read_frags(0, 0, 0);
-#pragma unroll
-            for (int kk = 0; kk < KSTEPS; ++kk) {
-                if (kk + 1 < KSTEPS) read_frags(0, kk + 1, (kk + 1) & 1);
-                mfma_group(kk & 1);
-            }
+        for (int kk = 0; kk < KSTEPS; ++kk) {
+            if (kk + 1 < KSTEPS) read_frags(0, kk + 1, (kk + 1) & 1);
+            mfma_group(kk & 1);
         }
     }
 
@@ -575,65 +553,6 @@ zgemm3m_dma_kernel(int M, int N, int K,
         }
 }
 
-template <int NST, int MINW, int MB, int NB, bool TILED = false, int BLAY = 0, bool CONJA = false, bool CONJB = false>
-void launch_dma(hipStream_t st, int M, int N, int K, const c128* A, long lda, long sA, const c128* B, long ldb, long sB,
-                c128* C, long ldc, long sC, double alpha, int beta, int batch, int, bool, bool,
-                const int* a_rows, const int* c_rows, long rows_stride, TCol tcol = TCol{0, 0, 0})
-{
-    constexpr int BM = 32 * MB, BN = 32 * NB;
-    int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-    int nwg = tiles_m * tiles_n;
-    hipLaunchKernelGGL((zgemm3m_dma_kernel<NST, MINW, MB, NB, TILED, BLAY, CONJA, CONJB>), dim3(nwg, batch), dim3(256), 0, st,
-                       M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, alpha, beta, tiles_n, nwg, a_rows, c_rows, rows_stride, tcol);
-}
-
-// population products (dot-product layout and / or conjugated operands) on the DMA-staged 3M kernel: 64 x 64 tiles for large
-// products, 64 x 32 otherwise
-template <int BLAY, bool CONJA, bool CONJB>
-void launch_dma_pop(hipStream_t st, int M, int N, int K, const c128* A, long lda, long sA, const c128* B, long ldb, long sB,
-                    c128* C, long ldc, long sC, double alpha, int beta, int batch, int blay, bool conja, bool conjb,
-                    const int* a_rows, const int* c_rows, long rows_stride)
-{
-    if (M >= 1536 && N >= 1536) launch_dma<2, 3, 2, 2, false, BLAY, CONJA, CONJB>(st, M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, alpha, beta, batch, blay, conja, conjb, a_rows, c_rows, rows_stride);
-    else launch_dma<2, 5, 2, 1, false, BLAY, CONJA, CONJB>(st, M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, alpha, beta, batch, blay, conja, conjb, a_rows, c_rows, rows_stride);
-}
-
-template <int BM, int BN, int BK, int WM, int WN, bool PIPE, int MINW>
-void launch_cfg(hipStream_t st, int M, int N, int K, const c128* A, long lda, long sA, const c128* B, long ldb, long sB,
-                c128* C, long ldc, long sC, double alpha, int beta, int batch, int blay, bool conja, bool conjb,
-                const int* a_rows, const int* c_rows, long rows_stride)
-{
-    int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-    int nwg = tiles_m * tiles_n;
-    dim3 grid(nwg, batch), block(64 * WM * WN);
-#define LAUNCH(BL, CA, CB) hipLaunchKernelGGL((zgemm_kernel<BM, BN, BK, WM, WN, BL, CA, CB, PIPE, MINW>), grid, block, 0, st, \
-        M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, alpha, beta, tiles_n, nwg, a_rows, c_rows, rows_stride, TCol{0, 0, 0})
-    if (blay == 0) {
-        if (!conja && !conjb) LAUNCH(0, false, false);
-        else if (!conja && conjb) LAUNCH(0, false, true);
-        else if (conja && !conjb) LAUNCH(0, true, false);
-        else LAUNCH(0, true, true);
-    } else {
-        if (!conja && !conjb) LAUNCH(1, false, false);
-        else if (!conja && conjb) LAUNCH(1, false, true);
-        else if (conja && !conjb) LAUNCH(1, true, false);
-        else LAUNCH(1, true, true);
-    }
-#undef LAUNCH
-}
-
-// plain-layout-only instantiation (LU trailing updates): one kernel per tile shape instead of eight
-template <int BM, int BN, int BK, int WM, int WN, bool PIPE = false, int MINW = 4, bool M3 = false, bool TILED = false>
-void launch_lu_only(hipStream_t st, int M, int N, int K, const c128* A, long lda, long sA, const c128* B, long ldb, long sB,
-                    c128* C, long ldc, long sC, double alpha, int beta, int batch, int, bool, bool,
-                    const int* a_rows, const int* c_rows, long rows_stride, TCol tcol = TCol{0, 0, 0})
-{
-    int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-    int nwg = tiles_m * tiles_n;
-    hipLaunchKernelGGL((zgemm_kernel<BM, BN, BK, WM, WN, 0, false, false, PIPE, MINW, M3, TILED>), dim3(nwg, batch), dim3(64 * WM * WN), 0, st,
-                       M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, alpha, beta, tiles_n, nwg, a_rows, c_rows, rows_stride, tcol);
-}
-
 // ---------------------------------------------------------------------------------------
 // Split-K population products for at most 32 rows (maus_few_rows_set_method(ctx, 1); DESIGN §3 "Few rows").  The 4M kernels above
 // give a product of up to 32 rows ceil(N / 32) workgroups, each walking the whole K alone: M = 15 against 8192 x 8192 occupies
@@ -794,17 +713,14 @@ int few_rule(int N, int K, int /*blay*/)
 
 // MAUS_LU_TILE=64x64|128x64 (read once per process): the workgroup tile of the large LU trailing updates, for timing one tile
 // against the other in one binary and for comparing their bits.  128x64: every update with M, N >= MAUS_LU_LT_MIN on the DMA
-// path, whatever its K; 64x64: the rule before the 128 x 64 tile (64 x 64 from 1536).  Unset: the rule of maus_zgemm_launch_lu.
-#ifndef MAUS_LU_LT_MIN
-#define MAUS_LU_LT_MIN 1024
-#endif
+// path, whatever its K; 64x64: the rule before the 128 x 64 tile (64 x 64 from 1536).  Unset: the rule of zgemm_plan.
 int lu_tile_mode()
 {
     static const int mode = [] {
         const char* e = getenv("MAUS_LU_TILE");
-        if (!e || !*e) return 0;
-        if (!strcmp(e, "128x64")) return 2;
-        if (!strcmp(e, "64x64")) return 3;
+        if (!e || !*e) return (int)MAUS_LU_TILE_DEFAULT;
+        if (!strcmp(e, "128x64")) return (int)MAUS_LU_TILE_128X64;
+        if (!strcmp(e, "64x64")) return (int)MAUS_LU_TILE_64X64;
         fprintf(stderr, "MAUS_LU_TILE=%s: expected 64x64 or 128x64\n", e);
         abort();
         return 0;
@@ -812,11 +728,137 @@ int lu_tile_mode()
     return mode;
 }
 
+// ---- dispatch: one plan, one launch table ------------------------------------------------------------------------------------
+// zgemm_plan is the rule "which kernel does a product run", stated once for the rows form (maus_zgemm_launch_rows and what calls
+// it) and the LU form (maus_zgemm_launch_lu): host arithmetic on its arguments, nothing read from the environment or a device.
+// maus_zgemm_plan exports it, and tests/test_zgemm_plan_host.py holds it against the independent statement of
+// tests/zgemm_cases.py on both sides of every threshold below.
+//
+// All kernels: 4 waves per workgroup and registers / LDS small enough for 2-5 INDEPENDENT workgroups per CU.  Measured on MI355X
+// (profiles/r01_gemm_sweep_configs.txt, r02_zgemm_tile_variants_small_shapes.txt; K = 256, 136 matrices, 8MNK-equivalent
+// TFLOP/s): every one-workgroup-per-CU shape (128 x 64 / 128 x 128, BK 16 / 32, software-pipelined or not) stays at 50-59 -- with
+// all waves of a SIMD in one workgroup they run in lockstep and every wait or barrier of one is a bubble for all; 8-wave
+// workgroups lose to 4-wave ones at equal tile area.  The variants that lost those sweeps are gone.
+// What the plan can answer: kernel family and workgroup tile BM x BN.  with_kernel below turns each into its instantiation.
+enum ZgemmKind { ZG_4M_128x16, ZG_4M_16x128, ZG_4M_64x64, ZG_4M_32x64, ZG_4M_32x32, ZG_3M_32x64, ZG_3M_64x32,
+                 ZG_DMA_64x32, ZG_DMA_64x64, ZG_DMA_128x64 };
+
+// Plain layout without conjugation (LU workspaces, row-major workspaces of the GMRES path, host-matrix entry points): skinny
+// shapes keep the workgroup tile shaped like the problem so that no MFMA runs on padding.
+constexpr int ZG_SKINNY_N = 16;                  // N <= 16: 128 x 16 tiles
+constexpr int ZG_SKINNY_M = 16;                  // M <= 16: 16 x 128 tiles
+constexpr int ZG_FEW_M = 32;                     // M <= 32: one 32-row tile, never DMA-staged
+// The LDS-DMA staged 3M kernel, in K-steps of 8 through a ring of two buffers.  3584 x 3616 x 512, 136 matrices: register-staged
+// kernel 79.2; DMA staging, 64 x 32 tiles, five workgroups per CU 86.8 (prefetch issued behind the fragment reads); 64 x 64 tiles
+// at three workgroups per CU 88.7 on large updates (86.3 at 1024 x 1056: the 64 x 32 form is kept below 1536).  Same summation
+// order as the register-staged kernel, hence the same bits.  It has every layout / conjugation form but the doubly conjugated.
+// (64 x 64 tiles from M >= 1024 / 512 and N >= 128 / 256 / 1024, or only from 2048: the 181-solve sweep stays within 0.5 ms of
+// 494 ms -- the K = 128 / 256 levels are not bound by the tile shape.)
+constexpr int ZG_DMA_KSTEP = 8, ZG_DMA_KMIN = 64;
+constexpr int ZG_DMA_BIG = 1536;                 // M, N >= 1536: 64 x 64 tiles
+// LU form only: 128 x 64 tiles (64 x 32 per wave: a quarter less LDS traffic per MFMA than the 32 x 32 wave tile, half the barriers
+// and DMA issues), two workgroups per CU, for the outer updates: 90.4 against 88.4 at 3584 x 3616 x 512 and 86.6 against 84.9
+// (64 x 32 tiles) at 1024 x 1056 x 512, 181 matrices; the 64 x 128 tile stayed at 64 x 64's rate (89.1) and is gone
+// (profiles/zgemm_large_tile_rates.txt).  Same summation order, same bits.  Only where the grid is at least eight rounds of the
+// 512 workgroups the chip holds: with fewer, larger tiles the last, partly filled round weighs more (one to eight matrices: 37-66
+// against 47-70 at 1024, 46 / 62 against 58 / 69 at 1536 with one / two matrices, equal from 1200-3200 tiles on).
+#ifndef MAUS_LU_LT_MIN
+#define MAUS_LU_LT_MIN 1024
+#endif
+constexpr int ZG_LT_MIN = MAUS_LU_LT_MIN, ZG_LT_KMIN = 256, ZG_LT_TILES = 4096;
+// 4M for what is left of the population products (a handful of candidates, K not a multiple of 8, both operands conjugated):
+// 64 x 64 tiles, 32 x 32 wave tile; with the next K-tile genuinely in flight during the MFMAs this needs ~160 VGPRs: three
+// workgroups per CU.  A population of a few hundred candidates against an n x n matrix gives few such tiles (M = 512, N = 2048:
+// 256 -- one workgroup on each CU where three fit): below two tiles per CU the tile shrinks to 32 x 64 / 32 x 32 so that the grid
+// covers the chip (M = 15 against 8192 x 8192 runs 0.57 ms per product on 256 workgroups of 32 x 32, 0.86 on 128 of 64 x 64).
+constexpr int ZG_4M_TILES = 512;
+
+ZgemmKind zgemm_plan(int form, int lu_tile, int M, int N, int K, int batch, int blay, bool conja, bool conjb)
+{
+    const bool plain = blay == 0 && !conja && !conjb;
+    auto tiles = [&](int bm, int bn) { return (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn) * batch; };
+    if (plain && N <= ZG_SKINNY_N) return ZG_4M_128x16;
+    if (plain && M <= ZG_SKINNY_M) return ZG_4M_16x128;
+    const bool few = M <= ZG_FEW_M;
+    if (!few && K % ZG_DMA_KSTEP == 0 && K >= ZG_DMA_KMIN && !(conja && conjb)) {
+        if (form == MAUS_ZGEMM_LU && M >= ZG_LT_MIN && N >= ZG_LT_MIN &&
+            (lu_tile == MAUS_LU_TILE_128X64 || (lu_tile == MAUS_LU_TILE_DEFAULT && K >= ZG_LT_KMIN && tiles(128, 64) >= ZG_LT_TILES)))
+            return ZG_DMA_128x64;
+        return M >= ZG_DMA_BIG && N >= ZG_DMA_BIG ? ZG_DMA_64x64 : ZG_DMA_64x32;
+    }
+    // 3M complex product on the register-staged kernel: three real MFMA products per complex one (ArBr, AiBi, (Ar+Ai)(Br+Bi)); a
+    // 32 x 16 wave tile keeps the three accumulator planes, the fragments and the in-flight prefetch of the next K-tile inside 128
+    // VGPRs.  Error is normwise the same as 4M (9.5e-16 vs 1.1e-15 relative on random data); the imaginary part loses its
+    // componentwise bound, which LU with partial pivoting does not rely on.
+    if (plain) return few ? ZG_3M_32x64 : ZG_3M_64x32;
+    if (tiles(64, 64) >= ZG_4M_TILES) return ZG_4M_64x64;
+    if (tiles(32, 64) >= ZG_4M_TILES) return ZG_4M_32x64;
+    return ZG_4M_32x32;
+}
+
+// Runtime (layout, conj A, conj B) -> compile-time constants: f(BLAY, CONJA, CONJB) with three std::integral_constant values.
+// Every kernel family that has such forms goes through here and leaves out the ones it lacks with `if constexpr`.
+template <class F>
+void with_form(int blay, bool conja, bool conjb, F&& f)
+{
+    auto conj = [&](auto bl) {
+        if (conja) { if (conjb) f(bl, std::true_type{}, std::true_type{}); else f(bl, std::true_type{}, std::false_type{}); }
+        else { if (conjb) f(bl, std::false_type{}, std::true_type{}); else f(bl, std::false_type{}, std::false_type{}); }
+    };
+    if (blay) conj(std::integral_constant<int, 1>{}); else conj(std::integral_constant<int, 0>{});
+}
+
+struct ZgemmArgs {
+    hipStream_t st; int M, N, K;
+    const c128* A; long lda, sA; const c128* B; long ldb, sB; c128* C; long ldc, sC;
+    double alpha; int beta, batch; const int* a_rows; const int* c_rows; long rows_stride; TCol tcol;
+};
+
+// The launch table: kind -> instantiation, each named once.  f(kernel, family, BM, BN, threads per workgroup) is called with the
+// kernel of `kind` for this form; false where the form has none (the rule never asks for one: tests/test_zgemm_plan_host.py
+// walks the rule through this table by way of maus_zgemm_plan).  zgemm_kernel and zgemm3m_dma_kernel take the same arguments, so
+// every entry has the same type.  TILED (the LU form) has the plain layout only; the 128 x 64 DMA tile is its alone; the DMA
+// kernel has no doubly conjugated form and the 4M tiles of the population products no plain one.
+template <bool TILED, int BLAY, bool CONJA, bool CONJB, class F>
+bool with_kernel(ZgemmKind kind, F&& f)
+{
+    constexpr bool PLAIN = BLAY == 0 && !CONJA && !CONJB, DMA_FORM = !(CONJA && CONJB);
+    static_assert(PLAIN || !TILED, "tiled operands: plain layout only");
+#define REG(BM, BN, WM, WN, MINW, M3) (f(zgemm_kernel<BM, BN, 16, WM, WN, BLAY, CONJA, CONJB, MINW, M3, TILED>, \
+                                         M3 ? MAUS_ZGEMM_3M : MAUS_ZGEMM_4M, BM, BN, 64 * WM * WN), true)
+#define DMA(MINW, MB, NB) (f(zgemm3m_dma_kernel<2, MINW, MB, NB, TILED, BLAY, CONJA, CONJB>, MAUS_ZGEMM_3M_DMA, 32 * MB, 32 * NB, 256), true)
+    switch (kind) {                                          // no default: a kind without a case is a compiler warning
+    case ZG_4M_128x16: if constexpr (PLAIN) return REG(128, 16, 4, 1, 4, false); break;
+    case ZG_4M_16x128: if constexpr (PLAIN) return REG(16, 128, 1, 4, 3, false); break;
+    case ZG_3M_32x64: if constexpr (PLAIN) return REG(32, 64, 1, 4, 4, true); break;
+    case ZG_3M_64x32: if constexpr (PLAIN) return REG(64, 32, 2, 2, 4, true); break;
+    case ZG_4M_64x64: if constexpr (!PLAIN) return REG(64, 64, 2, 2, 3, false); break;
+    case ZG_4M_32x64: if constexpr (!PLAIN) return REG(32, 64, 1, 4, 4, false); break;
+    case ZG_4M_32x32: if constexpr (!PLAIN) return REG(32, 32, 2, 2, 4, false); break;
+    case ZG_DMA_64x32: if constexpr (DMA_FORM) return DMA(5, 2, 1); break;                     // five workgroups per CU
+    case ZG_DMA_64x64: if constexpr (DMA_FORM) return DMA(3, 2, 2); break;                     // three
+    case ZG_DMA_128x64: if constexpr (TILED) return DMA(2, 4, 2); break;                       // two
+    }
+#undef REG
+#undef DMA
+    return false;
+}
+
+// one grid of ceil(M / BM) x ceil(N / BN) tiles per matrix; a kind without a kernel for the form is an error, never another kernel
+template <bool TILED, int BLAY, bool CONJA, bool CONJB>
+void launch_kind(ZgemmKind kind, const ZgemmArgs& a)
+{
+    const bool found = with_kernel<TILED, BLAY, CONJA, CONJB>(kind, [&](auto kernel, int, int BM, int BN, int threads) {
+        const int tiles_n = (a.N + BN - 1) / BN, nwg = (a.M + BM - 1) / BM * tiles_n;
+        hipLaunchKernelGGL(kernel, dim3(nwg, a.batch), dim3(threads), 0, a.st, a.M, a.N, a.K, a.A, a.lda, a.sA, a.B, a.ldb, a.sB,
+                           a.C, a.ldc, a.sC, a.alpha, a.beta, tiles_n, nwg, a.a_rows, a.c_rows, a.rows_stride, a.tcol);
+    });
+    if (!found) { fprintf(stderr, "zgemm: no kernel of kind %d for layout %d, conj %d %d\n", (int)kind, BLAY, CONJA, CONJB); abort(); }
+}
+
 }  // namespace
 
 // Host-side launcher (device pointers).  batch matrices at element strides sA/sB/sC.
-// tests/test_gpu_zgemm_variants.py carries a Python copy of the rule below (variant()) and a table of shapes that reaches every
-// kernel it can pick: a change to the rule has to be made there too.
 // a_rows / c_rows (device int arrays of length M, or null): row gather for A / row scatter
 // for C -- the population's candidate vectors live in arbitrary slots of one array.
 void maus_zgemm_launch_rows(hipStream_t st, int M, int N, int K, const c128* A, long lda, long sA,
@@ -825,88 +867,21 @@ void maus_zgemm_launch_rows(hipStream_t st, int M, int N, int K, const c128* A, 
                             const int* a_rows, const int* c_rows, long rows_stride)
 {
     if (M <= 0 || N <= 0 || batch <= 0) return;
-#define ARGS st, M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, alpha, beta, batch, blay, conja, conjb, a_rows, c_rows, rows_stride
-    // All kernels: 4 waves per workgroup and registers / LDS small enough for 3-5 INDEPENDENT workgroups per CU.  Measured on
-    // MI355X in rounds 1-3 (profiles/r01_gemm_sweep_configs.txt, r02_zgemm_tile_variants_small_shapes.txt; K = 256, 136 matrices,
-    // 8MNK-equivalent TFLOP/s): every one-workgroup-per-CU shape (128 x 64 / 128 x 128, BK 16 / 32, software-pipelined or not)
-    // stays at 50-59 -- with all waves of a SIMD in one workgroup they run in lockstep and every wait or barrier of one is a
-    // bubble for all; 8-wave workgroups lose to 4-wave ones at equal tile area.  The variants that lost those sweeps are gone.
-    constexpr int DMA_KMIN = 64;
-    if (blay == 0 && !conja && !conjb) {
-        // plain layout (row-major LU workspaces of the GMRES path, host-matrix entry points).  Skinny shapes keep the workgroup
-        // tile shaped like the problem so that no MFMA runs on padding.
-        if (N <= 16) { launch_lu_only<128, 16, 16, 4, 1>(ARGS); return; }
-        if (M <= 16) { launch_lu_only<16, 128, 16, 1, 4, false, 3>(ARGS); return; }
-        // K >= 64: the LDS-DMA staged 3M kernel.  3584 x 3616 x 512, 136 matrices: register-staged kernel 79.2; DMA staging,
-        // 64 x 32 tiles, five workgroups per CU 86.8 (prefetch issued behind the fragment reads); 64 x 64 tiles at three
-        // workgroups per CU 88.7 on large updates (86.3 at 1024 x 1056: the 64 x 32 form is kept below 1536).  Same summation
-        // order as the register-staged kernel, hence the same bits.
-        if (M > 32 && (K % 8) == 0 && K >= DMA_KMIN) {
-            if (M >= 1536 && N >= 1536) launch_dma<2, 3, 2, 2>(ARGS);   // 64 x 64 tiles, three workgroups per CU
-            else launch_dma<2, 5, 2, 1>(ARGS);
-            return;
-        }
-        // 3M complex product on the register-staged kernel: three real MFMA products per complex one (ArBr, AiBi,
-        // (Ar+Ai)(Br+Bi)); a 32 x 16 wave tile keeps the three accumulator planes, the fragments and the in-flight prefetch of
-        // the next K-tile inside 128 VGPRs.  Error is normwise the same as 4M (9.5e-16 vs 1.1e-15 relative on random data); the
-        // imaginary part loses its componentwise bound, which LU with partial pivoting does not rely on.
-        if (M <= 32) { launch_lu_only<32, 64, 16, 1, 4, false, 4, true>(ARGS); return; }
-        launch_lu_only<64, 32, 16, 2, 2, false, 4, true>(ARGS); return;
-    }
-    // Population products with a dot-product B layout and / or conjugated operands: the DMA-staged 3M kernel (round 3) where
-    // its staging applies (K a multiple of 8, >= 64, more than one 32-row tile)
-    if (M > 32 && (K % 8) == 0 && K >= DMA_KMIN) {
-        if (blay == 1 && !conja && !conjb) { launch_dma_pop<1, false, false>(ARGS); return; }
-        if (blay == 1 && conja && !conjb) { launch_dma_pop<1, true, false>(ARGS); return; }
-        if (blay == 1 && !conja && conjb) { launch_dma_pop<1, false, true>(ARGS); return; }
-        if (blay == 0 && conja && !conjb) { launch_dma_pop<0, true, false>(ARGS); return; }
-        if (blay == 0 && !conja && conjb) { launch_dma_pop<0, false, true>(ARGS); return; }
-    }
-    // 4M otherwise (a handful of candidates, K not a multiple of 8): 64 x 64 tiles, 32 x 32 wave tile; with the next K-tile
-    // genuinely in flight during the MFMAs this needs ~160 VGPRs: three workgroups per CU.  A population of a few hundred
-    // candidates against an n x n matrix gives few such tiles (M = 512, N = 2048: 256 -- one workgroup on each CU where three
-    // fit): below two tiles per CU the tile shrinks to 32 x 64 / 32 x 32 so that the grid covers the chip (M = 15 against
-    // 8192 x 8192 runs 0.57 ms per product on 256 workgroups of 32 x 32, 0.86 on 128 of 64 x 64).
-    const long t64 = (long)((M + 63) / 64) * ((N + 63) / 64) * batch;
-    const int tile = (t64 >= 512) ? 0 : ((long)((M + 31) / 32) * ((N + 63) / 64) * batch >= 512 ? 1 : 2);
-    if (tile == 1) { launch_cfg<32, 64, 16, 1, 4, false, 4>(ARGS); return; }
-    if (tile == 2) { launch_cfg<32, 32, 16, 2, 2, false, 4>(ARGS); return; }
-    launch_cfg<64, 64, 16, 2, 2, false, 3>(ARGS);
-#undef ARGS
+    const ZgemmKind kind = zgemm_plan(MAUS_ZGEMM_ROWS, MAUS_LU_TILE_DEFAULT, M, N, K, batch, blay, conja, conjb);
+    const ZgemmArgs a{st, M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, alpha, beta, batch, a_rows, c_rows, rows_stride, TCol{0, 0, 0}};
+    with_form(blay, conja, conjb, [&](auto bl, auto ca, auto cb) { launch_kind<false, decltype(bl)::value, decltype(ca)::value, decltype(cb)::value>(kind, a); });
 }
 
 // LU trailing update on the tile-major workspace (luws.h):  H[rows[m]][ccol + n] -= H[rows[m]][acol + k] * U[brow + k][ccol + n]
 // for m < M, n < N, k < K, all `batch` matrices (element stride `stride`, `nrows` rows per 64-column tile); rows = the LU's
-// per-matrix row permutation (rows_stride apart).  Same kernels and dispatch rule as the plain-layout path above.
+// per-matrix row permutation (rows_stride apart).
 void maus_zgemm_launch_lu(hipStream_t st, int M, int N, int K, const c128* H, const c128* U, c128* Hc, long nrows, long stride,
                           int acol, int brow, int ccol, int batch, const int* rows, long rows_stride)
 {
     if (M <= 0 || N <= 0 || K <= 0 || batch <= 0) return;
-    constexpr int dma_kmin = 64;
-    const TCol tc{acol, brow, ccol};
-#define ARGS st, M, N, K, H, nrows, stride, U, nrows, stride, Hc, nrows, stride, -1.0, 1, batch, 0, false, false, rows, rows, rows_stride, tc
-    if (N <= 16) { launch_lu_only<128, 16, 16, 4, 1, false, 4, false, true>(ARGS); return; }
-    if (M <= 16) { launch_lu_only<16, 128, 16, 1, 4, false, 3, false, true>(ARGS); return; }
-    if (M > 32 && (K % 8) == 0 && K >= dma_kmin) {
-        // (round 3: 64 x 64 tiles from M >= 1024 / 512 and N >= 128 / 256 / 1024, or only from 2048: the 181-solve sweep stays
-        // within 0.5 ms of 494 ms -- the K = 128 / 256 levels are not bound by the tile shape)
-        // 128 x 64 tiles (64 x 32 per wave: a quarter less LDS traffic per MFMA than the 32 x 32 wave tile, half the barriers
-        // and DMA issues), two workgroups per CU, for the outer updates: 90.4 against 88.4 at 3584 x 3616 x 512 and 86.6
-        // against 84.9 (64 x 32 tiles) at 1024 x 1056 x 512, 181 matrices; the 64 x 128 tile stayed at 64 x 64's rate (89.1)
-        // and is gone (profiles/zgemm_large_tile_rates.txt).  Same summation order, same bits.
-        // Only where the grid is at least eight rounds of the 512 workgroups the chip holds: with fewer, larger tiles the last,
-        // partly filled round weighs more (one to eight matrices: 37-66 against 47-70 at 1024, 46 / 62 against 58 / 69 at 1536
-        // with one / two matrices, equal from 1200-3200 tiles on).
-        const int tile = lu_tile_mode();
-        const long tiles = (long)((M + 127) / 128) * ((N + 63) / 64) * batch;
-        if (M >= MAUS_LU_LT_MIN && N >= MAUS_LU_LT_MIN && (tile == 2 || (tile == 0 && K >= 256 && tiles >= 4096))) { launch_dma<2, 2, 4, 2, true>(ARGS); return; }
-        if (M >= 1536 && N >= 1536) { launch_dma<2, 3, 2, 2, true>(ARGS); return; }      // 64 x 64 tiles, three workgroups per CU
-        launch_dma<2, 5, 2, 1, true>(ARGS);
-        return;
-    }
-    if (M <= 32) { launch_lu_only<32, 64, 16, 1, 4, false, 4, true, true>(ARGS); return; }
-    launch_lu_only<64, 32, 16, 2, 2, false, 4, true, true>(ARGS);
-#undef ARGS
+    const ZgemmKind kind = zgemm_plan(MAUS_ZGEMM_LU, lu_tile_mode(), M, N, K, batch, 0, false, false);
+    launch_kind<true, 0, false, false>(kind, ZgemmArgs{st, M, N, K, H, nrows, stride, U, nrows, stride, Hc, nrows, stride, -1.0, 1, batch,
+                                                        rows, rows, rows_stride, TCol{acol, brow, ccol}});
 }
 
 void maus_zgemm_launch_idx(hipStream_t st, int M, int N, int K, const c128* A, long lda, long sA,
@@ -970,19 +945,13 @@ int maus_zgemm_launch_few(maus_ctx* c, int M, int N, int K, const c128* A, long 
         c->few_ws_elems = need;
         ++c->few_allocs;
     }
-#define SLICES(BL, CA, CB) do { if (M <= 16) launch_slices<16, BL, CA, CB>(c->st, M, N, K, A, lda, B, ldb, c->few_ws, tiles_n, S, a_rows); \
-                                else launch_slices<32, BL, CA, CB>(c->st, M, N, K, A, lda, B, ldb, c->few_ws, tiles_n, S, a_rows); } while (0)
-    if (blay == 0) {
-        if (conja && conjb) SLICES(0, true, true);
-        else if (conja) SLICES(0, true, false);
-        else SLICES(0, false, true);
-    } else {
-        if (conja && conjb) SLICES(1, true, true);
-        else if (conja) SLICES(1, true, false);
-        else if (conjb) SLICES(1, false, true);
-        else SLICES(1, false, false);
-    }
-#undef SLICES
+    with_form(blay, conja, conjb, [&](auto bl, auto ca, auto cb) {
+        constexpr int BL = decltype(bl)::value; constexpr bool CA = decltype(ca)::value, CB = decltype(cb)::value;
+        if constexpr (BL != 0 || CA || CB) {                 // few_plan: a plain product never gets here
+            if (M <= 16) launch_slices<16, BL, CA, CB>(c->st, M, N, K, A, lda, B, ldb, c->few_ws, tiles_n, S, a_rows);
+            else launch_slices<32, BL, CA, CB>(c->st, M, N, K, A, lda, B, ldb, c->few_ws, tiles_n, S, a_rows);
+        }
+    });
     hipLaunchKernelGGL(zgemm_join_kernel, dim3((N + 255) / 256, M), dim3(256), 0, c->st, M, N, S, tiles_n, c->few_ws, C, ldc, alpha, beta, c_rows);
     return 0;
 }
@@ -1015,5 +984,19 @@ int maus_few_rows_kernel_for(maus_ctx* c, int M, int N, int K, int b_layout, int
 }
 
 int maus_few_rows_workspace_allocs(maus_ctx* c) { return c ? c->few_allocs : -1; }
+
+int maus_zgemm_plan(int form, int lu_tile, int M, int N, int K, int batch, int b_layout, int conj_a, int conj_b, int* bm_out, int* bn_out) {
+    if ((form != MAUS_ZGEMM_ROWS && form != MAUS_ZGEMM_LU) || lu_tile < MAUS_LU_TILE_DEFAULT || lu_tile > MAUS_LU_TILE_128X64) return -1;
+    if (M < 1 || N < 1 || K < 1 || batch < 1 || (b_layout != 0 && b_layout != 1)) return -1;
+    if (form == MAUS_ZGEMM_LU && (b_layout || conj_a || conj_b)) return -1;
+    // through the launch table, as the launchers go: -1 if it had no kernel of the plan's kind for this form
+    const ZgemmKind kind = zgemm_plan(form, lu_tile, M, N, K, batch, b_layout, conj_a != 0, conj_b != 0);
+    int family = -1;
+    auto report = [&](auto, int fam, int bm, int bn, int) { family = fam; if (bm_out) *bm_out = bm; if (bn_out) *bn_out = bn; };
+    if (form == MAUS_ZGEMM_LU) with_kernel<true, 0, false, false>(kind, report);
+    else with_form(b_layout, conj_a != 0, conj_b != 0, [&](auto bl, auto ca, auto cb) {
+        with_kernel<false, decltype(bl)::value, decltype(ca)::value, decltype(cb)::value>(kind, report); });
+    return family;
+}
 
 }  // extern "C"

@@ -440,6 +440,22 @@ int maus_few_rows_get_method(maus_ctx* ctx);
 int maus_few_rows_kernel_for(maus_ctx* ctx, int M, int N, int K, int b_layout, int conj_a, int conj_b, int* slices_out);
 int maus_few_rows_plan(int method, int slices, int M, int N, int K, int b_layout, int conj_a, int conj_b, int* slices_out);
 int maus_few_rows_workspace_allocs(maus_ctx* ctx);
+/* Which kernel a dense product C[M,N] = op(A)[M,K] op(B)[K,N] on `batch` matrices runs: the library's dispatch rule (zgemm_plan
+ * in csrc/zgemm.hip, the one place where it is stated), without a context or a device.
+ *   form      MAUS_ZGEMM_ROWS: row-major operands in either B layout with either operand conjugated -- every product outside the
+ *             LU factorisation (population products, GMRES, the Hermitian reduction, maus_zgemm_host).  MAUS_ZGEMM_LU: the
+ *             trailing updates on the LU's tile-major workspace; plain layout only.
+ *   lu_tile   what the environment variable MAUS_LU_TILE selects for the LU form (the library reads it once per process; this
+ *             function never does): MAUS_LU_TILE_DEFAULT (unset), MAUS_LU_TILE_64X64, MAUS_LU_TILE_128X64.  Ignored by the rows form.
+ * Returns the kernel family -- MAUS_ZGEMM_4M (register-staged, four real products per complex one), MAUS_ZGEMM_3M (register-
+ * staged, three) or MAUS_ZGEMM_3M_DMA (three, operands staged by LDS-DMA) -- and the workgroup tile in bm_out x bn_out (either may
+ * be NULL).  -1 for bad arguments: an unknown form or tile mode, a size or batch below 1, a layout other than 0 / 1, or a layout
+ * or conjugation on the LU form.  (Products of at most 32 rows under maus_few_rows_set_method(ctx, 1): maus_few_rows_plan.) */
+enum { MAUS_ZGEMM_ROWS = 0, MAUS_ZGEMM_LU = 1 };
+enum { MAUS_LU_TILE_DEFAULT = 0, MAUS_LU_TILE_64X64 = 1, MAUS_LU_TILE_128X64 = 2 };
+enum { MAUS_ZGEMM_4M = 0, MAUS_ZGEMM_3M = 1, MAUS_ZGEMM_3M_DMA = 2 };
+int maus_zgemm_plan(int form, int lu_tile, int M, int N, int K, int batch, int b_layout, int conj_a, int conj_b,
+                    int* bm_out, int* bn_out);
 /* Products with a CSR-bound matrix (every one goes through the same launcher: the Rayleigh quotient, the residuals, the SVD power
  * step, the GMRES products, the Lanczos steps).  The lane-per-row schedule (maus_matrix_is_sparse = 1) can read its operand from a
  * second, sliced-ELL copy: rows in slices of 64, slice s as wide as its longest row, entry p of row r at off[s] + 64 p + (r & 63),

@@ -18,21 +18,10 @@ import pytest
 
 import lu_cases as lc
 import lu_tile_child as child
+from zgemm_cases import LT_MIN, LU_TILES as TILES, lu_variant
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-TILES = ["default", "64x64", "128x64"]
 CASES = list(child.lu_tile_cases())
-# the dispatch of maus_zgemm_launch_lu, restated
-LT_MIN, LT_K, LT_TILES, DMA_KMIN = 1024, 256, 4096, 64
-
-
-def large_tile(tile, M, N, K, G):
-    """Does the update go to the 128 x 64 tile under this MAUS_LU_TILE?"""
-    if not (M > 32 and K % 8 == 0 and K >= DMA_KMIN and M >= LT_MIN and N >= LT_MIN):
-        return False
-    if tile == "128x64":
-        return True
-    return tile == "default" and K >= LT_K and -(-M // 128) * -(-N // 64) * G >= LT_TILES
 
 
 @pytest.fixture(scope="module")
@@ -82,7 +71,7 @@ def test_case_reaches_the_large_tile(runs, tile, name):
     here.  The other two runs are the comparison: none of their updates goes to the large tile."""
     L = runs[tile][f"{name}/launches"]
     assert L.shape[0] > 0, "no trailing update was logged"
-    served = np.array([large_tile(tile, *row) for row in L.tolist()])
+    served = np.array([lu_variant(tile, *row)[0] == "dma3m_128x64_lu" for row in L.tolist()])
     if tile != "128x64":
         assert not served.any(), f"{tile}/{name}: {L[served][:4].tolist()} go to the 128 x 64 tile"
         return

@@ -55,7 +55,7 @@ int main(int argc, char** argv) {
         float ms = 0; CK(hipEventElapsedTime(&ms, t0, t1));
         ms /= iters;
         CK(hipGetLastError());
-        printf("M=%d N=%d K=%d pop%s%s%s: %.3f ms per launch, %.1f TFLOP/s (8MNK)\n", M, N, K, plain ? " plain" : "", conja ? " conja" : "", conjb ? " conjb" : "",
+        printf("M=%d N=%d K=%d pop%s%s%s: %.4f ms per launch, %.1f TFLOP/s (8MNK)\n", M, N, K, plain ? " plain" : "", conja ? " conja" : "", conjb ? " conjb" : "",
                ms, 8.0 * M * N * K / (ms * 1e-3) / 1e12);
         return 0;
     }
@@ -90,7 +90,7 @@ int main(int argc, char** argv) {
         float ms = 0; CK(hipEventElapsedTime(&ms, t0, t1));
         ms /= iters;
         CK(hipGetLastError());
-        printf("M=%d N=%d K=%d npad=%d batch=%d lu%s: %.3f ms per launch, %.1f TFLOP/s (8MNK)\n", M, N, K, npad, batch, permute ? " perm" : "",
+        printf("M=%d N=%d K=%d npad=%d batch=%d lu%s: %.4f ms per launch, %.1f TFLOP/s (8MNK)\n", M, N, K, npad, batch, permute ? " perm" : "",
                ms, 8.0 * M * N * K * batch / (ms * 1e-3) / 1e12);
         return 0;
     }
@@ -116,7 +116,7 @@ int main(int argc, char** argv) {
     float ms = 0; CK(hipEventElapsedTime(&ms, t0, t1));
     ms /= iters;
     CK(hipGetLastError());
-    printf("M=%d N=%d K=%d ld=%d batch=%d%s%s: %.3f ms per launch, %.1f TFLOP/s (8MNK)\n", M, N, K, ld, batch, zero ? " zero" : "", shared ? " shared" : "",
+    printf("M=%d N=%d K=%d ld=%d batch=%d%s%s: %.4f ms per launch, %.1f TFLOP/s (8MNK)\n", M, N, K, ld, batch, zero ? " zero" : "", shared ? " shared" : "",
            ms, 8.0 * M * N * K * batch / (ms * 1e-3) / 1e12);
     (void)hipFree(base);
     return 0;
