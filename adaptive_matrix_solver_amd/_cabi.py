@@ -30,6 +30,7 @@ SYMBOLS = [
     "maus_gmres_set_method", "maus_gmres_get_method", "maus_gmres_kernel_for",
     "maus_few_rows_set_method", "maus_few_rows_get_method", "maus_few_rows_kernel_for", "maus_few_rows_plan", "maus_few_rows_workspace_allocs",
     "maus_zgemm_plan",
+    "maus_pop_draw", "maus_pop_draw_plan", "maus_pop_draw_min_len",
     "maus_spmm_set_method", "maus_spmm_get_method", "maus_spmm_kernel_for", "maus_spmm_plan", "maus_spmm_sell_info",
     "maus_device_count", "maus_comm_unique_id", "maus_comm_init", "maus_comm_destroy", "maus_comm_info",
     "maus_comm_allgather_records", "maus_comm_allgather_rows", "maus_comm_bcast", "maus_comm_bcast_eigvecs", "maus_comm_set_matrix", "maus_comm_stats",
@@ -51,6 +52,7 @@ ZGEMM_ROWS, ZGEMM_LU = 0, 1                          # maus_zgemm_plan: the form
 LU_TILE_DEFAULT, LU_TILE_64X64, LU_TILE_128X64 = 0, 1, 2   # ... what MAUS_LU_TILE selects ...
 ZGEMM_4M, ZGEMM_3M, ZGEMM_3M_DMA = 0, 1, 2           # ... and the kernel family it returns
 SPMM_SCHEDULES = {0: None, 1: "rows", 2: "wave"}     # maus_matrix_is_sparse: dense / lane per row / wave per row
+DRAW_RAW, DRAW_UNIT, DRAW_NORM = 0, 1, 2             # maus_pop_draw: kinds
 SPMM_CSR, SPMM_SELL = 0, 1                           # maus_spmm_set_method
 SPMM_KERNEL_NONE, SPMM_KERNEL_ROWS, SPMM_KERNEL_WAVE, SPMM_KERNEL_SELL = 0, 1, 2, 3   # maus_spmm_kernel_for / maus_spmm_plan
 
@@ -161,6 +163,10 @@ def load_library():
         "maus_few_rows_plan": ([C.c_int] * 8 + [C.POINTER(C.c_int)], C.c_int),
         "maus_few_rows_workspace_allocs": ([vp], C.c_int),
         "maus_zgemm_plan": ([C.c_int] * 9 + [ip, ip], C.c_int),
+        "maus_pop_draw": ([vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp], C.c_int),
+        "maus_pop_draw_plan": ([C.c_int, C.c_int, vp, C.c_int, C.c_int, ip, C.POINTER(C.c_int64), ip, C.POINTER(C.c_int64),
+                                C.POINTER(C.c_int64), vp, vp, C.c_int], C.c_int),
+        "maus_pop_draw_min_len": ([], C.c_int),
         "maus_spmm_set_method": ([vp, C.c_int, C.c_int], C.c_int),
         "maus_spmm_get_method": ([vp], C.c_int),
         "maus_spmm_kernel_for": ([vp, C.c_int], C.c_int),
@@ -363,6 +369,30 @@ class Context:
         out = np.empty((s.shape[0], length), dtype=np.complex128)
         self._ck(self.lib.maus_pop_get(self.h, which, _ptr(s), s.shape[0], _ptr(out), length), "maus_pop_get")
         return out
+
+    def pop_draw(self, which, length, slots, kinds, scale, state, ordinals, substreams=0):
+        """Rows `slots` of population array `which` drawn on the device from the legacy NumPy stream (maus_pop_draw): draw k
+        is the pair np.random.rand(length) + 1j*np.random.rand(length) number ordinals[k] counted from `state`
+        (np.random.get_state()), of kind kinds[k] (DRAW_RAW / DRAW_UNIT / DRAW_NORM) and scale[k] (None: 1.0).  Returns the
+        norms.  The caller advances its own stream."""
+        s = self._slots(slots)
+        k = s.shape[0]
+        kd = np.ascontiguousarray(kinds, dtype=np.int32)
+        ords = np.ascontiguousarray(ordinals, dtype=np.int32)
+        assert kd.shape == (k,) and ords.shape == (k,)
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64)
+        assert sc is None or sc.shape == (k,)
+        pd = MtDesc()
+        C.memmove(pd.key, np.ascontiguousarray(state[1], dtype=np.uint32).ctypes.data, 624 * 4)
+        pd.pos = int(state[2]); pd.words_per_candidate = 4 * int(length); pd.lead_words = 0
+        pd.ordinals = ords.ctypes.data_as(C.POINTER(C.c_int32))
+        norms = np.zeros(k, dtype=np.float64)
+        self._ck(self.lib.maus_pop_draw(self.h, int(which), int(length), k, _ptr(s), _ptr(kd), None if sc is None else _ptr(sc),
+                                        C.cast(C.pointer(pd), C.c_void_p), int(substreams), _ptr(norms)), "maus_pop_draw")
+        return norms
+
+    def pop_draw_min_len(self) -> int:
+        return int(self.lib.maus_pop_draw_min_len())
 
     def pop_copy(self, which_dst, which_src, slots):
         s = self._slots(slots)
@@ -905,6 +935,28 @@ def zgemm_plan(form, lu_tile, M, N, K, batch=1, b_layout=0, conj_a=False, conj_b
     if fam < 0:
         raise MausHipError(f"maus_zgemm_plan: bad form, tile mode, sizes or layout ({form}, {lu_tile}, {M}, {N}, {K}, {batch}, {b_layout}, {conj_a}, {conj_b})")
     return int(fam), int(bm.value), int(bn.value)
+
+
+def pop_draw_plan(length, ordinals, pos, substreams=0):
+    """The generator plan of a maus_pop_draw call (maus_pop_draw_plan): a dict with S, E, ngen, the jump strides dj / dj2 in
+    blocks of 624 words and the arrays extra / rpos, generator (k, sb, part) at index (k * S + sb) * 2 + part.  Needs neither
+    a context nor a device."""
+    lib = load_library()
+    ords = np.ascontiguousarray(ordinals, dtype=np.int32)
+    S, ngen = C.c_int(), C.c_int()
+    E, dj, dj2 = C.c_int64(), C.c_int64(), C.c_int64()
+    args = (int(length), int(ords.shape[0]), _ptr(ords), int(pos), int(substreams), C.byref(S), C.byref(E), C.byref(ngen), C.byref(dj), C.byref(dj2))
+    if lib.maus_pop_draw_plan(*args, None, None, 0) != 0:
+        raise MausHipError(f"maus_pop_draw_plan: bad length, count, ordinals, position or sub-stream count ({length}, {ords.shape[0]}, {pos}, {substreams})")
+    extra = np.zeros(ngen.value, dtype=np.int32)
+    rpos = np.zeros(ngen.value, dtype=np.int32)
+    if lib.maus_pop_draw_plan(*args, _ptr(extra), _ptr(rpos), int(ngen.value)) != 0:
+        raise MausHipError("maus_pop_draw_plan failed")
+    return {"S": int(S.value), "E": int(E.value), "ngen": int(ngen.value), "dj": int(dj.value), "dj2": int(dj2.value), "extra": extra, "rpos": rpos}
+
+
+def pop_draw_min_len() -> int:
+    return int(load_library().maus_pop_draw_min_len())
 
 
 def spmm_plan(method, fill_cap_percent, rows, nnz, padded) -> int:

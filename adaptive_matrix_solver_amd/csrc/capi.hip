@@ -824,21 +824,15 @@ static int mt_buf_reserve(maus_ctx* c, int sbi, int ngen, size_t nints) {
     return 0;
 }
 
-// MAUS_PERT_MT19937: generator start states for candidates [first, first+g) of the run by binary lifting (over the
-// draw index m, then over the sub-stream index b), then the H build that regenerates the draws (mtdev.hip).  The plan
-// itself (pure host arithmetic on stream offsets) lives in mtplan.cpp so that it can be built and run under the CPU
-// sanitizers (`make asan`).
-static int mt_prepare_and_build(maus_ctx* c, const LuWs& w, const maus_mt_desc* d, int first, int g, int rhs_mode, int lo, int sbi, int tiled) {
-    if ((int)c->mt_bufs.size() <= sbi) c->mt_bufs.resize(sbi + 1);
-    maus_ctx::MtBuf& mb = c->mt_bufs[sbi];
-    const int n = w.n;
-    int s_override = 0;
-    { const char* e = getenv("MAUS_MT_SUBSTREAMS"); if (e && atoi(e) > 0) s_override = std::min(64, atoi(e)); }
-    MausMtPlan& pl = c->mt_plan;
-    const char* perr = nullptr;
-    if (maus_mt_plan(d, n, first, g, s_override, &pl, &perr)) FAIL(c, perr ? perr : "maus_mt_plan failed");
+// Generator start states of a plan (mtplan.cpp) from the one NumPy state `key`, on stream st in the buffers of sub-batch
+// `sbi`: the state and the plan's staging image go up, the tap lists of the jump polynomials come from the context's cache
+// (a new one is computed on the host and uploaded), every generator starts as a copy of the state and the plan's levels --
+// the lifting over the draw index, then the doubling tree over the sub-stream index -- are applied by mt_jump_kernel.  Shared
+// by the H build of the dense regulariser and by maus_pop_draw.  On return mb.ints holds extra[ngen] | rpos[ngen] | ...
+static int mt_prepare_states(maus_ctx* c, hipStream_t st, const MausMtPlan& pl, const uint32_t* key, int sbi) {
     const int ngen = pl.ngen;
     if (mt_buf_reserve(c, sbi, ngen, pl.hs.size())) return -1;
+    maus_ctx::MtBuf& mb = c->mt_bufs[sbi];
     struct DevLevel { size_t off; int count; MausJumpPolys P; int src_off; bool multi; };
     std::vector<DevLevel> levels;
     auto poly_taps = [&](uint64_t J, MausJumpPolys& P, int v) -> int {     // tap list of x^J mod phi, cached on the device
@@ -874,16 +868,74 @@ static int mt_prepare_and_build(maus_ctx* c, const LuWs& w, const maus_mt_desc* 
         levels.push_back(D);
     }
     const std::vector<int>& hs = pl.hs;
-    if (maus_h2d(c, mb.base, d->key, sizeof(uint32_t) * 624, w.st)) return -1;
-    if (maus_h2d(c, mb.ints, hs.data(), sizeof(int) * hs.size(), w.st)) return -1;
-    HIPCHK(c, hipStreamSynchronize(w.st));                       // staging (hs, d->key) is reusable from here on
-    maus_mt_copy_states(w.st, mb.states, mb.base, ngen);
-    for (const DevLevel& L : levels) maus_mt_jump(w.st, mb.states, mb.ints + L.off, L.multi ? mb.ints + L.off + L.count : nullptr, L.count, L.P, L.src_off);
+    if (maus_h2d(c, mb.base, key, sizeof(uint32_t) * 624, st)) return -1;
+    if (maus_h2d(c, mb.ints, hs.data(), sizeof(int) * hs.size(), st)) return -1;
+    HIPCHK(c, hipStreamSynchronize(st));                         // staging (hs, key) is reusable from here on
+    maus_mt_copy_states(st, mb.states, mb.base, ngen);
+    for (const DevLevel& L : levels) maus_mt_jump(st, mb.states, mb.ints + L.off, L.multi ? mb.ints + L.off + L.count : nullptr, L.count, L.P, L.src_off);
+    return 0;
+}
+
+// MAUS_PERT_MT19937: generator start states for candidates [first, first+g) of the run by binary lifting (over the
+// draw index m, then over the sub-stream index b), then the H build that regenerates the draws (mtdev.hip).  The plan
+// itself (pure host arithmetic on stream offsets) lives in mtplan.cpp so that it can be built and run under the CPU
+// sanitizers (`make asan`).
+static int mt_prepare_and_build(maus_ctx* c, const LuWs& w, const maus_mt_desc* d, int first, int g, int rhs_mode, int lo, int sbi, int tiled) {
+    const int n = w.n;
+    int s_override = 0;
+    { const char* e = getenv("MAUS_MT_SUBSTREAMS"); if (e && atoi(e) > 0) s_override = std::min(64, atoi(e)); }
+    MausMtPlan& pl = c->mt_plan;
+    const char* perr = nullptr;
+    if (maus_mt_plan(d, n, first, g, s_override, &pl, &perr)) FAIL(c, perr ? perr : "maus_mt_plan failed");
+    const int ngen = pl.ngen;
+    if (mt_prepare_states(c, w.st, pl, d->key, sbi)) return -1;
+    maus_ctx::MtBuf& mb = c->mt_bufs[sbi];
     const int* d_extra = mb.ints; const int* d_rpos = mb.ints + ngen;
     prof_tick(c, KC_BUILD, 0, 0, 0);
     maus_build_h_mt(w.st, c->A, n, w.npad, w.ldh, w.strideH, w.H, g, pl.S, (long)pl.E, c->d_c1 + lo, c->d_r1 + lo, rhs_mode, c->X, c->ldp,
                     c->d_slots + lo, c->b, mb.states, d_extra, d_rpos, w.flags, tiled);
     prof_tick(c, KC_BUILD, 1, 0, 32.0 * w.npad * w.ldh * g);
+    return 0;
+}
+
+// Candidate vectors drawn on the device (include/maus_hip.h): the plan of mtplan.cpp for draws of `len` elements, the start
+// states as for the H build, then the draw and join kernels of mtdev.hip.  Accounted under the vector class.
+int maus_pop_draw(maus_ctx* c, int which, int len, int count, const int32_t* slots, const int32_t* kinds, const double* scale,
+                  const maus_mt_desc* desc, int substreams, double* norm_out) {
+    av_drop_all(c);
+    c128* P = pop_array(c, which);
+    if (!P) FAIL(c, "maus_pop_draw: population not reserved / bad array id");
+    if (count < 0 || !desc || (count > 0 && (!slots || !kinds || !norm_out))) FAIL(c, "maus_pop_draw: bad arguments");
+    if (len < maus_pop_draw_min_len()) FAIL(c, "maus_pop_draw: len below maus_pop_draw_min_len()");
+    if (len > c->ldp || len > maus_sparse_max_n()) FAIL(c, "maus_pop_draw: len exceeds the row length / maus_sparse_max_n()");
+    if (substreams < 0 || substreams > 64) FAIL(c, "maus_pop_draw: substreams must be 0 (the rule) or 1..64");
+    if (desc->words_per_candidate != 4ull * (uint64_t)len || desc->lead_words != 0) FAIL(c, "maus_pop_draw: desc must have words_per_candidate = 4*len and lead_words = 0");
+    if (count == 0) return 0;
+    for (int k = 0; k < count; ++k) {
+        if (kinds[k] != MAUS_DRAW_RAW && kinds[k] != MAUS_DRAW_UNIT && kinds[k] != MAUS_DRAW_NORM) FAIL(c, "maus_pop_draw: unknown kind");
+        if (kinds[k] != MAUS_DRAW_NORM && (slots[k] < 0 || slots[k] >= c->cap)) FAIL(c, "slot out of range");
+    }
+    if (which == MAUS_POP_U) { std::vector<int> sl(slots, slots + count); ahu_drop(c, sl.data(), count); }
+    MausMtPlan& pl = c->mt_plan;
+    const char* perr = nullptr;
+    if (maus_pop_draw_plan_desc(desc, len, count, substreams, &pl, &perr)) FAIL(c, perr ? perr : "maus_pop_draw: plan failed");
+    if (ensure_scalars(c, count)) return -1;
+    const int nchunks = (len + maus_pop_draw_chunk() - 1) / maus_pop_draw_chunk();
+    if (ensure_scratch(c, sizeof(double) * 2 * (size_t)nchunks * count)) return -1;
+    std::vector<double> sc(count, 1.0);
+    if (scale) for (int k = 0; k < count; ++k) sc[k] = scale[k];
+    if (maus_h2d(c, c->d_slots, slots, sizeof(int) * count, c->st)) return -1;
+    if (maus_h2d(c, c->d_i1, kinds, sizeof(int) * count, c->st)) return -1;
+    if (maus_h2d(c, c->d_r1, sc.data(), sizeof(double) * count, c->st)) return -1;
+    if (mt_prepare_states(c, c->st, pl, desc->key, 0)) return -1;
+    maus_ctx::MtBuf& mb = c->mt_bufs[0];
+    prof_tick(c, KC_VEC, 0, 0, 0);
+    maus_pop_draw_launch(c->st, P, c->ldp, len, count, pl.S, (long)pl.E, c->d_slots, c->d_i1, c->d_r1, mb.states, mb.ints, mb.ints + pl.ngen,
+                         (double*)c->scratch, c->d_r2);
+    prof_tick(c, KC_VEC, 1, 0, 32.0 * len * count);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(norm_out, c->d_r2, sizeof(double) * count, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
     return 0;
 }
 

@@ -28,6 +28,9 @@ void maus_build_h_mt(hipStream_t st, const c128* A, int n, int npad, long ldh, l
                      const c128* d_shift, const double* d_psi, int rhs_mode, const c128* X, long ldx, const int* d_slots,
                      const c128* bvec, const uint32_t* states, const int* extra, const int* rpos, int* flags, int tiled);
 int maus_mt_jump_poly(uint64_t J, uint64_t* out312);
+int maus_pop_draw_chunk();
+void maus_pop_draw_launch(hipStream_t st, c128* P, long ldp, int len, int count, int S, long E, const int* d_slots, const int* d_kinds,
+                          const double* d_scale, const uint32_t* states, const int* extra, const int* rpos, double* part, double* d_norm);
 void maus_launch_rayleigh_dots(hipStream_t st, const c128* X, const c128* Y, long ld, const int* slots, int count, int n, c128* num, c128* den);
 void maus_launch_relax(hipStream_t st, c128* X, const c128* W, long ld, const int* slots, int count, int n, const c128* alpha, int normalise, double* norm_out);
 void maus_launch_residual(hipStream_t st, int kind, const c128* X, const c128* Y, long ld, const int* slots, int count, int n,

@@ -284,7 +284,9 @@ extern "C" int maus_mt19937_jump(uint32_t* key, int32_t* pos, uint64_t nwords) {
     const uint64_t qb = (total - 1) / N;                 // number of block regenerations NumPy would perform
     const int32_t newpos = (int32_t)(total - qb * N);    // 1..624
     if (qb == 0) { *pos = newpos; return 0; }
-    if (qb <= 4) { for (uint64_t k = 0; k < qb; ++k) regen(key); *pos = newpos; return 0; }
+    // short advances are walked: 512 regenerations cost about what one evaluation of a cached polynomial does, and a new
+    // polynomial tens of milliseconds (the candidate vectors of maus_pop_draw advance by 4N words per vector)
+    if (qb <= 512) { for (uint64_t k = 0; k < qb; ++k) regen(key); *pos = newpos; return 0; }
     // F^(624*(qb-1)) by the polynomial, then one real regeneration (which also repairs the 31
     // low bits of word 0 that the 19937-bit state does not carry)
     const uint64_t J = (uint64_t)N * (qb - 1);

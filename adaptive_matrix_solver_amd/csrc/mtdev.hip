@@ -15,8 +15,10 @@
 #include "common.h"
 #include "luws.h"
 #include "mtjump.h"
+#include "mtplan.h"
 #include <cstdint>
 #include <cstdlib>
+#include <algorithm>
 
 namespace {
 
@@ -296,6 +298,123 @@ build_h_mt4_kernel(const c128* __restrict__ A, int n, int npad, long ldh, long s
     if (__any(bad) && lane == 0) atomicOr(&flags[g], 1);
 }
 
+// ---------------------------------------------------------------------------------------
+// Candidate vectors from the stream (maus_pop_draw): row = U1 + i U2, U1 then U2 = np.random.rand(N), i.e. 4N consecutive
+// words per vector (AMS:130).  The workgroup of build_h_mt4_kernel without a matrix: waves 0 / 1 produce the U1 / U2 stream
+// in three LDS blocks each, waves 2 / 3 temper, convert and store (u1, u2) into the destination row, one barrier per block.
+// grid = (draw, sub-stream).
+//   * The squared norm is summed per CHUNK of DRAW_CHUNK elements counted from the start of the draw -- a constant of this
+//     file -- and the plan makes every sub-stream start on a chunk boundary (mtplan.cpp: E is a multiple of DRAW_CHUNK), so a
+//     chunk always belongs to one workgroup and is always summed in the same order: a lane adds its own elements of the
+//     chunk's 16 blocks in stream order, the wave joins its lanes on the DPP network, and each of the two consumer waves
+//     leaves one partial sum per chunk.  pop_draw_join_kernel adds the 2 * nchunks partial sums of a draw in one order.  No
+//     atomics; nothing depends on the sub-stream count, on the other draws of the call or on the slot.
+//   * MAUS_DRAW_NORM stores no row: it sums |((u1 - .5) + i (u2 - .5)) * scale|^2 (the spawn's v_pert, AMS:544).
+// A workgroup whose sub-stream starts behind the end of the draw (forced sub-stream counts) has nothing to do.
+// ---------------------------------------------------------------------------------------
+constexpr int DRAW_CHUNK_BLOCKS = 16;
+constexpr int DRAW_CHUNK = DRAW_CHUNK_BLOCKS * EPB;      // 4992 elements
+static_assert(DRAW_CHUNK == MAUS_POP_DRAW_CHUNK, "the plan aligns the sub-streams to the kernel's chunks");
+constexpr int DRAW_RAW = 0, DRAW_UNIT = 1, DRAW_NORM = 2;   // MAUS_DRAW_* (include/maus_hip.h)
+
+__global__ void __launch_bounds__(256)
+pop_draw_kernel(c128* __restrict__ P, long ldp, int len, const int* __restrict__ slots, const int* __restrict__ kinds,
+                const double* __restrict__ scale, const uint32_t* __restrict__ states /* [G][S][2][624] */,
+                const int* __restrict__ extra /* [G][S][2] */, const int* __restrict__ rpos /* [G][S][2] */, long E,
+                int nchunks, double* __restrict__ part /* [G][nchunks][2] */)
+{
+    __shared__ uint32_t blk[2][NBUF][MTN];   // [stream][buffer][word]
+    const int g = blockIdx.x, sb = blockIdx.y, S = gridDim.y, tid = threadIdx.x, lane = tid & 63;
+    const long e0 = (long)sb * E;
+    if (e0 >= len) return;                                    // the whole workgroup
+    const int role = ((tid >> 6) + g + sb) & 3;               // 0 / 1: producer of U1 / U2, 2 / 3: consumers
+    const long gi = ((long)g * S + sb) * 2;                   // index of this workgroup's first generator
+    const int kind = kinds[g];
+    const double sc = scale[g];
+    c128* __restrict__ row = (kind == DRAW_NORM) ? nullptr : P + (long)slots[g] * ldp;
+
+    // each producer brings its stream to its start block and writes the block behind it
+    const int ex0 = extra[gi], ex1 = extra[gi + 1];
+    int c0 = ex0 % NBUF, c1 = ex1 % NBUF;                    // buffers holding block t of U1 / U2 (t = 0 now)
+    if (role < 2) {
+        uint32_t (*B)[MTN] = blk[role];
+        const uint32_t* St = states + (gi + role) * MTN;
+        for (int k = lane; k < MTN; k += 64) B[0][k] = St[k];
+        __builtin_amdgcn_wave_barrier();
+        const int ex = role ? ex1 : ex0;
+        int cur = 0;
+        for (int it = 0; it <= ex; ++it) { const int nx = (cur + 1 == NBUF) ? 0 : cur + 1; regen_wave(B[cur], B[nx], lane); cur = nx; }
+    }
+    __syncthreads();
+
+    const int w0 = rpos[gi], w1 = rpos[gi + 1];      // first unread word of each stream's start block
+    const long total = min((long)len, e0 + E);       // this workgroup's element range is [e0, total)
+    const int niter = (int)((total - e0 + EPB - 1) / EPB);
+    const int ci = role - 2;                         // consumer: chunks of 64 elements ci, ci + 2, (ci + 4) of every block
+    constexpr int CPC = (ECH + 1) / 2;
+    const long chunk0 = e0 / DRAW_CHUNK;             // e0 is a multiple of DRAW_CHUNK
+    double acc = 0.0;
+    for (int it = 0; it < niter; ++it) {
+        const int n0 = (c0 + 1 == NBUF) ? 0 : c0 + 1, n1 = (c1 + 1 == NBUF) ? 0 : c1 + 1;
+        if (role < 2) {
+            // block it+2 from block it+1
+            const int nx = role ? n1 : n0, nn = (nx + 1 == NBUF) ? 0 : nx + 1;
+            regen_wave(blk[role][nx], blk[role][nn], lane);
+        } else {
+            const long e = e0 + (long)it * EPB;
+            const uint32_t* cu0 = blk[0][c0]; const uint32_t* nx0 = blk[0][n0];
+            const uint32_t* cu1 = blk[1][c1]; const uint32_t* nx1 = blk[1][n1];
+#pragma unroll
+            for (int u = 0; u < CPC; ++u) {
+                const int c = ci + 2 * u;
+                const int q = c * 64 + lane;
+                if (c < ECH && q < EPB && e + q < total) {
+                    const int t0 = w0 + 2 * q, t1 = w1 + 2 * q;
+                    const uint32_t a0 = (t0 < MTN) ? cu0[t0] : nx0[t0 - MTN], b0 = (t0 + 1 < MTN) ? cu0[t0 + 1] : nx0[t0 + 1 - MTN];
+                    const uint32_t a1 = (t1 < MTN) ? cu1[t1] : nx1[t1 - MTN], b1 = (t1 + 1 < MTN) ? cu1[t1 + 1] : nx1[t1 + 1 - MTN];
+                    const double u0 = ((double)(temper(a0) >> 5) * 67108864.0 + (double)(temper(b0) >> 6)) / 9007199254740992.0;
+                    const double u1 = ((double)(temper(a1) >> 5) * 67108864.0 + (double)(temper(b1) >> 6)) / 9007199254740992.0;
+                    double a = u0, b = u1;
+                    if (kind == DRAW_NORM) { a = __dmul_rn(__dsub_rn(u0, 0.5), sc); b = __dmul_rn(__dsub_rn(u1, 0.5), sc); }
+                    else row[e + q] = cmake(u0, u1);
+                    acc = __dadd_rn(acc, __dadd_rn(__dmul_rn(a, a), __dmul_rn(b, b)));
+                }
+            }
+            if ((it % DRAW_CHUNK_BLOCKS) == DRAW_CHUNK_BLOCKS - 1 || it == niter - 1) {
+                const double s = wave_sum_dpp(acc);
+                if (lane == 0) part[((long)g * nchunks + chunk0 + it / DRAW_CHUNK_BLOCKS) * 2 + ci] = s;
+                acc = 0.0;
+            }
+        }
+        c0 = n0; c1 = n1;
+        lds_barrier();            // LDS only: the consumers' stores stay in flight across it
+    }
+}
+
+// norm_out[g] = sqrt of the draw's 2 * nchunks partial sums added in one order (lane l takes chunks l, l + 64, ..., then the
+// DPP join); a MAUS_DRAW_UNIT row becomes (row * (1 / norm)) * scale, component by component -- NumPy's v / np.linalg.norm(v)
+// on complex128 multiplies by the reciprocal, and a real scale leaves each component one product.  grid = (draw, row blocks).
+__global__ void __launch_bounds__(256)
+pop_draw_join_kernel(c128* __restrict__ P, long ldp, int len, const int* __restrict__ slots, const int* __restrict__ kinds,
+                     const double* __restrict__ scale, int nchunks, const double* __restrict__ part, double* __restrict__ norm_out)
+{
+    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const double* p = part + (long)g * nchunks * 2;
+    double a = 0.0;
+    for (int k = lane; k < nchunks; k += 64) a = __dadd_rn(a, __dadd_rn(p[2 * k], p[2 * k + 1]));
+    const double nrm = __dsqrt_rn(wave_sum_dpp(a));
+    if (blockIdx.y == 0 && tid == 0) norm_out[g] = nrm;
+    if (kinds[g] != DRAW_UNIT) return;
+    const double inv = __ddiv_rn(1.0, nrm), sc = scale[g];
+    c128* __restrict__ row = P + (long)slots[g] * ldp;
+    for (long e = (long)blockIdx.y * 256 + tid; e < len; e += (long)gridDim.y * 256) {
+        c128 v = row[e];
+        v.x = __dmul_rn(__dmul_rn(v.x, inv), sc);
+        v.y = __dmul_rn(__dmul_rn(v.y, inv), sc);
+        row[e] = v;
+    }
+}
+
 }  // namespace
 
 void maus_mt_copy_states(hipStream_t st, uint32_t* states, const uint32_t* base, int count) {
@@ -311,4 +430,13 @@ void maus_build_h_mt(hipStream_t st, const c128* A, int n, int npad, long ldh, l
                      const c128* bvec, const uint32_t* states, const int* extra, const int* rpos, int* flags, int tiled) {
     hipLaunchKernelGGL(build_h_mt4_kernel, dim3(G, S), dim3(256), 0, st, A, n, npad, ldh, strideH, H, d_shift, d_psi, rhs_mode,
                        X, ldx, d_slots, bvec, states, extra, rpos, E, flags, tiled);
+}
+int maus_pop_draw_chunk() { return DRAW_CHUNK; }
+void maus_pop_draw_launch(hipStream_t st, c128* P, long ldp, int len, int count, int S, long E, const int* d_slots, const int* d_kinds,
+                          const double* d_scale, const uint32_t* states, const int* extra, const int* rpos, double* part, double* d_norm) {
+    const int nchunks = (len + DRAW_CHUNK - 1) / DRAW_CHUNK;
+    hipLaunchKernelGGL(pop_draw_kernel, dim3(count, S), dim3(256), 0, st, P, ldp, len, d_slots, d_kinds, d_scale, states, extra, rpos, E,
+                       nchunks, part);
+    const int jb = std::max(1, std::min(64, (len + 4095) / 4096));
+    hipLaunchKernelGGL(pop_draw_join_kernel, dim3(count, jb), dim3(256), 0, st, P, ldp, len, d_slots, d_kinds, d_scale, nchunks, part, d_norm);
 }

@@ -17,9 +17,20 @@
 #include <algorithm>
 
 int maus_mt_plan(const maus_mt_desc* d, int n, int first, int g, int s_override, MausMtPlan* out, const char** err) {
+    if (n <= 0) { if (err) *err = "maus_mt_plan: bad arguments"; return -1; }
+    // the rule of the dense regulariser: up to 64 sub-streams from n = 2048, each at least ~64 blocks long (measured, below)
+    return maus_mt_plan_len(d, (uint64_t)n * n, first, g, s_override, (n >= 2048) ? 64 : 16, 64 * 312, 1, out, err);
+}
+
+// The same plan for draws of L elements each (one np.random.rand(L) = 2L words; a candidate's two draws are consecutive
+// units of the stream).  L = n*n is the dense regulariser above; L = N with words_per_candidate = 4N, lead_words = 0 is a
+// candidate vector rand(N) + 1j*rand(N) (maus_pop_draw).  s_cap / min_sub: at most s_cap sub-streams per draw, each at
+// least min_sub elements long and a multiple of e_align elements (the last one of a draw takes what is left, possibly nothing).
+int maus_mt_plan_len(const maus_mt_desc* d, uint64_t L, int first, int g, int s_override, int s_cap, uint64_t min_sub,
+                     uint64_t e_align, MausMtPlan* out, const char** err) {
     auto fail = [&](const char* m) { if (err) *err = m; return -1; };
-    if (!d || !out || n <= 0 || g <= 0 || first < 0) return fail("maus_mt_plan: bad arguments");
-    const uint64_t two_n2 = 2ull * n * n;
+    if (!d || !out || L == 0 || L > (1ull << 40) || g <= 0 || first < 0 || s_cap < 1 || min_sub < 1 || e_align < 1) return fail("maus_mt_plan: bad arguments");
+    const uint64_t two_n2 = 2ull * L;
     if (d->pos < 0 || d->pos > 624) return fail("maus_mt_desc: bad position");
     if (d->words_per_candidate % two_n2 || d->lead_words % two_n2 || d->words_per_candidate < 2 * two_n2 || !d->ordinals)
         return fail("maus_mt_desc: words_per_candidate / lead_words must be multiples of 2*n*n");
@@ -30,13 +41,12 @@ int maus_mt_plan(const maus_mt_desc* d, int n, int first, int g, int s_override,
     // H build (round 4: 21.0 -> 20.1 ms per 256-solve call).  Each sub-stream at least ~64 blocks long.
     // Small batches of large matrices go on to 64 sub-streams (32 candidates at n = 4096: 32 instead of 16 -> H build 4.9 -> 3.4 ms,
     // the call 109.0 -> 107.5; at n = 1024 the extra jumps would cost more than the build gains).
-    const int s_cap = (n >= 2048) ? 64 : 16;
     int S = 1;
     while (2 * S <= s_cap && (long)S * std::max(1, g) < 1024) S *= 2;
-    const uint64_t nn = (uint64_t)n * n;
-    while (S > 1 && nn / S < 64 * 312) --S;
+    const uint64_t nn = L;
+    while (S > 1 && nn / S < min_sub) --S;
     if (s_override > 0) S = std::max(1, std::min(64, s_override));
-    const uint64_t E = (nn + S - 1) / S;                          // elements per sub-stream
+    const uint64_t E = ((nn + S - 1) / S + e_align - 1) / e_align * e_align;   // elements per sub-stream
     const int ngen = 2 * g * S;
     const uint64_t dblocks = two_n2 / 624;
     const uint64_t dj = dblocks;                                 // jump stride (blocks) per draw
@@ -89,5 +99,38 @@ int maus_mt_plan(const maus_mt_desc* d, int n, int first, int g, int s_override,
     }
     (void)maxb;
     out->S = S; out->E = E; out->ngen = ngen; out->dj = dj; out->dj2 = dj2;
+    return 0;
+}
+
+// The plan of maus_pop_draw without a context or a device (include/maus_hip.h).
+extern "C" int maus_pop_draw_min_len(void) { return MAUS_POP_DRAW_MIN_LEN; }
+
+int maus_pop_draw_plan_desc(const maus_mt_desc* d, int len, int count, int substreams, MausMtPlan* out, const char** err) {
+    if (len < MAUS_POP_DRAW_MIN_LEN) { if (err) *err = "maus_pop_draw: len below maus_pop_draw_min_len()"; return -1; }
+    // Sub-streams of a vector draw: a sub-stream costs a jump (as much LDS traffic as ~3300 blocks of generation), so each is
+    // at least MAUS_POP_DRAW_MIN_SUB elements (256 blocks) long and a draw has at most 16.  Each starts on a boundary of the
+    // chunks in which the draw kernel sums the squared norm (mtdev.hip), so that the sums do not depend on the sub-stream count.
+    return maus_mt_plan_len(d, (uint64_t)len, 0, count, substreams, 16, MAUS_POP_DRAW_MIN_SUB, MAUS_POP_DRAW_CHUNK, out, err);
+}
+
+extern "C" int maus_pop_draw_plan(int len, int count, const int32_t* ordinals, int pos, int substreams, int* s_out, int64_t* e_out,
+                                  int* ngen_out, int64_t* dj_out, int64_t* dj2_out, int32_t* extra_out, int32_t* rpos_out, int cap) {
+    if (len <= 0 || count <= 0 || !ordinals || substreams < 0) return -1;
+    maus_mt_desc d;
+    d.pos = pos; d.reserved = 0; d.words_per_candidate = 4ull * (uint64_t)len; d.lead_words = 0; d.ordinals = ordinals;
+    MausMtPlan pl;
+    const char* err = nullptr;
+    if (maus_pop_draw_plan_desc(&d, len, count, substreams, &pl, &err)) return -1;
+    if (s_out) *s_out = pl.S;
+    if (e_out) *e_out = (int64_t)pl.E;
+    if (ngen_out) *ngen_out = pl.ngen;
+    if (dj_out) *dj_out = (int64_t)pl.dj;
+    if (dj2_out) *dj2_out = (int64_t)pl.dj2;
+    if (pl.ngen <= cap) {
+        for (int i = 0; i < pl.ngen; ++i) {
+            if (extra_out) extra_out[i] = pl.hs[i];
+            if (rpos_out) rpos_out[i] = pl.hs[pl.ngen + i];
+        }
+    }
     return 0;
 }

@@ -24,3 +24,11 @@ struct MausMtPlan {
 // Candidates [first, first+g) of a run described by d (n x n matrices).  s_override > 0 forces the sub-stream count.
 // Returns 0, or -1 with *err set.
 int maus_mt_plan(const maus_mt_desc* d, int n, int first, int g, int s_override, MausMtPlan* out, const char** err);
+// The same for draws of `L` elements (maus_mt_plan is L = n*n with the dense regulariser's rule): at most s_cap sub-streams per
+// draw, each at least min_sub elements long and a multiple of e_align.
+int maus_mt_plan_len(const maus_mt_desc* d, uint64_t L, int first, int g, int s_override, int s_cap, uint64_t min_sub,
+                     uint64_t e_align, MausMtPlan* out, const char** err);
+// Candidate vectors (maus_pop_draw): `count` pairs of rand(len) draws at d->ordinals[0..count), the rule of a vector draw.
+#define MAUS_POP_DRAW_MIN_SUB (256 * 312)
+#define MAUS_POP_DRAW_CHUNK (16 * 312)          // elements per partial sum of the squared norm (mtdev.hip)
+int maus_pop_draw_plan_desc(const maus_mt_desc* d, int len, int count, int substreams, MausMtPlan* out, const char** err);

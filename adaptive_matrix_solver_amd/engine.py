@@ -29,7 +29,7 @@ import numpy as np
 
 from . import _cabi
 from .band import DIRECT_METHOD
-from .candstore import C_NP, C_PY, EXACT, F_NP, F_PY, MISSING, CandidateStore, HistoryRecord
+from .candstore import C_NP, C_PY, EXACT, F_NP, F_PY, HREF, MISSING, CandidateStore, HistoryRecord
 from ._cabi import KIND_EIG, KIND_LINEAR, KIND_SVD, PERT_MT19937, PERT_NONE, PERT_UNIFORM, POP_U, POP_W, POP_X
 
 # reference constants (AMS:16-26) used by the step
@@ -260,6 +260,17 @@ def sparse_split_mode(mode):
     return mode
 
 
+VECTOR_DRAWS_MODES = ("host", "device", "auto")
+
+
+def vector_draws_mode(mode):
+    """The `vector_draws` keyword: an explicit value, else MAUS_VECTOR_DRAWS, else 'host' ('auto' means 'host')."""
+    mode = mode if mode is not None else os.environ.get("MAUS_VECTOR_DRAWS", "host")
+    if mode not in VECTOR_DRAWS_MODES:
+        raise ValueError(f"vector_draws must be one of {VECTOR_DRAWS_MODES}, not {mode!r}")
+    return "host" if mode == "auto" else mode
+
+
 SPARSE_GMRES_MODES = ("auto", "wide")
 
 
@@ -393,7 +404,7 @@ class DeviceEngine:
 
     def __init__(self, device: int = 0, pert_mode: str = "auto", gmres_compat: str = "rtol",
                  comm=None, ctx=None, eigh_mode: str = "auto", sparse_mode=None, sparse_direct=None, sparse_eigsh=None,
-                 sparse_gmres=None, few_rows=None, sparse_spmm=None, sparse_split=None):
+                 sparse_gmres=None, few_rows=None, sparse_spmm=None, sparse_split=None, vector_draws=None):
         self.ctx = ctx if ctx is not None else _cabi.Context(device)
         cap_blas_threads()
         # Hermitian eigendecomposition (AMS:161), once per matrix: 'host' = scipy.linalg.eigh, the reference's call, (lambda, V)
@@ -469,6 +480,15 @@ class DeviceEngine:
         self._next_slot = 0
         self.store = CandidateStore()           # per-candidate bookkeeping, indexed by slot (candstore.py)
         self._deferred = None                   # candidates whose host vectors wait for one common transfer
+        # the random vectors of new candidates (AMS:129-143; DESIGN §1 "RNG-event replay"): 'host' = np.random.rand on the
+        # host and one upload, as ever, bit for bit; 'device' = candidates of eigenvalue and linear problems constructed
+        # between begin_deferred_push and end_deferred_push take the next pair of rand(N) draws of the stream by number only,
+        # one maus_pop_draw regenerates all of them in their rows on the device and the host stream is advanced by a jump
+        # (opt-in; the draws bit for bit, the normalised vectors to rounding: another summation order of the norm).  SVD
+        # problems, sharded runs, N below maus_pop_draw_min_len() and the engine's own re-initialisations draw on the host.
+        # MAUS_VECTOR_DRAWS sets the default.
+        self.vector_draws = vector_draws_mode(vector_draws)
+        self._draws = None                      # the draws registered in the current bracket (device mode only)
         self.steps_executed = 0
 
     # ---- shared default engine (for stand-alone SolutionCandidate use) ----------------
@@ -630,10 +650,90 @@ class DeviceEngine:
 
     def begin_deferred_push(self) -> None:
         self._deferred = []
+        device = (self.vector_draws == "device" and (self.comm is None or self.comm.world == 1)
+                  and hasattr(self.ctx, "pop_draw"))
+        self._draws = [] if device else None
+
+    def defers_draw(self, n: int, svd: bool = False) -> bool:
+        """Whether a candidate vector of length n constructed now is drawn on the device at the end of the bracket."""
+        return self._draws is not None and not svd and n >= self.ctx.pop_draw_min_len()
+
+    def register_draw(self, cand, scale: float, scalar) -> None:
+        """The next pair of rand(N) draws becomes cand's row: normalised, times scale (AMS:134, 137).  `scalar`: the lambda_k
+        of the candidate's first history entry (None: a linear problem records (x,)); the entry itself is appended here as a
+        placeholder and becomes a reference into the device history store when the row exists."""
+        cand.param_history.append(None)
+        self._draws.append(("unit", cand, float(scale), len(cand._ph) - 1, scalar))
+
+    def register_norm_draw(self, n: int, scale: float, base, base_norm: float) -> None:
+        """The next pair of draws is the v_pert of a spawn from a converged base (AMS:544): only its norm is needed."""
+        self._draws.append(("norm", int(n), float(scale), base, float(base_norm)))
+
+    def draw_vectors(self, length, slots, kinds, scales=None, ordinals=None, pairs=None, which=POP_X, substreams=0):
+        """Rows `slots` drawn on the device from the global NumPy stream (ctx.pop_draw) and the stream advanced by `pairs`
+        pairs of rand(length) draws (default: up to the largest ordinal) without producing them.  Returns the norms."""
+        k = len(slots)
+        ords = np.arange(k, dtype=np.int32) if ordinals is None else np.asarray(ordinals, dtype=np.int32)
+        norms = self.ctx.pop_draw(which, length, slots, kinds, scales, np.random.get_state(), ords, substreams)
+        if pairs is None:
+            pairs = int(ords.max()) + 1 if k else 0
+        _advance_numpy_stream(4 * int(length) * int(pairs))
+        return norms
+
+    def _run_draws(self, draws) -> None:
+        """The registered draws of a bracket: one maus_pop_draw, one jump of the host stream, the first history entries
+        through the device history store.  (The stream-advance workers of the batched step are joined inside the step that
+        starts them, so the global state read here is current.)  A draw whose norm test the host cannot decide from the
+        device norms -- AMS:131's norm > 1e-10, AMS:546's norm_new_v > 1e-9 -- and every draw after it are replayed on the
+        host from the stream position they start at."""
+        n = draws[0][1].N_diag if draws[0][0] == "unit" else draws[0][1]
+        last = {}
+        for k, d in enumerate(draws):
+            if d[0] == "unit":
+                last[id(d[1])] = k              # a candidate re-initialised twice keeps its last vector
+        slots = np.zeros(len(draws), dtype=np.int32)
+        kinds = np.full(len(draws), _cabi.DRAW_NORM, dtype=np.int32)
+        scales = np.ones(len(draws))
+        for k, d in enumerate(draws):
+            if d[0] == "unit" and last[id(d[1])] == k:
+                slots[k], kinds[k], scales[k] = d[1]._slot, _cabi.DRAW_UNIT, d[2]
+            elif d[0] == "norm":
+                scales[k] = d[2]
+        norms = self.ctx.pop_draw(POP_X, n, slots, kinds, scales, np.random.get_state(), np.arange(len(draws), dtype=np.int32))
+        good = len(draws)
+        for k, d in enumerate(draws):
+            if d[0] == "unit":
+                ok = kinds[k] != _cabi.DRAW_UNIT or norms[k] > 1e-10
+            else:                               # ||base + v_pert|| >= ||v_pert|| - ||base||
+                ok = norms[k] * (1.0 - 1e-9) - d[4] > 1e-9
+            if not ok:
+                good = k
+                break
+        _advance_numpy_stream(4 * n * good)
+        drawn = [(k, d) for k, d in enumerate(draws[:good]) if kinds[k] == _cabi.DRAW_UNIT]
+        if drawn:
+            ds = slots[[k for k, _ in drawn]]
+            self.store.dev_valid[ds] = True
+            self.store.host_valid[ds] = False
+            iv = self.ctx.hist_append(POP_X, ds, n)
+            gen = self.ctx.hist_generation() if hasattr(self.ctx, "hist_generation") else 0
+            for j, (_k, d) in enumerate(drawn):
+                list.__setitem__(d[1]._ph, d[3], (HREF, d[4], gen, iv + j, n))
+        for d in draws[good:]:
+            if d[0] == "unit":
+                d[1]._host_draw(d[2], d[3])
+            else:
+                v_pert = (np.random.rand(d[1]) - 0.5 + 1j * (np.random.rand(d[1]) - 0.5)) * d[2]
+                if not np.linalg.norm(d[3] + v_pert) > 1e-9:
+                    np.random.rand(d[1]); np.random.rand(d[1])                      # AMS:546's second pair
 
     def end_deferred_push(self) -> None:
         """One pop_put per population array for the candidates constructed since begin_deferred_push (the spawns of
-        AMS:533-549: up to 15 per loop body, one 22 us call each before)."""
+        AMS:533-549: up to 15 per loop body, one 22 us call each before).  Under vector_draws='device' the candidates that
+        registered a draw get their rows from one maus_pop_draw first (_run_draws)."""
+        draws, self._draws = self._draws, None
+        if draws:
+            self._run_draws(draws)
         cands, self._deferred = self._deferred, None
         if not cands:
             return

@@ -32,7 +32,7 @@ from . import _cabi
 from ._cabi import POP_U, POP_X
 from .band import DIRECT_METHOD, band_bytes_per_solve, band_order, split_bytes_per_solve
 from .candstore import C_NP as _C_NP, C_PY as _C_PY, EXACT as _EXACT, F_NP as _F_NP, F_PY as _F_PY, HREF as _HREF, MISSING as _MISSING
-from .engine import DIRECT, GMRES, DeviceEngine, _advance_numpy_stream, few_rows_mode, sparse_direct_mode, sparse_eigsh_mode, sparse_gmres_mode, sparse_split_mode, sparse_spmm_mode
+from .engine import DIRECT, GMRES, DeviceEngine, _advance_numpy_stream, few_rows_mode, vector_draws_mode, sparse_direct_mode, sparse_eigsh_mode, sparse_gmres_mode, sparse_split_mode, sparse_spmm_mode
 
 
 class ProblemType(Enum):                     # AMS:10-13
@@ -733,6 +733,21 @@ class SolutionCandidate:
             w = rand_vec_init(v.shape[0])
             return w / np.linalg.norm(rand_vec_init(v.shape[0]))
 
+        eng = self._engine
+        if getattr(eng, "_draws", None) is not None and eng.defers_draw(self.N_diag, self.problem_type == ProblemType.SVD):
+            # vector_draws='device': the vector is the next pair of draws of the stream by number; its row is written by
+            # the one maus_pop_draw at the end of the bracket (engine._run_draws).  Python's `random` is consumed as ever.
+            if self.problem_type == ProblemType.EIGENVALUE:
+                self.lambda_k = (random.random() * 5 - 2.5 + 1j * (random.random() * 5 - 2.5))
+                scale, scalar = 1.0, self.lambda_k
+            else:
+                scale, scalar = random.uniform(0.1, 10.0), None
+            self._hv = None
+            self._host_valid = False                          # neither copy exists before the bracket ends
+            self._dev_valid = False
+            eng.register_draw(self, scale, scalar)
+            self.residual_history.append(self.residual_k)
+            return
         if self.problem_type == ProblemType.EIGENVALUE:
             self.v_k = norm_rand_vec(rand_vec_init(self.N_diag))
             self.lambda_k = (random.random() * 5 - 2.5 + 1j * (random.random() * 5 - 2.5))
@@ -745,6 +760,22 @@ class SolutionCandidate:
         self._push(force=True)
         self.param_history.append(self.get_current_solution_params())
         self.residual_history.append(self.residual_k)
+
+    def _host_draw(self, scale, ph_index):
+        """The host path of a draw that was registered for the device (engine._run_draws: a norm test the device norms did not
+        decide): the vector from the stream as it stands, its row uploaded, the placeholder of the first history entry
+        replaced."""
+        v = (np.random.rand(self.N_diag) + 1j * np.random.rand(self.N_diag)).astype(np.complex128)
+        if np.linalg.norm(v) > 1e-10:
+            v = v / np.linalg.norm(v)
+        else:
+            w = (np.random.rand(self.N_diag) + 1j * np.random.rand(self.N_diag)).astype(np.complex128)
+            v = w / np.linalg.norm((np.random.rand(self.N_diag) + 1j * np.random.rand(self.N_diag)).astype(np.complex128))
+        self._hv = v if self.problem_type == ProblemType.EIGENVALUE else v * scale
+        self._host_valid = True
+        self._dev_valid = False
+        self._push(force=True)
+        list.__setitem__(self._ph, ph_index, self.get_current_solution_params())
 
     def _record_history(self):
         """AMS:303-304 for a candidate whose vectors are recorded from the host mirrors (n <= 512; the engine refreshed them
@@ -784,8 +815,10 @@ class MAUS_Solver:
                  global_convergence_tol=1e-8, *, device=0, pert_mode="auto", gmres_compat="rtol",
                  record_history=None, comm=None, quiet=False, engine=None, gram_min=8, cond_exact_max=1024,
                  diag_info=None, eigh_mode="auto", sparse_mode=None, sparse_direct=None, sparse_eigsh=None,
-                 sparse_hermitian_check=None, sparse_gmres=None, few_rows=None, sparse_spmm=None, sparse_split=None):
+                 sparse_hermitian_check=None, sparse_gmres=None, few_rows=None, sparse_spmm=None, sparse_split=None,
+                 vector_draws=None):
         few_rows = few_rows_mode(few_rows)
+        vector_draws = vector_draws_mode(vector_draws)
         sparse_split = sparse_split_mode(sparse_split)
         sparse_spmm = sparse_spmm_mode(sparse_spmm)
         sparse_mode = _sparse_mode(sparse_mode)
@@ -817,7 +850,7 @@ class MAUS_Solver:
                                                                      sparse_mode=sparse_mode, sparse_direct=sparse_direct,
                                                                      sparse_eigsh=sparse_eigsh, sparse_gmres=sparse_gmres,
                                                                      few_rows=few_rows, sparse_spmm=sparse_spmm,
-                                                                     sparse_split=sparse_split)
+                                                                     sparse_split=sparse_split, vector_draws=vector_draws)
         # `diag_info`: start-up diagnostics of the same matrix taken from an earlier solver (bench side runs)
         if diag_info is not None:
             self.diag_info = dict(diag_info)
@@ -888,7 +921,15 @@ class MAUS_Solver:
         if self.problem_type == ProblemType.SVD:
             initial_num_candidates = max(initial_num_candidates, min(self.N_rows, self.N_cols) * 3)
         self.engine.ctx.pop_reserve(initial_num_candidates + 64)
-        self.candidates = [self._new_candidate() for _ in range(initial_num_candidates)]
+        if getattr(self.engine, "vector_draws", "host") == "device":
+            # the initial population's vectors come from one device draw like the spawns' (engine.end_deferred_push)
+            self.engine.begin_deferred_push()
+            try:
+                self.candidates = [self._new_candidate() for _ in range(initial_num_candidates)]
+            finally:
+                self.engine.end_deferred_push()
+        else:
+            self.candidates = [self._new_candidate() for _ in range(initial_num_candidates)]
         SolutionCandidate._candidate_id_counter = initial_num_candidates              # AMS:368
         if not quiet:
             print(f"MAUS Initialized with {initial_num_candidates} candidates for {self.problem_type.name} "
@@ -902,6 +943,16 @@ class MAUS_Solver:
         self.converged_solutions = []
         self.true_solution = None
         self.candidate_steps = 0
+
+    def _base_norm(self, sol):
+        """||v|| of a stored converged solution (lambda, v), computed once per stored tuple."""
+        cache = self.__dict__.setdefault("_base_norms", {})
+        hit = cache.get(id(sol))
+        if hit is None or hit[0] is not sol:
+            if len(cache) > 4096:
+                cache.clear()
+            hit = cache[id(sol)] = (sol, float(np.linalg.norm(sol[1])))
+        return hit[1]
 
     def _new_candidate(self, **kw):
         return SolutionCandidate(self.M, self.problem_type, self.N_diag, engine=self.engine,
@@ -1334,11 +1385,17 @@ class MAUS_Solver:
                         continue
                     if self.problem_type == ProblemType.EIGENVALUE:
                         kw["initial_lambda"] = base_sol_tuple[0] + (random.random() * 0.1 - 0.05 + 1j * (random.random() * 0.1 - 0.05)) * (0.1 + self.landscape_energy)
-                        v_pert = (np.random.rand(self.N_diag) - 0.5 + 1j * (np.random.rand(self.N_diag) - 0.5)) * (0.1 + self.landscape_energy)
-                        new_v = base_sol_tuple[1] + v_pert
-                        norm_new_v = np.linalg.norm(new_v)
-                        kw["initial_v"] = new_v / norm_new_v if norm_new_v > 1e-9 else \
-                            (np.random.rand(self.N_diag) + 1j * np.random.rand(self.N_diag)) / np.sqrt(self.N_diag)
+                        if getattr(self.engine, "_draws", None) is not None and self.engine.defers_draw(self.N_diag):
+                            # vector_draws='device': v_pert is used in the norm test below only (__init__ overwrites the
+                            # vector, AMS:127), so the pair is taken by number and the test decided from its device norm
+                            self.engine.register_norm_draw(self.N_diag, 0.1 + self.landscape_energy, base_sol_tuple[1],
+                                                           self._base_norm(base_sol_tuple))
+                        else:
+                            v_pert = (np.random.rand(self.N_diag) - 0.5 + 1j * (np.random.rand(self.N_diag) - 0.5)) * (0.1 + self.landscape_energy)
+                            new_v = base_sol_tuple[1] + v_pert
+                            norm_new_v = np.linalg.norm(new_v)
+                            kw["initial_v"] = new_v / norm_new_v if norm_new_v > 1e-9 else \
+                                (np.random.rand(self.N_diag) + 1j * np.random.rand(self.N_diag)) / np.sqrt(self.N_diag)
                 new_candidate = self._new_candidate(**kw, initial_weight=0.01)
                 new_candidate.alpha_local_step = GLOBAL_DEFAULT_ALPHA_V_INITIAL * (1 + self.strat_params["overall_psi_aggression_factor"] / 10.0)
                 self.candidates.append(new_candidate)

@@ -566,6 +566,34 @@ int maus_sync(maus_ctx* ctx);
  * materialising them (GF(2) jump polynomial; cached per nwords). */
 int maus_mt19937_jump(uint32_t* key624, int32_t* pos, uint64_t nwords);
 
+/* ---- candidate vectors drawn on the device from the NumPy stream (AMS:129-143, 544) ------------------------------
+ * A new candidate's vector is normalise(np.random.rand(N) + 1j*np.random.rand(N)): two consecutive rand(N) draws, 4N words of
+ * the legacy stream.  maus_pop_draw regenerates `count` such pairs on the device, bit for bit, from the state in `desc`
+ * (desc->ordinals[k] = index of pair k in the stream counted from that state, need not be contiguous;
+ * desc->words_per_candidate = 4*len, desc->lead_words = 0) and writes them into rows slots[k] of population array `which`.
+ * The caller advances its own stream (maus_mt19937_jump by 4*len words per pair consumed).
+ *   kinds[k]  MAUS_DRAW_RAW:  row = U1 + i U2, norm_out[k] = its 2-norm.
+ *             MAUS_DRAW_UNIT: row = ((U1 + i U2) * (1 / norm)) * scale[k] component by component (NumPy's v / np.linalg.norm(v)
+ *                             multiplies by the reciprocal); norm_out[k] = the norm before scaling.
+ *             MAUS_DRAW_NORM: nothing is written and slots[k] is ignored; norm_out[k] = ||((U1 - .5) + i (U2 - .5)) * scale[k]||.
+ *   scale     NULL: 1.0 for every draw.   substreams  0: the library's rule; 1..64 forces the sub-stream count (tests, timing).
+ * A row's bits and norm_out depend on the state, the ordinal, the kind and the scale only: not on the sub-stream count, the
+ * other draws of the call or the slot.  The squared norm is summed in chunks of 4992 elements in a fixed order, so it agrees
+ * with NumPy's to rounding ((len + 2) 2^-53 relative), not bit for bit.  Elements of the row past `len` and all other rows
+ * are untouched; the kept-product stamps are dropped.  len from maus_pop_draw_min_len() (1024) to maus_sparse_max_n(), at
+ * most the population's row length; a shorter or longer len is an error.
+ * maus_pop_draw_plan: the generator plan of such a call without a context or a device: S sub-streams of E elements per draw,
+ * ngen = 2 * count * S generators, generator (k, sb, part) at index (k * S + sb) * 2 + part (part 0 = U1, 1 = U2) starts at
+ * stream word 624 * ((2 * ordinals[k] + part) * dj + sb * dj2 + extra) + rpos counted from word 0 of the state's block;
+ * extra_out / rpos_out (either may be NULL) are filled when ngen <= cap.  -1 for bad arguments. */
+enum { MAUS_DRAW_RAW = 0, MAUS_DRAW_UNIT = 1, MAUS_DRAW_NORM = 2 };
+#define MAUS_POP_DRAW_MIN_LEN 1024
+int maus_pop_draw_min_len(void);
+int maus_pop_draw(maus_ctx* ctx, int which, int len, int count, const int32_t* slots, const int32_t* kinds, const double* scale,
+                  const maus_mt_desc* desc, int substreams /* 0 = the rule */, double* norm_out);
+int maus_pop_draw_plan(int len, int count, const int32_t* ordinals, int pos, int substreams, int* s_out, int64_t* e_out,
+                       int* ngen_out, int64_t* dj_out, int64_t* dj2_out, int32_t* extra_out, int32_t* rpos_out, int cap);
+
 #ifdef __cplusplus
 }
 #endif
