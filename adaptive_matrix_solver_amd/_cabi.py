@@ -28,6 +28,7 @@ SYMBOLS = [
     "maus_band_set_method", "maus_band_get_method", "maus_band_kernel_for", "maus_band_outer_nb", "maus_band_plan",
     "maus_band_set_split", "maus_band_get_split", "maus_band_split_plan",
     "maus_gmres_set_method", "maus_gmres_get_method", "maus_gmres_kernel_for",
+    "maus_real_set_method", "maus_real_get_method", "maus_real_plan", "maus_real_spmm", "maus_real_values_flagged",
     "maus_few_rows_set_method", "maus_few_rows_get_method", "maus_few_rows_kernel_for", "maus_few_rows_plan", "maus_few_rows_workspace_allocs",
     "maus_zgemm_plan",
     "maus_pop_draw", "maus_pop_draw_plan", "maus_pop_draw_min_len",
@@ -47,6 +48,10 @@ KC_BAND_SPLIT = len(KC_NAMES)      # band solves by the split method (maus_band_
 BAND_COLUMN, BAND_BLOCKED, BAND_TILED, BAND_WIDE, BAND_NARROW = (      # maus_band_set_method: 0, 1, 2, 4, 8 (no 3, 5, 6, 7)
     DIRECT_METHOD[m] for m in ("band", "blocked", "tiled", "wide", "narrow"))
 GMRES_DEFAULT, GMRES_WIDE = 0, 1                     # maus_gmres_set_method
+REAL_OFF, REAL_ON = 0, 1                             # maus_real_set_method
+# maus_real_plan: why a call runs complex (the first condition of the rule that fails), or REAL_OK
+REAL_OK, REAL_METHOD_OFF, REAL_NOT_CSR, REAL_MATRIX_COMPLEX, REAL_RHS_ROWS, REAL_RHS_COMPLEX, REAL_SHIFT_COMPLEX = range(7)
+KC_GMRES_REAL, KC_SPMM_REAL = 19, 20                 # the real path's post step and products: read as "gmres_real" / "spmm_real", behind the named classes
 FEW_ROWS_DEFAULT, FEW_ROWS_SPLITK = 0, 1             # maus_few_rows_set_method
 ZGEMM_ROWS, ZGEMM_LU = 0, 1                          # maus_zgemm_plan: the form ...
 LU_TILE_DEFAULT, LU_TILE_64X64, LU_TILE_128X64 = 0, 1, 2   # ... what MAUS_LU_TILE selects ...
@@ -157,6 +162,11 @@ def load_library():
         "maus_gmres_set_method": ([vp, C.c_int], C.c_int),
         "maus_gmres_get_method": ([vp], C.c_int),
         "maus_gmres_kernel_for": ([vp, C.c_int, C.c_int], C.c_int),
+        "maus_real_set_method": ([vp, C.c_int], C.c_int),
+        "maus_real_get_method": ([vp], C.c_int),
+        "maus_real_plan": ([vp, C.c_int, C.c_int, vp, vp], C.c_int),
+        "maus_real_spmm": ([vp, vp, C.c_int], C.c_int),
+        "maus_real_values_flagged": ([vp, C.c_int64], C.c_int),
         "maus_few_rows_set_method": ([vp, C.c_int, C.c_int], C.c_int),
         "maus_few_rows_get_method": ([vp], C.c_int),
         "maus_few_rows_kernel_for": ([vp] + [C.c_int] * 6 + [C.POINTER(C.c_int)], C.c_int),
@@ -281,6 +291,8 @@ class Context:
     def profile_read(self):
         prof = {name: self.profile_read_class(k) for k, name in enumerate(KC_NAMES)}
         prof["band_split"] = self.profile_read_class(KC_BAND_SPLIT)
+        prof["gmres_real"] = self.profile_read_class(KC_GMRES_REAL)
+        prof["spmm_real"] = self.profile_read_class(KC_SPMM_REAL)
         return prof
 
     def lu_workspace_allocations(self) -> int:
@@ -755,6 +767,31 @@ class Context:
         self._ck(min(k, 0), "maus_gmres_kernel_for")
         return int(k)
 
+    def real_set_method(self, method):
+        """Real arithmetic for gmres() on a real sparse system: REAL_OFF, or REAL_ON (a call whose CSR operand, b and shifts all
+        have imaginary parts of +-0 runs on rows of doubles with real copies of the operand, the diagonal and b; the complex
+        path's bits; csrc/gmres.hip).  Every other call runs complex as ever.  Kept across matrices."""
+        self._ck(self.lib.maus_real_set_method(self.h, int(method)), "maus_real_set_method")
+
+    def real_method(self) -> int:
+        return int(self.lib.maus_real_get_method(self.h))
+
+    def real_plan(self, rhs_mode, shift) -> dict:
+        """What a gmres() call with this rhs_mode and these shifts does on the bound matrix and b (maus_real_plan, the function
+        gmres() itself decides by): 'real' (bool), 'why' (REAL_OK or the first condition of the rule that fails), 'post' (0
+        register kernel, 1 stream kernel, 2 wide step; -1 without a square CSR matrix), 'spmm' (SPMM_KERNEL_*), 'allocs' (real
+        copies allocated on this context so far) and 'bytes' (of the real copies held now)."""
+        sh = _c128(np.atleast_1d(np.asarray(shift, dtype=np.complex128)))
+        out = np.zeros(6, dtype=np.int64)
+        self._ck(self.lib.maus_real_plan(self.h, int(rhs_mode), int(sh.shape[0]), _ptr(sh), _ptr(out)), "maus_real_plan")
+        return {"real": bool(out[0]), "why": int(out[1]), "post": int(out[2]), "spmm": int(out[3]), "allocs": int(out[4]),
+                "bytes": int(out[5])}
+
+    def real_spmm(self, slots):
+        """Y[slot] = A Re(X[slot]) by the SpMM kernels of the real path, imaginary part +0.0 (maus_real_spmm)."""
+        s = self._slots(slots)
+        self._ck(self.lib.maus_real_spmm(self.h, _ptr(s), s.shape[0]), "maus_real_spmm")
+
     def few_rows_set_method(self, method, slices=0):
         """Dense population products of at most 32 rows (A X, A^H u, conj(X) V, Gram blocks): FEW_ROWS_DEFAULT, or FEW_ROWS_SPLITK
         (K cut into slices over the whole device, joined in a fixed order; csrc/zgemm.hip).  `slices` 0: the library's rule;
@@ -957,6 +994,16 @@ def pop_draw_plan(length, ordinals, pos, substreams=0):
 
 def pop_draw_min_len() -> int:
     return int(load_library().maus_pop_draw_min_len())
+
+
+def real_values_flagged(values) -> bool:
+    """Whether the real path's rule counts these complex values as real: every imaginary part +0.0 or -0.0 in its bits
+    (maus_real_values_flagged).  Needs neither a context nor a device."""
+    v = _c128(np.ravel(np.asarray(values, dtype=np.complex128)))
+    r = load_library().maus_real_values_flagged(_ptr(v), int(v.shape[0]))
+    if r < 0:
+        raise MausHipError("maus_real_values_flagged: bad arguments")
+    return bool(r)
 
 
 def spmm_plan(method, fill_cap_percent, rows, nnz, padded) -> int:

@@ -267,6 +267,8 @@ int maus_ctx_destroy(maus_ctx* c) {
     maus_band_drop(c);
     maus_lanczos_drop(c);
     if (c->Adiag) (void)hipFree(c->Adiag);
+    if (c->Adiag_r) (void)hipFree(c->Adiag_r);
+    if (c->b_r) (void)hipFree(c->b_r);
     if (c->pin) (void)hipHostFree(c->pin);
     if (c->pin_small) (void)hipHostFree(c->pin_small);
     for (auto e : c->pin_small_ev) if (e) (void)hipEventDestroy(e);
@@ -323,7 +325,8 @@ static void csr_drop(maus_ctx* c) {
     maus_band_drop(c);
     maus_lanczos_drop(c);
     if (c->Adiag) { (void)hipFree(c->Adiag); c->Adiag = nullptr; }
-    c->csr = false; c->csr_sched = 0;
+    if (c->Adiag_r) { (void)hipFree(c->Adiag_r); c->Adiag_r = nullptr; }     // the real copies of the values go with the operands
+    c->csr = false; c->csr_sched = 0; c->A_real = false;
 }
 
 int maus_matrix_reserve(maus_ctx* c, int rows, int cols) {
@@ -373,7 +376,9 @@ int maus_set_rhs(maus_ctx* c, const double* b, int n) {
     if (!b || n <= 0) FAIL(c, "maus_set_rhs: bad arguments");
     HIPCHK(c, hipStreamSynchronize(c->st));
     if (n != c->bn) { if (c->b) (void)hipFree(c->b); c->b = nullptr; HIPCHK(c, hipMalloc((void**)&c->b, sizeof(c128) * n)); c->bn = n; }
-    return maus_stage_h2d(c, c->b, b, sizeof(c128) * n, c->st);
+    if (maus_stage_h2d(c, c->b, b, sizeof(c128) * n, c->st)) return -1;
+    c->b_real = maus_real_flagged(b, (size_t)n);
+    return maus_real_sync_rhs(c);
 }
 
 int maus_set_eigvecs(maus_ctx* c, const double* v, int n) {
@@ -1254,6 +1259,8 @@ int maus_gmres(maus_ctx* c, const int* slots, int count, const double* shift, co
     // Candidates never share arithmetic (per-row SpMM; a post step whose sums are a candidate's own, whether one workgroup per
     // candidate or, under maus_gmres_set_method(ctx, 1), the wide step with its per-candidate partial sums, which the rule
     // counts), so the chunking changes no result.
+    // real or complex: one decision for the whole call (maus_real_rule), also where the call then runs in chunks
+    const bool real = c && shift && count > 0 && maus_real_rule(c, rhs_mode, count, shift) == MAUS_REAL_OK;
     if (c && c->csr && c->rows > maus_lu_max_n() && count > 1 && slots && shift && psi && use_jacobi && info_out && inner_out && status) {
         size_t fr = 0, tot = 0;
         HIPCHK(c, hipMemGetInfo(&fr, &tot));
@@ -1264,13 +1271,13 @@ int maus_gmres(maus_ctx* c, const int* slots, int count, const double* shift, co
             for (int off = 0; off < count; off += chunk) {
                 const int g = std::min(chunk, count - off);
                 if (maus_gmres_run(c, slots + off, g, shift + 2 * (size_t)off, psi + off, rhs_mode, use_jacobi + off, rtol, restart, maxiter,
-                                   info_out + off, inner_out + off, status + off, nullptr, 0, 0, nullptr)) return -1;
+                                   info_out + off, inner_out + off, status + off, nullptr, 0, 0, nullptr, real)) return -1;
             }
             return 0;
         }
     }
     return maus_gmres_run(c, slots, count, shift, psi, rhs_mode, use_jacobi, rtol, restart, maxiter, info_out, inner_out, status,
-                          nullptr, 0, 0, nullptr);
+                          nullptr, 0, 0, nullptr, real);
 }
 
 int maus_gmres_pert(maus_ctx* c, const int* slots, int count, const double* shift, const double* psi, int rhs_mode,

@@ -28,6 +28,14 @@ __device__ __forceinline__ void cfma_conj(c128& a, c128 b, c128 c) {
     a.x = fma(b.x, c.x, a.x); a.x = fma(b.y, c.y, a.x);
     a.y = fma(b.x, c.y, a.y); a.y = fma(-b.y, c.x, a.y);
 }
+// The same three on real operands: what the complex ones compute when every imaginary part is an exact zero -- each dropped
+// fma adds a product of zeros to the real part and leaves it as it is (the real path of spmm.hip and gmres.hip)
+__device__ __forceinline__ void cfms(double& a, double b, double c) { a = fma(-b, c, a); }
+__device__ __forceinline__ void cfma(double& a, double b, double c) { a = fma(b, c, a); }
+__device__ __forceinline__ void cfma_conj(double& a, double b, double c) { a = fma(b, c, a); }
+template <class T> __device__ __forceinline__ T czero();
+template <> __device__ __forceinline__ c128 czero<c128>() { return cmake(0.0, 0.0); }
+template <> __device__ __forceinline__ double czero<double>() { return 0.0; }
 // LAPACK dcabs1: |re| + |im|  (izamax pivot rule)
 __device__ __forceinline__ double cabs1(c128 a) { return fabs(a.x) + fabs(a.y); }
 // 1/z by Smith's algorithm (no intermediate overflow for representable results)
@@ -109,4 +117,4 @@ static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 // kernel classes for the profiling counters (maus_profile_read)
 enum { KC_GEMM = 0, KC_PANEL = 1, KC_TRSM = 2, KC_LASWP = 3, KC_BUILD = 4, KC_BACKSOLVE = 5, KC_VEC = 6,
-       KC_GEMM_K128 = 7, KC_GEMM_K64 = 8, KC_GEMM_K32 = 9, KC_GEMM_K16 = 10, KC_SPMM = 11, KC_BAND = 12, KC_LANCZOS = 13, KC_BAND_BLOCKED = 14, KC_BAND_TILED = 15, KC_BAND_WIDE = 16, KC_GMRES_WIDE = 17, KC_BAND_SPLIT = 18, KC_COUNT = 19 };   // 7..10: LU recursion GEMMs by K (<256); 11: CSR products (spmm.hip); 12: band solves (band.hip); 13: Lanczos reorthogonalisation, restart and match (lanczos.hip); 14: band solves by the blocked method (band.hip); 15: band solves by the tiled method (band.hip); 16: band solves by the wide method (band.hip); 17: the wide GMRES post step (gmres.hip); 18: band solves by the split method (band.hip)
+       KC_GEMM_K128 = 7, KC_GEMM_K64 = 8, KC_GEMM_K32 = 9, KC_GEMM_K16 = 10, KC_SPMM = 11, KC_BAND = 12, KC_LANCZOS = 13, KC_BAND_BLOCKED = 14, KC_BAND_TILED = 15, KC_BAND_WIDE = 16, KC_GMRES_WIDE = 17, KC_BAND_SPLIT = 18, KC_GMRES_REAL = 19, KC_SPMM_REAL = 20, KC_COUNT = 21 };   // 7..10: LU recursion GEMMs by K (<256); 11: CSR products (spmm.hip); 12: band solves (band.hip); 13: Lanczos reorthogonalisation, restart and match (lanczos.hip); 14: band solves by the blocked method (band.hip); 15: band solves by the tiled method (band.hip); 16: band solves by the wide method (band.hip); 17: the wide GMRES post step (gmres.hip); 18: band solves by the split method (band.hip); 19: the GMRES post step of the real path, any schedule (gmres.hip); 20: CSR products of the real path (spmm.hip)

@@ -46,13 +46,23 @@ void maus_spmm_launch(hipStream_t st, const MausCsr& m, int sched, const c128* B
 // operand bytes of one pass over a sparse operand, for the profiling counters: the sliced-ELL copy streams 20 bytes per padded
 // slot where it is resident; the CSR kernels are accounted as ever
 inline double maus_spmm_operand_bytes(const MausCsr& m) { return m.sell.val ? 20.0 * m.sell.padded : 12.0 * m.nnz; }
+void maus_spmm_launch_real(hipStream_t st, const MausCsr& m, int sched, const double* B, long ldb, double* C, long ldc,
+                           const int* a_rows, const int* c_rows, int count);
+inline double maus_spmm_operand_bytes_real(const MausCsr& m) { return m.sell.val ? 12.0 * m.sell.padded : 12.0 * m.nnz; }   // 8 B value + 4 B index per slot or nonzero, the row pointers as ever
 void maus_csr_diag_launch(hipStream_t st, const MausCsr& m, int n, c128* d);
+// The real copies of the real path (spmm.hip): brought in line with the method, the flags and what is bound -- built where the
+// rule can hold, freed where it cannot.  Called wherever one of the three changes.
+int maus_real_sync_matrix(maus_ctx* c);
+int maus_real_sync_rhs(maus_ctx* c);
+bool maus_real_flagged(const double* values_c128, size_t count);      // every imaginary part has the bits of +0 or -0
+// The rule of the real path, stated once (gmres.hip): MAUS_REAL_OK or the first condition that fails
+int maus_real_rule(const maus_ctx* c, int rhs_mode, int count, const double* shift_c128);
 void maus_csr_free(MausCsr& m);
 void maus_build_h_csr(const LuWs& w, const MausCsr& A, const c128* d_shift, const double* d_psi, int rhs_mode,
                       const c128* X, long ldx, const int* d_slots, const c128* bvec, int tiled);
 int maus_gmres_run(maus_ctx* ctx, const int* slots, int count, const double* shift, const double* psi, int rhs_mode,
                    const int32_t* use_jacobi, double rtol, int restart, int maxiter, int32_t* info_out, int32_t* inner_out, int32_t* status,
-                   const c128* Hdense, long ldh, long strideH, int32_t* jacobi_out);
+                   const c128* Hdense, long ldh, long strideH, int32_t* jacobi_out, bool real = false);
 void maus_band_drop(maus_ctx* c);            // band.hip: the ordering and workspace of the previous sparse matrix
 void maus_lanczos_drop(maus_ctx* c);         // lanczos.hip: the basis and the Ritz rows of the previous sparse matrix
 size_t maus_gmres_wide_bytes_per_candidate(int n);   // gmres.hip: what the wide step adds to a candidate's scratch
@@ -92,6 +102,11 @@ struct maus_ctx {
     // dense population products of at most 32 rows (zgemm.hip, maus_few_rows_set_method): 0 the default kernels, 1 split-K with
     // `few_slices` slices (0: the rule); the partial-sum slabs, grown on demand and never shrunk; kept across matrices
     int few_method = 0, few_slices = 0; c128* few_ws = nullptr; size_t few_ws_elems = 0; int few_allocs = 0;
+    // real path of maus_gmres (maus_real_set_method; the rule: maus_real_rule): the method, kept across matrices; whether every
+    // stored value of the CSR matrix / of b has an imaginary part of +-0 (set on the host when they are bound); the real copies
+    // (Acsr.rval, Acsr.sell.rval, Adiag_r, b_r), which exist only under method 1 for flagged data; how often one was allocated
+    int real_method = 0; bool A_real = false, b_real = false;
+    double* Adiag_r = nullptr; double* b_r = nullptr; int b_rn = 0; int real_allocs = 0;
     c128* b = nullptr; int bn = 0;                  // rhs
     c128* V = nullptr; int vn = 0;                  // eigenvectors (Hermitian shortcut)
     c128* hq = nullptr; c128* htau = nullptr; int hqn = 0;   // Householder reflectors of maus_herm_tridiag, until the back-transformation (herm.hip)

@@ -28,6 +28,11 @@
 // one-lane Arnoldi tail (arnoldi_tail).  Their reductions are NOT shared: blk_sum and gw_block_sum / gw_join add in different
 // orders, and each schedule's bits are those of its own order.  The vector bodies of the register and the streamed kernel are
 // two texts on purpose (profiles/gmres_share.txt, section 5).
+//
+// Every kernel that touches a candidate's vectors is one text over their scalar type T: c128, or double on the real path
+// (maus_real_set_method(ctx, 1)), which a maus_gmres call takes when maus_real_rule holds for it -- a CSR-bound matrix, the
+// bound right-hand side and every shift of the call with imaginary parts of exactly +-0.  See "the scalar type T" below for
+// why the two instantiations return the same bits, and for what differs on non-finite data.
 #include "ctx.h"
 #include <algorithm>
 #include <cstring>
@@ -80,6 +85,47 @@ __device__ __forceinline__ c128 cdiv_np(c128 a, c128 b) {
     const double rat = b.x / b.y, scl = 1.0 / (b.y + b.x * rat);
     return cmake((a.x * rat + a.y) * scl, (a.y * rat - a.x) * scl);
 }
+
+// ---- the scalar type T of a solve's vectors: c128, or double on the real path (maus_real_set_method) ----
+// The real path runs where the operand, b and every shift of the call have imaginary parts of exactly +-0; then so has every
+// Krylov vector, every Hessenberg entry and the iterate of the complex solve.  Its kernels are the instantiation T = double of
+// the texts below: rows of n doubles, and every vector operation the complex one with the terms that multiply an exact zero
+// left out -- each of those adds +-0 to a sum and leaves it as it is -- in the same thread, the same order and through the same
+// joins.  The helpers here state each such pair once.  Products and differences on the real side are single roundings by
+// intrinsic, so that no contraction can fuse what the complex text rounds twice.  The one-lane state machine (zlartg,
+// resid_decide, arnoldi_tail, GState) is NOT instantiated twice: both paths run the complex text on Hessenberg entries whose
+// imaginary part is zero, so its decisions and rotations are the complex path's by construction (Smith's division by a real
+// number is a multiplication by a reciprocal, which a real division would not reproduce).
+// Non-finite data: 0 * Inf = NaN reaches the real part only through the terms left out, so the real path can hold Inf where the
+// complex one holds NaN; what is finite or not, and with it info and status, is the same.
+template <class T> __device__ __forceinline__ T sc_of(c128 z);                       // a Hessenberg-side scalar as T
+template <> __device__ __forceinline__ c128 sc_of<c128>(c128 z) { return z; }
+template <> __device__ __forceinline__ double sc_of<double>(c128 z) { return z.x; }
+__device__ __forceinline__ c128 sc_c(c128 z) { return z; }                            // and back: imaginary part +0
+__device__ __forceinline__ c128 sc_c(double r) { return cmake(r, 0.0); }
+__device__ __forceinline__ void sc_abs2(double& s, c128 v) { s = fma(v.x, v.x, s); s = fma(v.y, v.y, s); }   // s += |v|^2
+__device__ __forceinline__ void sc_abs2(double& s, double v) { s = fma(v, v, s); }
+__device__ __forceinline__ c128 sc_scale(c128 v, double f) { return cmake(v.x * f, v.y * f); }
+__device__ __forceinline__ double sc_scale(double v, double f) { return __dmul_rn(v, f); }
+__device__ __forceinline__ c128 sc_sub(c128 a, c128 b) { return cmake(a.x - b.x, a.y - b.y); }
+__device__ __forceinline__ double sc_sub(double a, double b) { return __dsub_rn(a, b); }
+__device__ __forceinline__ c128 sc_add(c128 a, c128 b) { return cadd(a, b); }
+__device__ __forceinline__ double sc_add(double a, double b) { return __dadd_rn(a, b); }
+__device__ __forceinline__ bool sc_finite(c128 v) { return cfinite(v); }
+__device__ __forceinline__ bool sc_finite(double v) { return isfinite(v); }
+// psi - lambda, the shift behind the product
+template <class T> __device__ __forceinline__ T sc_shift(double psi, c128 lam);
+template <> __device__ __forceinline__ c128 sc_shift<c128>(double psi, c128 lam) { return cmake(psi - lam.x, -lam.y); }
+template <> __device__ __forceinline__ double sc_shift<double>(double psi, c128 lam) { return __dsub_rn(psi, lam.x); }
+// (1 / d) v, the Jacobi scale: crecip_np of a real d is 1 / d (1 / |d| for d = 0), its product with v one multiplication
+__device__ __forceinline__ c128 sc_jacobi(c128 d, c128 v) { return cmul(crecip_np(d), v); }
+__device__ __forceinline__ double sc_jacobi(double d, double v) { return __dmul_rn(d == 0.0 ? 1.0 / fabs(d) : 1.0 / d, v); }
+// blk_sum of a T: the real part, then the imaginary part
+template <int NT = GT> __device__ __forceinline__ c128 blk_sum_t(c128 v, double* sbuf) {
+    const double re = blk_sum<NT>(v.x, sbuf), im = blk_sum<NT>(v.y, sbuf);
+    return cmake(re, im);
+}
+template <int NT = GT> __device__ __forceinline__ double blk_sum_t(double v, double* sbuf) { return blk_sum<NT>(v, sbuf); }
 
 // LAPACK 3.10+ zlartg, safe-range branches:  [c s; -conj(s) c] [f; g] = [r; 0], c real
 // By value, every result component a scalar that is assigned once per branch, the call inlined: c, s and r stay in registers
@@ -186,6 +232,7 @@ __device__ __forceinline__ void arnoldi_tail(GState& s, c128* h, c128* y, int* e
 __device__ __forceinline__ c128 shifted_diag(c128 d, c128 lam, double ps) {
     return cmake(__dadd_rn(__dsub_rn(d.x, lam.x), ps), __dadd_rn(__dsub_rn(d.y, lam.y), 0.0));
 }
+__device__ __forceinline__ double shifted_diag(double d, c128 lam, double ps) { return __dadd_rn(__dsub_rn(d, lam.x), ps); }
 // AMS:67-72: a diagonal entry rules the Jacobi scale out unless 1/d is finite and |d| > 1e-12
 __device__ __forceinline__ bool jacobi_bad(c128 d) {
     const c128 inv = crecip_np(d);
@@ -215,22 +262,26 @@ jacobi_check_kernel(const c128* __restrict__ dA, int n, const c128* __restrict__
     if (threadIdx.x == 0) ok[g] = sbad ? 0 : 1;
 }
 
-struct GArgs {
+template <class T>
+struct GArgsT {
     int n, R, maxiter, rows_per;          // rows_per = R + 2 rows of the basis array per candidate
     double rtol;
-    const c128* dA; const c128* shift; const double* psi; const int* jac;
-    const c128* X; long ldx; const int* slots; const c128* bvec; int rhs_mode;
-    c128* Vb; c128* Y; GState* st;
-    const c128* Hd; long ldh, strideH;    // dense mode: materialised H_k (null in shared-matrix mode)
+    const T* dA; const c128* shift; const double* psi; const int* jac;
+    const T* X; long ldx; const int* slots; const T* bvec; int rhs_mode;     // T = double: rhs_mode 1 only (the rule), X null
+    T* Vb; T* Y; GState* st;
+    const T* Hd; long ldh, strideH;       // dense mode: materialised H_k (null in shared-matrix mode)
 };
+using GArgs = GArgsT<c128>;
 
-__device__ __forceinline__ const c128* rhs_of(const GArgs& a, int k) {
+template <class T>
+__device__ __forceinline__ const T* rhs_of(const GArgsT<T>& a, int k) {
     return a.rhs_mode == 0 ? a.X + (long)a.slots[k] * a.ldx : a.bvec;
 }
-__device__ __forceinline__ c128 psolve1(const GArgs& a, int k, int i, c128 v) {
+template <class T>
+__device__ __forceinline__ T psolve1(const GArgsT<T>& a, int k, int i, T v) {
     if (!a.jac[k]) return v;
-    const c128 d = a.Hd ? a.Hd[(long)k * a.strideH + (long)i * a.ldh + i] : shifted_diag(a.dA[i], a.shift[k], a.psi[k]);
-    return cmul(crecip_np(d), v);
+    const T d = a.Hd ? a.Hd[(long)k * a.strideH + (long)i * a.ldh + i] : shifted_diag(a.dA[i], a.shift[k], a.psi[k]);
+    return sc_jacobi(d, v);
 }
 
 // dense mode, AMS:65-86: Jacobi only where it was asked for AND every 1/diag(H_k) is finite and every |diag(H_k)| > 1e-12
@@ -277,19 +328,20 @@ gemv_dense_kernel(GArgs a, const int* __restrict__ act, const int* __restrict__ 
 }
 
 // x0 = b; norms; ptol (iterative.py:696-724)
+template <class T>
 __global__ void __launch_bounds__(GT)
-gmres_init_kernel(GArgs a) {
+gmres_init_kernel(GArgsT<T> a) {
     __shared__ double sbuf[GT / 64];
     const int k = blockIdx.x;
-    const c128* b = rhs_of(a, k);
-    c128* x = a.Vb + ((long)k * a.rows_per + a.R + 1) * a.n;
+    const T* b = rhs_of(a, k);
+    T* x = a.Vb + ((long)k * a.rows_per + a.R + 1) * a.n;
     double sb = 0.0, sm = 0.0;
     for (int i = threadIdx.x; i < a.n; i += GT) {
-        const c128 v = b[i];
+        const T v = b[i];
         x[i] = v;
-        sb = fma(v.x, v.x, sb); sb = fma(v.y, v.y, sb);
-        const c128 m = psolve1(a, k, i, v);
-        sm = fma(m.x, m.x, sm); sm = fma(m.y, m.y, sm);
+        sc_abs2(sb, v);
+        const T m = psolve1(a, k, i, v);
+        sc_abs2(sm, m);
     }
     sb = blk_sum(sb, sbuf); sm = blk_sum(sm, sbuf);
     if (threadIdx.x == 0) {
@@ -381,9 +433,9 @@ gmres_compact_kernel(const GState* __restrict__ st, int count, int rows_per, int
 
 // EPT entries of the candidate's vectors per thread of an NT-thread workgroup: 256 threads up to n = 8192, 512 threads (EPT 32,
 // the same 128 VGPRs of w) for 8192 < n <= 16384
-template <int EPT, int NT = GT>
+template <class T, int EPT, int NT = GT>
 __global__ void __launch_bounds__(NT)
-gmres_post_kernel(GArgs a, const int* __restrict__ act) {
+gmres_post_kernel(GArgsT<T> a, const int* __restrict__ act) {
     __shared__ double sbuf[NT / 64];
     __shared__ c128 s_h[MAXR + 2];
     __shared__ c128 s_y[MAXR + 1];
@@ -392,26 +444,26 @@ gmres_post_kernel(GArgs a, const int* __restrict__ act) {
     GState& s = a.st[k];
     const int n = a.n, R = a.R, tid = threadIdx.x;
     const int phase = s.phase, col = s.col;
-    c128* Vk = a.Vb + (long)k * a.rows_per * n;
-    c128* x = Vk + (long)(R + 1) * n;
-    const c128* y = a.Y + (long)k * n;
+    T* Vk = a.Vb + (long)k * a.rows_per * n;
+    T* x = Vk + (long)(R + 1) * n;
+    const T* y = a.Y + (long)k * n;
     const c128 lam = a.shift[k];
     // H z = A z + (psi - lambda) z ; in dense mode the shift is part of the materialised H_k
-    const c128 sh = a.Hd ? cmake(0.0, 0.0) : cmake(a.psi[k] - lam.x, -lam.y);
-    c128 w[EPT];
+    const T sh = a.Hd ? czero<T>() : sc_shift<T>(a.psi[k], lam);
+    T w[EPT];
 
     if (phase == 1) {
         // ---- r = b - H x ; exit tests ; start of the next restart cycle (iterative.py:737-748, 826-838) ----
-        const c128* b = rhs_of(a, k);
+        const T* b = rhs_of(a, k);
         double ss = 0.0;
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
             const int i = tid + e * NT;
             if (i < n) {
-                c128 hx = y[i]; cfma(hx, sh, x[i]);
-                const c128 r = cmake(b[i].x - hx.x, b[i].y - hx.y);
+                T hx = y[i]; cfma(hx, sh, x[i]);
+                const T r = sc_sub(b[i], hx);
                 w[e] = r;
-                ss = fma(r.x, r.x, ss); ss = fma(r.y, r.y, ss);
+                sc_abs2(ss, r);
             }
         }
         const double rnorm = sqrt(blk_sum<NT>(ss, sbuf));
@@ -426,14 +478,14 @@ gmres_post_kernel(GArgs a, const int* __restrict__ act) {
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
             const int i = tid + e * NT;
-            if (i < n) { w[e] = psolve1(a, k, i, w[e]); sv = fma(w[e].x, w[e].x, sv); sv = fma(w[e].y, w[e].y, sv); }
+            if (i < n) { w[e] = psolve1(a, k, i, w[e]); sc_abs2(sv, w[e]); }
         }
         const double tmp = sqrt(blk_sum<NT>(sv, sbuf));
         const double inv = 1.0 / tmp;
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
             const int i = tid + e * NT;
-            if (i < n) Vk[i] = cmake(w[e].x * inv, w[e].y * inv);
+            if (i < n) Vk[i] = sc_scale(w[e], inv);
         }
         if (tid == 0) {
             s.rnorm = rnorm; s.pmf = d.pmf; s.ptol = d.ptol; s.cycle = d.cycle; s.first = 0;
@@ -445,33 +497,28 @@ gmres_post_kernel(GArgs a, const int* __restrict__ act) {
     }
 
     // ---- Arnoldi step (iterative.py:751-800) ----
-    const c128* z = Vk + (long)col * n;
+    const T* z = Vk + (long)col * n;
     double ss = 0.0;
 #pragma unroll
     for (int e = 0; e < EPT; ++e) {
         const int i = tid + e * NT;
         if (i < n) {
-            c128 av = y[i]; cfma(av, sh, z[i]);
+            T av = y[i]; cfma(av, sh, z[i]);
             w[e] = psolve1(a, k, i, av);
-            ss = fma(w[e].x, w[e].x, ss); ss = fma(w[e].y, w[e].y, ss);
+            sc_abs2(ss, w[e]);
         }
     }
     const double h0 = sqrt(blk_sum<NT>(ss, sbuf));
     for (int kk = 0; kk <= col; ++kk) {                        // modified Gram-Schmidt
-        const c128* vk = Vk + (long)kk * n;
-        double tr = 0.0, ti = 0.0;
+        const T* vk = Vk + (long)kk * n;
+        T t = czero<T>();                                      // vdot(V[kk], w)
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
             const int i = tid + e * NT;
-            if (i < n) {
-                const c128 v = vk[i];
-                tr = fma(v.x, w[e].x, tr); tr = fma(v.y, w[e].y, tr);
-                ti = fma(v.x, w[e].y, ti); ti = fma(-v.y, w[e].x, ti);
-            }
+            if (i < n) cfma_conj(t, vk[i], w[e]);
         }
-        tr = blk_sum<NT>(tr, sbuf); ti = blk_sum<NT>(ti, sbuf);
-        const c128 t = cmake(tr, ti);
-        if (tid == 0) s_h[kk] = t;
+        t = blk_sum_t<NT>(t, sbuf);
+        if (tid == 0) s_h[kk] = sc_c(t);
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
             const int i = tid + e * NT;
@@ -482,17 +529,17 @@ gmres_post_kernel(GArgs a, const int* __restrict__ act) {
 #pragma unroll
     for (int e = 0; e < EPT; ++e) {
         const int i = tid + e * NT;
-        if (i < n) { ss = fma(w[e].x, w[e].x, ss); ss = fma(w[e].y, w[e].y, ss); }
+        if (i < n) { sc_abs2(ss, w[e]); }
     }
     const double h1 = sqrt(blk_sum<NT>(ss, sbuf));
     const bool brk = h1 <= EPS * h0;
     {
-        c128* vn = Vk + (long)(col + 1) * n;
+        T* vn = Vk + (long)(col + 1) * n;
         const double inv = brk ? 1.0 : 1.0 / h1;
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
             const int i = tid + e * NT;
-            if (i < n) vn[i] = cmake(w[e].x * inv, w[e].y * inv);
+            if (i < n) vn[i] = sc_scale(w[e], inv);
         }
     }
     if (tid == 0) arnoldi_tail(s, s_h, s_y, &s_flag[0], col, R, brk, h1);
@@ -502,8 +549,8 @@ gmres_post_kernel(GArgs a, const int* __restrict__ act) {
         for (int e = 0; e < EPT; ++e) {
             const int i = tid + e * NT;
             if (i < n) {
-                c128 acc = x[i];
-                for (int j = 0; j <= col; ++j) cfma(acc, s_y[j], Vk[(long)j * n + i]);
+                T acc = x[i];
+                for (int j = 0; j <= col; ++j) cfma(acc, sc_of<T>(s_y[j]), Vk[(long)j * n + i]);
                 x[i] = acc;
             }
         }
@@ -514,9 +561,9 @@ gmres_post_kernel(GArgs a, const int* __restrict__ act) {
 // becomes, V[col + 1] (the Arnoldi step) or V[0] (the residual of a new cycle); thread t owns the entries t, t + NT, ... of
 // every vector, as the register kernels do.  Same modified Gram-Schmidt order, state machine and exits; the variant is picked
 // from n alone.  The vector loops below are gmres_post_kernel's line for line but for where w lives.
-template <int NT>
+template <class T, int NT>
 __global__ void __launch_bounds__(NT)
-gmres_post_stream_kernel(GArgs a, const int* __restrict__ act) {
+gmres_post_stream_kernel(GArgsT<T> a, const int* __restrict__ act) {
     __shared__ double sbuf[NT / 64];
     __shared__ c128 s_h[MAXR + 2];
     __shared__ c128 s_y[MAXR + 1];
@@ -525,21 +572,21 @@ gmres_post_stream_kernel(GArgs a, const int* __restrict__ act) {
     GState& s = a.st[k];
     const int n = a.n, R = a.R, tid = threadIdx.x;
     const int phase = s.phase, col = s.col;
-    c128* Vk = a.Vb + (long)k * a.rows_per * n;
-    c128* x = Vk + (long)(R + 1) * n;
-    const c128* y = a.Y + (long)k * n;
+    T* Vk = a.Vb + (long)k * a.rows_per * n;
+    T* x = Vk + (long)(R + 1) * n;
+    const T* y = a.Y + (long)k * n;
     const c128 lam = a.shift[k];
-    const c128 sh = a.Hd ? cmake(0.0, 0.0) : cmake(a.psi[k] - lam.x, -lam.y);
+    const T sh = a.Hd ? czero<T>() : sc_shift<T>(a.psi[k], lam);
 
     if (phase == 1) {
-        const c128* b = rhs_of(a, k);
-        c128* w = Vk;
+        const T* b = rhs_of(a, k);
+        T* w = Vk;
         double ss = 0.0;
         for (int i = tid; i < n; i += NT) {
-            c128 hx = y[i]; cfma(hx, sh, x[i]);
-            const c128 r = cmake(b[i].x - hx.x, b[i].y - hx.y);
+            T hx = y[i]; cfma(hx, sh, x[i]);
+            const T r = sc_sub(b[i], hx);
             w[i] = r;
-            ss = fma(r.x, r.x, ss); ss = fma(r.y, r.y, ss);
+            sc_abs2(ss, r);
         }
         const double rnorm = sqrt(blk_sum<NT>(ss, sbuf));
         const Resid d = resid_decide(s, rnorm, a.maxiter);
@@ -550,13 +597,13 @@ gmres_post_stream_kernel(GArgs a, const int* __restrict__ act) {
         }
         double sv = 0.0;
         for (int i = tid; i < n; i += NT) {
-            const c128 v = psolve1(a, k, i, w[i]);
+            const T v = psolve1(a, k, i, w[i]);
             w[i] = v;
-            sv = fma(v.x, v.x, sv); sv = fma(v.y, v.y, sv);
+            sc_abs2(sv, v);
         }
         const double tmp = sqrt(blk_sum<NT>(sv, sbuf));
         const double inv = 1.0 / tmp;
-        for (int i = tid; i < n; i += NT) w[i] = cmake(w[i].x * inv, w[i].y * inv);
+        for (int i = tid; i < n; i += NT) w[i] = sc_scale(w[i], inv);
         if (tid == 0) {
             s.rnorm = rnorm; s.pmf = d.pmf; s.ptol = d.ptol; s.cycle = d.cycle; s.first = 0;
             for (int j = 0; j <= R; ++j) s.S[j] = cmake(0.0, 0.0);
@@ -566,43 +613,38 @@ gmres_post_stream_kernel(GArgs a, const int* __restrict__ act) {
         return;
     }
 
-    const c128* z = Vk + (long)col * n;
-    c128* w = Vk + (long)(col + 1) * n;
+    const T* z = Vk + (long)col * n;
+    T* w = Vk + (long)(col + 1) * n;
     double ss = 0.0;
     for (int i = tid; i < n; i += NT) {
-        c128 av = y[i]; cfma(av, sh, z[i]);
-        const c128 v = psolve1(a, k, i, av);
+        T av = y[i]; cfma(av, sh, z[i]);
+        const T v = psolve1(a, k, i, av);
         w[i] = v;
-        ss = fma(v.x, v.x, ss); ss = fma(v.y, v.y, ss);
+        sc_abs2(ss, v);
     }
     const double h0 = sqrt(blk_sum<NT>(ss, sbuf));
     for (int kk = 0; kk <= col; ++kk) {                        // modified Gram-Schmidt
-        const c128* vk = Vk + (long)kk * n;
-        double tr = 0.0, ti = 0.0;
-        for (int i = tid; i < n; i += NT) {
-            const c128 v = vk[i], wi = w[i];
-            tr = fma(v.x, wi.x, tr); tr = fma(v.y, wi.y, tr);
-            ti = fma(v.x, wi.y, ti); ti = fma(-v.y, wi.x, ti);
-        }
-        tr = blk_sum<NT>(tr, sbuf); ti = blk_sum<NT>(ti, sbuf);
-        const c128 t = cmake(tr, ti);
-        if (tid == 0) s_h[kk] = t;
-        for (int i = tid; i < n; i += NT) { c128 wi = w[i]; cfms(wi, t, vk[i]); w[i] = wi; }
+        const T* vk = Vk + (long)kk * n;
+        T t = czero<T>();                                      // vdot(V[kk], w)
+        for (int i = tid; i < n; i += NT) cfma_conj(t, vk[i], w[i]);
+        t = blk_sum_t<NT>(t, sbuf);
+        if (tid == 0) s_h[kk] = sc_c(t);
+        for (int i = tid; i < n; i += NT) { T wi = w[i]; cfms(wi, t, vk[i]); w[i] = wi; }
     }
     ss = 0.0;
-    for (int i = tid; i < n; i += NT) { const c128 wi = w[i]; ss = fma(wi.x, wi.x, ss); ss = fma(wi.y, wi.y, ss); }
+    for (int i = tid; i < n; i += NT) { const T wi = w[i]; sc_abs2(ss, wi); }
     const double h1 = sqrt(blk_sum<NT>(ss, sbuf));
     const bool brk = h1 <= EPS * h0;
     {
         const double inv = brk ? 1.0 : 1.0 / h1;
-        for (int i = tid; i < n; i += NT) w[i] = cmake(w[i].x * inv, w[i].y * inv);
+        for (int i = tid; i < n; i += NT) w[i] = sc_scale(w[i], inv);
     }
     if (tid == 0) arnoldi_tail(s, s_h, s_y, &s_flag[0], col, R, brk, h1);
     __syncthreads();
     if (s_flag[0]) {                                           // x += y @ V[:col+1]
         for (int i = tid; i < n; i += NT) {
-            c128 acc = x[i];
-            for (int j = 0; j <= col; ++j) cfma(acc, s_y[j], Vk[(long)j * n + i]);
+            T acc = x[i];
+            for (int j = 0; j <= col; ++j) cfma(acc, sc_of<T>(s_y[j]), Vk[(long)j * n + i]);
             x[i] = acc;
         }
     }
@@ -628,73 +670,87 @@ __device__ __forceinline__ c128 gw_block_sum(c128 v, c128* sbuf) {
     __syncthreads();
     return s;
 }
-__device__ __forceinline__ c128 gw_join(const c128* __restrict__ part, int np, c128* sbuf) {
-    c128 acc = cmake(0.0, 0.0);
-    for (int b = threadIdx.x; b < np; b += GW_BT) acc = cadd(acc, part[b]);
+// a sum of doubles: the real part of the same tree (the squared norms; every sum of the real path)
+__device__ __forceinline__ double gw_block_sum(double v, c128* sbuf) {
+    double* sb = (double*)sbuf;
+    const double re = wave_sum_dpp(v);
+    if ((threadIdx.x & 63) == 0) sb[threadIdx.x >> 6] = re;
+    __syncthreads();
+    const double s = (sb[0] + sb[1]) + (sb[2] + sb[3]);
+    __syncthreads();
+    return s;
+}
+template <class T>
+__device__ __forceinline__ T gw_join(const T* __restrict__ part, int np, c128* sbuf) {
+    T acc = czero<T>();
+    for (int b = threadIdx.x; b < np; b += GW_BT) acc = sc_add(acc, part[b]);
     return gw_block_sum(acc, sbuf);
 }
 
-struct WArgs {
-    WState* ws; c128* part0; c128* part1; c128* pn;     // part0 / part1: the dot products, alternating by column; pn: (|w|^2 before, after)
+template <class T>
+struct WArgsT {
+    WState* ws; T* part0; T* part1; c128* pn;     // part0 / part1: the dot products, alternating by column; pn: the pair (|w|^2 before, after)
     int np;
 };
 
 // Form.  Phase 0: w = psolve(y + sh z) into V[col + 1], pn.x = the piece's share of ||w||^2, part0 = its share of vdot(V[0], w).
 // Phase 1: r = b - (y + sh x) into V[0], pn.x = its share of ||r||^2.
+template <class T>
 __global__ void __launch_bounds__(GW_BT)
-gw_form_kernel(GArgs a, const int* __restrict__ act, WArgs wa) {
+gw_form_kernel(GArgsT<T> a, const int* __restrict__ act, WArgsT<T> wa) {
     __shared__ c128 sbuf[GW_BT / 64];
     const int piece = blockIdx.x % wa.np, k = act[blockIdx.x / wa.np];
     const WState& W = wa.ws[k];
     const int n = a.n, phase = W.phase, col = W.col;
-    c128* Vk = a.Vb + (long)k * a.rows_per * n;
-    const c128* y = a.Y + (long)k * n;
+    T* Vk = a.Vb + (long)k * a.rows_per * n;
+    const T* y = a.Y + (long)k * n;
     const c128 lam = a.shift[k];
-    const c128 sh = cmake(a.psi[k] - lam.x, -lam.y);
+    const T sh = sc_shift<T>(a.psi[k], lam);
     const int x0 = piece * GW_SPAN + threadIdx.x;
     const long o = (long)k * wa.np + piece;
     if (phase == 1) {
-        const c128* b = rhs_of(a, k);
-        const c128* x = Vk + (long)(a.R + 1) * n;
+        const T* b = rhs_of(a, k);
+        const T* x = Vk + (long)(a.R + 1) * n;
         double ss = 0.0;
 #pragma unroll
         for (int e = 0; e < GW_E; ++e) {
             const int i = x0 + e * GW_BT;
             if (i < n) {
-                c128 hx = y[i]; cfma(hx, sh, x[i]);
-                const c128 r = cmake(b[i].x - hx.x, b[i].y - hx.y);
+                T hx = y[i]; cfma(hx, sh, x[i]);
+                const T r = sc_sub(b[i], hx);
                 Vk[i] = r;
-                ss = fma(r.x, r.x, ss); ss = fma(r.y, r.y, ss);
+                sc_abs2(ss, r);
             }
         }
-        const c128 s = gw_block_sum(cmake(ss, 0.0), sbuf);
-        if (threadIdx.x == 0) wa.pn[o].x = s.x;
+        const double s = gw_block_sum(ss, sbuf);
+        if (threadIdx.x == 0) wa.pn[o].x = s;
         return;
     }
-    const c128* z = Vk + (long)col * n;
-    const c128* v0 = Vk;
-    c128* w = Vk + (long)(col + 1) * n;
+    const T* z = Vk + (long)col * n;
+    const T* v0 = Vk;
+    T* w = Vk + (long)(col + 1) * n;
     double ss = 0.0;
-    c128 acc = cmake(0.0, 0.0);
+    T acc = czero<T>();
 #pragma unroll
     for (int e = 0; e < GW_E; ++e) {
         const int i = x0 + e * GW_BT;
         if (i < n) {
-            c128 av = y[i]; cfma(av, sh, z[i]);
-            const c128 v = psolve1(a, k, i, av);
+            T av = y[i]; cfma(av, sh, z[i]);
+            const T v = psolve1(a, k, i, av);
             w[i] = v;
-            ss = fma(v.x, v.x, ss); ss = fma(v.y, v.y, ss);
+            sc_abs2(ss, v);
             cfma_conj(acc, v0[i], v);
         }
     }
-    const c128 s = gw_block_sum(cmake(ss, 0.0), sbuf);
-    const c128 d = gw_block_sum(acc, sbuf);
-    if (threadIdx.x == 0) { wa.pn[o].x = s.x; wa.part0[o] = d; }
+    const double s = gw_block_sum(ss, sbuf);
+    const T d = gw_block_sum(acc, sbuf);
+    if (threadIdx.x == 0) { wa.pn[o].x = s; wa.part0[o] = d; }
 }
 
 // Phase 1, the decisions of iterative.py:737-748 / 826-838 from the joined ||r||: done (phase 2) or a new cycle (cont)
+template <class T>
 __global__ void __launch_bounds__(GW_BT)
-gw_resid_kernel(GArgs a, const int* __restrict__ act, WArgs wa) {
+gw_resid_kernel(GArgsT<T> a, const int* __restrict__ act, WArgsT<T> wa) {
     __shared__ c128 sbuf[GW_BT / 64];
     const int k = act[blockIdx.x];
     WState& W = wa.ws[k];
@@ -709,45 +765,47 @@ gw_resid_kernel(GArgs a, const int* __restrict__ act, WArgs wa) {
 }
 
 // Phase 1, new cycle: V[0] = psolve(r), pn.y = the piece's share of its squared norm
+template <class T>
 __global__ void __launch_bounds__(GW_BT)
-gw_psolve_kernel(GArgs a, const int* __restrict__ act, WArgs wa) {
+gw_psolve_kernel(GArgsT<T> a, const int* __restrict__ act, WArgsT<T> wa) {
     __shared__ c128 sbuf[GW_BT / 64];
     const int piece = blockIdx.x % wa.np, k = act[blockIdx.x / wa.np];
     const WState& W = wa.ws[k];
     if (W.phase != 1 || !W.cont) return;
     const int n = a.n;
-    c128* w = a.Vb + (long)k * a.rows_per * n;
+    T* w = a.Vb + (long)k * a.rows_per * n;
     const int x0 = piece * GW_SPAN + threadIdx.x;
     double sv = 0.0;
 #pragma unroll
     for (int e = 0; e < GW_E; ++e) {
         const int i = x0 + e * GW_BT;
         if (i < n) {
-            const c128 v = psolve1(a, k, i, w[i]);
+            const T v = psolve1(a, k, i, w[i]);
             w[i] = v;
-            sv = fma(v.x, v.x, sv); sv = fma(v.y, v.y, sv);
+            sc_abs2(sv, v);
         }
     }
-    const c128 s = gw_block_sum(cmake(sv, 0.0), sbuf);
-    if (threadIdx.x == 0) wa.pn[(long)k * wa.np + piece].y = s.x;
+    const double s = gw_block_sum(sv, sbuf);
+    if (threadIdx.x == 0) wa.pn[(long)k * wa.np + piece].y = s;
 }
 
 // Phase 1, new cycle: V[0] /= ||V[0]||; piece 0 starts the cycle in GState (nothing of this tick reads GState after it)
+template <class T>
 __global__ void __launch_bounds__(GW_BT)
-gw_start_kernel(GArgs a, const int* __restrict__ act, WArgs wa) {
+gw_start_kernel(GArgsT<T> a, const int* __restrict__ act, WArgsT<T> wa) {
     __shared__ c128 sbuf[GW_BT / 64];
     const int piece = blockIdx.x % wa.np, k = act[blockIdx.x / wa.np];
     const WState& W = wa.ws[k];
     if (W.phase != 1 || !W.cont) return;
     const int n = a.n;
-    c128* w = a.Vb + (long)k * a.rows_per * n;
+    T* w = a.Vb + (long)k * a.rows_per * n;
     const double tmp = sqrt(gw_join(wa.pn + (long)k * wa.np, wa.np, sbuf).y);
     const double inv = 1.0 / tmp;
     const int x0 = piece * GW_SPAN + threadIdx.x;
 #pragma unroll
     for (int e = 0; e < GW_E; ++e) {
         const int i = x0 + e * GW_BT;
-        if (i < n) w[i] = cmake(w[i].x * inv, w[i].y * inv);
+        if (i < n) w[i] = sc_scale(w[i], inv);
     }
     if (piece == 0 && threadIdx.x == 0) {
         GState& s = a.st[k];
@@ -761,8 +819,9 @@ gw_start_kernel(GArgs a, const int* __restrict__ act, WArgs wa) {
 // before, or by the form kernel), apply w -= t V[kk - 1] and write their share of vdot(V[kk], w) from the w that leaves.
 // kk == 0 is the tail: every phase-0 candidate joins its last dot (column col), applies the last subtraction and writes
 // pn.y = its share of ||w||^2.
+template <class T>
 __global__ void __launch_bounds__(GW_BT)
-gw_mgs_kernel(GArgs a, const int* __restrict__ act, WArgs wa, int kk) {
+gw_mgs_kernel(GArgsT<T> a, const int* __restrict__ act, WArgsT<T> wa, int kk) {
     __shared__ c128 sbuf[GW_BT / 64];
     const int piece = blockIdx.x % wa.np, k = act[blockIdx.x / wa.np];
     WState& W = wa.ws[k];
@@ -772,33 +831,37 @@ gw_mgs_kernel(GArgs a, const int* __restrict__ act, WArgs wa, int kk) {
     if (tail) kk = col + 1; else if (kk > col) return;
     const int j = kk - 1, n = a.n;
     const long o = (long)k * wa.np;
-    const c128 t = gw_join(((j & 1) ? wa.part1 : wa.part0) + o, wa.np, sbuf);
-    if (piece == 0 && threadIdx.x == 0) W.hcol[j] = t;
-    c128* Vk = a.Vb + (long)k * a.rows_per * n;
-    const c128* vj = Vk + (long)j * n;
-    const c128* vk = Vk + (long)kk * n;          // the tail never reads it (it is w)
-    c128* w = Vk + (long)(col + 1) * n;
+    const T t = gw_join(((j & 1) ? wa.part1 : wa.part0) + o, wa.np, sbuf);
+    if (piece == 0 && threadIdx.x == 0) W.hcol[j] = sc_c(t);
+    T* Vk = a.Vb + (long)k * a.rows_per * n;
+    const T* vj = Vk + (long)j * n;
+    const T* vk = Vk + (long)kk * n;          // the tail never reads it (it is w)
+    T* w = Vk + (long)(col + 1) * n;
     const int x0 = piece * GW_SPAN + threadIdx.x;
-    c128 acc = cmake(0.0, 0.0);
+    T acc = czero<T>();
+    double ss = 0.0;
 #pragma unroll
     for (int e = 0; e < GW_E; ++e) {
         const int i = x0 + e * GW_BT;
         if (i < n) {
-            c128 wi = w[i]; cfms(wi, t, vj[i]); w[i] = wi;
-            if (tail) { acc.x = fma(wi.x, wi.x, acc.x); acc.x = fma(wi.y, wi.y, acc.x); }
+            T wi = w[i]; cfms(wi, t, vj[i]); w[i] = wi;
+            if (tail) sc_abs2(ss, wi);
             else cfma_conj(acc, vk[i], wi);
         }
     }
-    const c128 s = gw_block_sum(acc, sbuf);
-    if (threadIdx.x == 0) {
-        if (tail) wa.pn[o + piece].y = s.x;
-        else ((kk & 1) ? wa.part1 : wa.part0)[o + piece] = s;
+    if (tail) {                                   // uniform over the workgroup
+        const double s = gw_block_sum(ss, sbuf);
+        if (threadIdx.x == 0) wa.pn[o + piece].y = s;
+    } else {
+        const T s = gw_block_sum(acc, sbuf);
+        if (threadIdx.x == 0) ((kk & 1) ? wa.part1 : wa.part0)[o + piece] = s;
     }
 }
 
 // State: h0 and h1 from the joined partials, then arnoldi_tail on one lane per candidate, the Hessenberg column and y in WState
+template <class T>
 __global__ void __launch_bounds__(GW_BT)
-gw_state_kernel(GArgs a, const int* __restrict__ act, WArgs wa) {
+gw_state_kernel(GArgsT<T> a, const int* __restrict__ act, WArgsT<T> wa) {
     __shared__ c128 sbuf[GW_BT / 64];
     const int k = act[blockIdx.x];
     WState& W = wa.ws[k];
@@ -813,8 +876,9 @@ gw_state_kernel(GArgs a, const int* __restrict__ act, WArgs wa) {
 }
 
 // Finish: V[col + 1] = w * inv, and x += y @ V[:col + 1] where the inner loop ended
+template <class T>
 __global__ void __launch_bounds__(GW_BT)
-gw_finish_kernel(GArgs a, const int* __restrict__ act, WArgs wa) {
+gw_finish_kernel(GArgsT<T> a, const int* __restrict__ act, WArgsT<T> wa) {
     __shared__ c128 s_y[MAXR + 1];
     const int piece = blockIdx.x % wa.np, k = act[blockIdx.x / wa.np];
     const WState& W = wa.ws[k];
@@ -823,18 +887,18 @@ gw_finish_kernel(GArgs a, const int* __restrict__ act, WArgs wa) {
     const double inv = W.inv;
     if (end && threadIdx.x <= col) s_y[threadIdx.x] = W.y[threadIdx.x];
     __syncthreads();
-    c128* Vk = a.Vb + (long)k * a.rows_per * n;
-    c128* w = Vk + (long)(col + 1) * n;
-    c128* x = Vk + (long)(a.R + 1) * n;
+    T* Vk = a.Vb + (long)k * a.rows_per * n;
+    T* w = Vk + (long)(col + 1) * n;
+    T* x = Vk + (long)(a.R + 1) * n;
     const int x0 = piece * GW_SPAN + threadIdx.x;
 #pragma unroll
     for (int e = 0; e < GW_E; ++e) {
         const int i = x0 + e * GW_BT;
         if (i < n) {
-            w[i] = cmake(w[i].x * inv, w[i].y * inv);
+            w[i] = sc_scale(w[i], inv);
             if (end) {
-                c128 acc = x[i];
-                for (int j = 0; j <= col; ++j) cfma(acc, s_y[j], Vk[(long)j * n + i]);
+                T acc = x[i];
+                for (int j = 0; j <= col; ++j) cfma(acc, sc_of<T>(s_y[j]), Vk[(long)j * n + i]);
                 x[i] = acc;
             }
         }
@@ -842,16 +906,17 @@ gw_finish_kernel(GArgs a, const int* __restrict__ act, WArgs wa) {
 }
 
 // W[slot] <- x ; outputs
+template <class T>
 __global__ void __launch_bounds__(GT)
-gmres_finish_kernel(GArgs a, c128* __restrict__ W, long ldw, int* __restrict__ info, int* __restrict__ inner, int* __restrict__ status) {
+gmres_finish_kernel(GArgsT<T> a, c128* __restrict__ W, long ldw, int* __restrict__ info, int* __restrict__ inner, int* __restrict__ status) {
     __shared__ int sbad;
     const int k = blockIdx.x;
     if (threadIdx.x == 0) sbad = 0;
     __syncthreads();
-    const c128* x = a.Vb + ((long)k * a.rows_per + a.R + 1) * a.n;
+    const T* x = a.Vb + ((long)k * a.rows_per + a.R + 1) * a.n;
     c128* w = W + (long)a.slots[k] * ldw;
     bool bad = false;
-    for (int i = threadIdx.x; i < a.n; i += GT) { const c128 v = x[i]; w[i] = v; bad |= !cfinite(v); }
+    for (int i = threadIdx.x; i < a.n; i += GT) { const T v = x[i]; w[i] = sc_c(v); bad |= !sc_finite(v); }
     if (bad) atomicOr(&sbad, 1);
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -864,11 +929,32 @@ gmres_finish_kernel(GArgs a, c128* __restrict__ W, long ldw, int* __restrict__ i
 
 // sparse matrix: every active candidate's product through the CSR operand (rows do not depend on the batch, so the shared first
 // product A x0 of rhs_mode 1 needs no special case)
-void csr_product(maus_ctx* c, const GArgs& a, const int* zrow, const int* act, int nact) {
+void csr_product(maus_ctx* c, const GArgsT<c128>& a, const int* zrow, const int* act, int nact) {
     const int n = a.n;
     ProfScope ps(c, KC_SPMM, 8.0 * nact * c->Acsr.nnz, maus_spmm_operand_bytes(c->Acsr) * ((nact + 7) / 8) + 32.0 * nact * n);
     maus_spmm_launch(c->st, c->Acsr, c->csr_sched, a.Vb, n, a.Y, n, zrow, act, nact);
 }
+// the real path: a quarter of the flops, 8 of the 16 bytes of every value and vector entry
+void csr_product(maus_ctx* c, const GArgsT<double>& a, const int* zrow, const int* act, int nact) {
+    const int n = a.n;
+    ProfScope ps(c, KC_SPMM_REAL, 2.0 * nact * c->Acsr.nnz, maus_spmm_operand_bytes_real(c->Acsr) * ((nact + 7) / 8) + 16.0 * nact * n);
+    maus_spmm_launch_real(c->st, c->Acsr, c->csr_sched, a.Vb, n, a.Y, n, zrow, act, nact);
+}
+
+// what a solve over T reads of the context, and the profile classes of its post step (one workgroup per candidate / wide)
+template <class T> struct Bound;
+template <> struct Bound<c128> {
+    static const c128* diag(const maus_ctx* c) { return c->Adiag; }
+    static const c128* rhs(const maus_ctx* c) { return c->b; }
+    static const c128* pop(const maus_ctx* c) { return c->X; }
+    enum { KC_POST = KC_VEC, KC_POST_WIDE = KC_GMRES_WIDE };
+};
+template <> struct Bound<double> {
+    static const double* diag(const maus_ctx* c) { return c->Adiag_r; }
+    static const double* rhs(const maus_ctx* c) { return c->b_r; }
+    static const double* pop(const maus_ctx*) { return nullptr; }
+    enum { KC_POST = KC_GMRES_REAL, KC_POST_WIDE = KC_GMRES_REAL };
+};
 
 }  // namespace
 
@@ -889,9 +975,13 @@ int maus_jacobi_check_run(maus_ctx* c, int count, const double* shift, const dou
     return 0;
 }
 
-int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift, const double* psi, int rhs_mode,
-                   const int32_t* use_jacobi, double rtol, int restart, int maxiter, int32_t* info_out, int32_t* inner_out,
-                   int32_t* status, const c128* Hdense, long ldh, long strideH, int32_t* jacobi_out) {
+// The driver over the scalar type T of the vectors.  T = double: the real path -- maus_gmres_run has checked the rule, the
+// matrix is CSR-bound, rhs_mode is 1 and Hdense is null; the scratch holds rows of n doubles, the states are the complex ones.
+template <class T>
+static int gmres_run_t(maus_ctx* c, const int* slots, int count, const double* shift, const double* psi, int rhs_mode,
+                       const int32_t* use_jacobi, double rtol, int restart, int maxiter, int32_t* info_out, int32_t* inner_out,
+                       int32_t* status, const T* Hdense, long ldh, long strideH, int32_t* jacobi_out) {
+    constexpr bool CPLX = sizeof(T) == sizeof(c128);
     if (!maus_has_matrix(c) || !c->X) FAIL(c, "maus_gmres: matrix/population missing");
     if (c->csr && Hdense) FAIL(c, "maus_gmres: a sparse matrix has no random term (no materialised H)");
     if (c->rows != c->cols) FAIL(c, "maus_gmres: square matrix required");
@@ -908,36 +998,37 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
     const size_t rows_per = (size_t)R + 2;
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    const size_t o_d = take(sizeof(c128) * n), o_v = take(sizeof(c128) * rows_per * count * n), o_y = take(sizeof(c128) * (size_t)count * n),
+    const size_t o_d = take(sizeof(T) * n), o_v = take(sizeof(T) * rows_per * count * n), o_y = take(sizeof(T) * (size_t)count * n),
                  o_s = take(sizeof(GState) * count), o_a = take(sizeof(int) * std::max(count, PAD_ROWS)),
                  o_z = take(sizeof(int) * std::max(count, PAD_ROWS)),
                  o_n = take(sizeof(int) * 4), o_j = take(sizeof(int) * count), o_o = take(sizeof(int) * 3 * count);
-    // the wide step (method 1, CSR only): per-candidate tick state and three partial-sum buffers of one entry per piece
+    // the wide step (method 1, CSR only): per-candidate tick state and three partial-sum buffers of one entry per piece (the
+    // pair of squared norms, then the two dot products in T)
     const bool wide = c->gmres_method == 1 && c->csr && !Hdense;
     const int np = (n + GW_SPAN - 1) / GW_SPAN;
-    const size_t o_w = wide ? take(sizeof(WState) * count) : 0, o_p = wide ? take(sizeof(c128) * 3 * (size_t)count * np) : 0;
+    const size_t o_w = wide ? take(sizeof(WState) * count) : 0, o_p = wide ? take((sizeof(T) * 2 + sizeof(c128)) * (size_t)count * np) : 0;
     if (wide && (size_t)count * np > 0x7fffffffull) FAIL(c, "maus_gmres: candidates x pieces of the wide step exceed a launch");
     if (ensure_scratch(c, off)) return -1;
     char* base = (char*)c->scratch;
-    GArgs a;
+    GArgsT<T> a;
     a.n = n; a.R = R; a.maxiter = maxiter; a.rows_per = (int)rows_per; a.rtol = rtol;
-    a.dA = (c128*)(base + o_d); a.Vb = (c128*)(base + o_v); a.Y = (c128*)(base + o_y); a.st = (GState*)(base + o_s);
+    a.dA = (T*)(base + o_d); a.Vb = (T*)(base + o_v); a.Y = (T*)(base + o_y); a.st = (GState*)(base + o_s);
     int* act = (int*)(base + o_a); int* zrow = (int*)(base + o_z); int* nact = (int*)(base + o_n);
     int* jac = (int*)(base + o_j); int* outs = (int*)(base + o_o);
     a.Hd = Hdense; a.ldh = ldh; a.strideH = strideH;
-    a.shift = c->d_c1; a.psi = c->d_r1; a.jac = jac; a.X = c->X; a.ldx = c->ldp; a.slots = c->d_slots; a.bvec = c->b; a.rhs_mode = rhs_mode;
+    a.shift = c->d_c1; a.psi = c->d_r1; a.jac = jac; a.X = Bound<T>::pop(c); a.ldx = c->ldp; a.slots = c->d_slots; a.bvec = Bound<T>::rhs(c); a.rhs_mode = rhs_mode;
     if (maus_h2d(c, c->d_c1, shift, sizeof(c128) * count, c->st)) return -1;
     if (maus_h2d(c, c->d_r1, psi, sizeof(double) * count, c->st)) return -1;
     if (maus_h2d(c, jac, use_jacobi, sizeof(int) * count, c->st)) return -1;
-    if (c->csr) HIPCHK(c, hipMemcpyAsync(base + o_d, c->Adiag, sizeof(c128) * n, hipMemcpyDeviceToDevice, c->st));
+    if (c->csr) HIPCHK(c, hipMemcpyAsync(base + o_d, Bound<T>::diag(c), sizeof(T) * n, hipMemcpyDeviceToDevice, c->st));
     else hipLaunchKernelGGL(diag_kernel, dim3((n + 255) / 256), dim3(256), 0, c->st, c->A, n, (c128*)(base + o_d));
-    if (Hdense) hipLaunchKernelGGL(jacobi_gate_dense_kernel, dim3(count), dim3(GT), 0, c->st, a, jac);
-    hipLaunchKernelGGL(gmres_init_kernel, dim3(count), dim3(GT), 0, c->st, a);
+    if constexpr (CPLX) { if (Hdense) hipLaunchKernelGGL(jacobi_gate_dense_kernel, dim3(count), dim3(GT), 0, c->st, a, jac); }
+    hipLaunchKernelGGL(gmres_init_kernel<T>, dim3(count), dim3(GT), 0, c->st, a);
     const long max_ticks = (long)maxiter * (R + 1) + 2;
     int h_nact = 0;
-    WArgs wa;
-    wa.ws = (WState*)(base + o_w); wa.part0 = (c128*)(base + o_p); wa.part1 = wa.part0 + (size_t)count * np;
-    wa.pn = wa.part1 + (size_t)count * np; wa.np = np;
+    WArgsT<T> wa;
+    wa.ws = (WState*)(base + o_w); wa.pn = (c128*)(base + o_p); wa.part0 = (T*)(wa.pn + (size_t)count * np);
+    wa.part1 = wa.part0 + (size_t)count * np; wa.np = np;
     for (long tick = 0; wide && tick < max_ticks; ++tick) {
         // one read-back per tick, as below: how many candidates are active, the largest column among those in phase 0 and how
         // many are in phase 1 -- the host issues only the launches this tick has work for
@@ -952,19 +1043,19 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
         csr_product(c, a, zrow, act, h_nact);
         // bytes: form 64 n per candidate; a Gram-Schmidt column 64 n (w in and out, V[kk - 1], V[kk]), the tail 48 n; finish 32 n;
         // a new cycle 64 n (x += y @ V of the candidates whose inner loop ends is not counted)
-        ProfScope ps(c, KC_GMRES_WIDE, 0, (double)n * (64.0 * h_nact + 64.0 * h[3] + 80.0 * n0 + 64.0 * n1));
+        ProfScope ps(c, Bound<T>::KC_POST_WIDE, 0, (sizeof(T) / 16.0) * (double)n * (64.0 * h_nact + 64.0 * h[3] + 80.0 * n0 + 64.0 * n1));
         const dim3 gp((unsigned)((size_t)h_nact * np)), gc(h_nact), bt(GW_BT);
-        hipLaunchKernelGGL(gw_form_kernel, gp, bt, 0, c->st, a, act, wa);
+        hipLaunchKernelGGL(gw_form_kernel<T>, gp, bt, 0, c->st, a, act, wa);
         if (n1 > 0) {
-            hipLaunchKernelGGL(gw_resid_kernel, gc, bt, 0, c->st, a, act, wa);
-            hipLaunchKernelGGL(gw_psolve_kernel, gp, bt, 0, c->st, a, act, wa);
-            hipLaunchKernelGGL(gw_start_kernel, gp, bt, 0, c->st, a, act, wa);
+            hipLaunchKernelGGL(gw_resid_kernel<T>, gc, bt, 0, c->st, a, act, wa);
+            hipLaunchKernelGGL(gw_psolve_kernel<T>, gp, bt, 0, c->st, a, act, wa);
+            hipLaunchKernelGGL(gw_start_kernel<T>, gp, bt, 0, c->st, a, act, wa);
         }
         if (n0 > 0) {
-            for (int kk = 1; kk <= maxcol; ++kk) hipLaunchKernelGGL(gw_mgs_kernel, gp, bt, 0, c->st, a, act, wa, kk);
-            hipLaunchKernelGGL(gw_mgs_kernel, gp, bt, 0, c->st, a, act, wa, 0);
-            hipLaunchKernelGGL(gw_state_kernel, gc, bt, 0, c->st, a, act, wa);
-            hipLaunchKernelGGL(gw_finish_kernel, gp, bt, 0, c->st, a, act, wa);
+            for (int kk = 1; kk <= maxcol; ++kk) hipLaunchKernelGGL(gw_mgs_kernel<T>, gp, bt, 0, c->st, a, act, wa, kk);
+            hipLaunchKernelGGL(gw_mgs_kernel<T>, gp, bt, 0, c->st, a, act, wa, 0);
+            hipLaunchKernelGGL(gw_state_kernel<T>, gc, bt, 0, c->st, a, act, wa);
+            hipLaunchKernelGGL(gw_finish_kernel<T>, gp, bt, 0, c->st, a, act, wa);
         }
     }
     for (long tick = 0; !wide && tick < max_ticks; ++tick) {
@@ -973,7 +1064,8 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
         HIPCHK(c, hipStreamSynchronize(c->st));
         if (h_nact <= 0) break;
         if (c->csr) csr_product(c, a, zrow, act, h_nact);
-        else if (Hdense) {
+        else if constexpr (CPLX) {                                 // the dense products: complex only (the rule)
+        if (Hdense) {
             ProfScope ps(c, KC_VEC, 0, 16.0 * h_nact * (double)n * n);
             hipLaunchKernelGGL(gemv_dense_kernel, dim3((n + 15) / 16, h_nact), dim3(GT), 0, c->st, a, act, zrow);
         } else
@@ -999,14 +1091,15 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
             ProfScope ps(c, KC_GEMM, 8.0 * m * (double)n * n, 16.0 * ((double)n * n + 2.0 * m * n));
             maus_zgemm_launch_idx(c->st, m, n, n, a.Vb, n, 0, c->A, n, 0, a.Y, n, 0, 1.0, 0, 1, 1, false, false, zrow, act);
         }
-        { ProfScope ps(c, KC_VEC, 0, 16.0 * h_nact * (double)n * (R + 4));
-          if (n <= 4 * GT) hipLaunchKernelGGL((gmres_post_kernel<4>), dim3(h_nact), dim3(GT), 0, c->st, a, act);
-          else if (n <= 16 * GT) hipLaunchKernelGGL((gmres_post_kernel<16>), dim3(h_nact), dim3(GT), 0, c->st, a, act);
-          else if (n <= 32 * GT) hipLaunchKernelGGL((gmres_post_kernel<32>), dim3(h_nact), dim3(GT), 0, c->st, a, act);
-          else if (n <= 64 * GT) hipLaunchKernelGGL((gmres_post_kernel<32, 2 * GT>), dim3(h_nact), dim3(2 * GT), 0, c->st, a, act);
-          else hipLaunchKernelGGL((gmres_post_stream_kernel<4 * GT>), dim3(h_nact), dim3(4 * GT), 0, c->st, a, act); }
+        }
+        { ProfScope ps(c, Bound<T>::KC_POST, 0, sizeof(T) * (double)h_nact * (double)n * (R + 4));
+          if (n <= 4 * GT) hipLaunchKernelGGL((gmres_post_kernel<T, 4>), dim3(h_nact), dim3(GT), 0, c->st, a, act);
+          else if (n <= 16 * GT) hipLaunchKernelGGL((gmres_post_kernel<T, 16>), dim3(h_nact), dim3(GT), 0, c->st, a, act);
+          else if (n <= 32 * GT) hipLaunchKernelGGL((gmres_post_kernel<T, 32>), dim3(h_nact), dim3(GT), 0, c->st, a, act);
+          else if (n <= 64 * GT) hipLaunchKernelGGL((gmres_post_kernel<T, 32, 2 * GT>), dim3(h_nact), dim3(2 * GT), 0, c->st, a, act);
+          else hipLaunchKernelGGL((gmres_post_stream_kernel<T, 4 * GT>), dim3(h_nact), dim3(4 * GT), 0, c->st, a, act); }
     }
-    hipLaunchKernelGGL(gmres_finish_kernel, dim3(count), dim3(GT), 0, c->st, a, c->W, c->ldp, outs, outs + count, outs + 2 * count);
+    hipLaunchKernelGGL(gmres_finish_kernel<T>, dim3(count), dim3(GT), 0, c->st, a, c->W, c->ldp, outs, outs + count, outs + 2 * count);
     if (maus_d2h(c, info_out, outs, sizeof(int) * count, c->st)) return -1;
     if (maus_d2h(c, inner_out, outs + count, sizeof(int) * count, c->st)) return -1;
     if (maus_d2h(c, status, outs + 2 * count, sizeof(int) * count, c->st)) return -1;
@@ -1014,6 +1107,31 @@ int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift
     HIPCHK(c, hipStreamSynchronize(c->st));
     HIPCHK(c, hipGetLastError());
     return 0;
+}
+
+int maus_gmres_run(maus_ctx* c, const int* slots, int count, const double* shift, const double* psi, int rhs_mode,
+                   const int32_t* use_jacobi, double rtol, int restart, int maxiter, int32_t* info_out, int32_t* inner_out,
+                   int32_t* status, const c128* Hdense, long ldh, long strideH, int32_t* jacobi_out, bool real) {
+    if (real) {
+        // the caller decided by maus_real_rule for the whole call; what the rule relies on is checked again where it is used
+        if (Hdense || !c->csr || rhs_mode != 1 || !c->Acsr.rval || !c->Adiag_r || !c->b_r || c->b_rn != c->rows)
+            FAIL(c, "maus_gmres: the real path was chosen without its real copies");
+        return gmres_run_t<double>(c, slots, count, shift, psi, rhs_mode, use_jacobi, rtol, restart, maxiter, info_out, inner_out,
+                                   status, nullptr, 0, 0, jacobi_out);
+    }
+    return gmres_run_t<c128>(c, slots, count, shift, psi, rhs_mode, use_jacobi, rtol, restart, maxiter, info_out, inner_out,
+                             status, Hdense, ldh, strideH, jacobi_out);
+}
+
+// The rule of the real path, stated once: maus_gmres decides by it and maus_real_plan reports it.  All or nothing per call.
+int maus_real_rule(const maus_ctx* c, int rhs_mode, int count, const double* shift) {
+    if (c->real_method != 1) return MAUS_REAL_METHOD_OFF;
+    if (!c->csr || c->rows != c->cols) return MAUS_REAL_NOT_CSR;         // no square CSR matrix bound: no real copies either
+    if (!c->A_real) return MAUS_REAL_MATRIX_COMPLEX;
+    if (rhs_mode != 1) return MAUS_REAL_RHS_ROWS;
+    if (!c->b || !c->b_real) return MAUS_REAL_RHS_COMPLEX;
+    if (count > 0 && !maus_real_flagged(shift, (size_t)count)) return MAUS_REAL_SHIFT_COMPLEX;
+    return MAUS_REAL_OK;
 }
 
 int maus_gmres_set_method(maus_ctx* c, int method) {
@@ -1024,6 +1142,21 @@ int maus_gmres_set_method(maus_ctx* c, int method) {
 }
 
 int maus_gmres_get_method(maus_ctx* c) { return c ? c->gmres_method : -1; }
+
+int maus_real_plan(maus_ctx* c, int rhs_mode, int count, const double* shift, int64_t* out) {
+    if (!c) return -1;
+    if (count < 0 || (count > 0 && !shift) || !out) FAIL(c, "maus_real_plan: bad arguments");
+    const int why = maus_real_rule(c, rhs_mode, count, shift);
+    const bool bound = c->csr && c->rows == c->cols;
+    out[0] = why == MAUS_REAL_OK;
+    out[1] = why;
+    out[2] = bound ? maus_gmres_kernel_for(c, c->rows, 1) : -1;                                  // post schedule: 0 register, 1 stream, 2 wide
+    out[3] = bound ? (c->Acsr.sell.val ? 3 : c->csr_sched) : 0;                                  // SpMM kernel, as maus_spmm_kernel_for
+    out[4] = c->real_allocs;
+    out[5] = (c->Acsr.rval ? 8 * std::max(1L, c->Acsr.nnz) : 0) + (c->Acsr.sell.rval ? 8 * c->Acsr.sell.padded : 0)
+             + (c->Adiag_r ? 8L * c->rows : 0) + (c->b_r ? 8L * c->b_rn : 0);                     // bytes of the real copies held
+    return 0;
+}
 
 int maus_gmres_kernel_for(maus_ctx* c, int n, int csr) {
     if (!c) return -1;

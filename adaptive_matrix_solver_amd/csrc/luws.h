@@ -41,7 +41,7 @@ struct LuWs {
 // 64 s .. 64 s + 63 with the width w_s of its longest row; entry p of row r sits at off[s] + 64 p + (r & 63), in the order it
 // has in the CSR row.  off has slices + 1 entries (64-bit: the padded size may pass 2^31), len one per row; wmax is the longest
 // row of the matrix.  val == nullptr: the operand has no such copy and runs the CSR kernels.
-struct MausSell { c128* val = nullptr; int* idx = nullptr; int* len = nullptr; long* off = nullptr; long padded = 0; int slices = 0, wmax = 0; };
+struct MausSell { c128* val = nullptr; double* rval = nullptr; int* idx = nullptr; int* len = nullptr; long* off = nullptr; long padded = 0; int slices = 0, wmax = 0; };
 
 // CSR operand of a sparse problem matrix (spmm.hip, maus_build_h_csr): 32-bit row pointers and column indices, complex values
-struct MausCsr { int* ptr = nullptr; int* idx = nullptr; c128* val = nullptr; long nnz = 0; int rows = 0; MausSell sell; };
+struct MausCsr { int* ptr = nullptr; int* idx = nullptr; c128* val = nullptr; double* rval = nullptr; long nnz = 0; int rows = 0; MausSell sell; };

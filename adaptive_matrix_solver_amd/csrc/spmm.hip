@@ -17,6 +17,7 @@
 // device at bind time) and spmm_sell_kernel reads that copy: the same lane per row, the same operations in the same order, the
 // same bits, with coalesced operand loads and several nonzeros' gathers in flight.  spmm_kind states which operand takes it.
 #include "ctx.h"
+#include <cstring>
 
 namespace {
 
@@ -24,25 +25,28 @@ constexpr int SP_CG = 8;          // candidates per thread: each nonzero (16 B v
 constexpr int SP_BT = 256;        // threads per block
 
 // short rows (banded operators, up to ~32 nonzeros per row): one lane per row, so consecutive lanes gather neighbouring x[col]
+// T = c128, or double for the real path (maus_real_set_method): the operand's real copy times rows of doubles, the same lane,
+// the same order, one fma where the complex text has the two of a real part (common.h)
+template <class T>
 __global__ void __launch_bounds__(SP_BT)
-spmm_rows_kernel(const int* __restrict__ ptr, const int* __restrict__ idx, const c128* __restrict__ val, int nrows,
-                 const c128* __restrict__ B, long ldb, c128* __restrict__ C, long ldc,
+spmm_rows_kernel(const int* __restrict__ ptr, const int* __restrict__ idx, const T* __restrict__ val, int nrows,
+                 const T* __restrict__ B, long ldb, T* __restrict__ C, long ldc,
                  const int* __restrict__ a_rows, const int* __restrict__ c_rows, int count)
 {
     const int i = blockIdx.x * SP_BT + threadIdx.x;
     const int k0 = blockIdx.y * SP_CG;
     if (i >= nrows) return;
     const int ng = min(SP_CG, count - k0);
-    const c128* b[SP_CG];
-    c128 acc[SP_CG];
+    const T* b[SP_CG];
+    T acc[SP_CG];
 #pragma unroll
     for (int g = 0; g < SP_CG; ++g) {
         b[g] = B + (long)a_rows[k0 + (g < ng ? g : 0)] * ldb;
-        acc[g] = cmake(0.0, 0.0);
+        acc[g] = czero<T>();
     }
     const int p1 = ptr[i + 1];
     for (int p = ptr[i]; p < p1; ++p) {
-        const c128 a = val[p];
+        const T a = val[p];
         const int j = idx[p];
 #pragma unroll
         for (int g = 0; g < SP_CG; ++g)
@@ -78,12 +82,12 @@ constexpr bool SELL_G1 = MAUS_SELL_G1;  // a lone candidate runs the instantiati
 
 // W consecutive entries of the lane's row from entry p on: W index / value loads, then W x ng gathers, then the products for
 // p ascending
-template <int CG, int W>
-__device__ __forceinline__ void sell_chunk(c128 (&acc)[CG], const c128* const (&b)[CG], int ng,
-                                           const int* __restrict__ ji, const c128* __restrict__ av, int p)
+template <class T, int CG, int W>
+__device__ __forceinline__ void sell_chunk(T (&acc)[CG], const T* const (&b)[CG], int ng,
+                                           const int* __restrict__ ji, const T* __restrict__ av, int p)
 {
     int j[W];
-    c128 a[W], x[W][CG];
+    T a[W], x[W][CG];
 #pragma unroll
     for (int u = 0; u < W; ++u) {
         j[u] = ji[(long)(p + u) * MAUS_WAVE];
@@ -101,33 +105,33 @@ __device__ __forceinline__ void sell_chunk(c128 (&acc)[CG], const c128* const (&
             if (g < ng) cfma(acc[g], a[u], x[u][g]);
 }
 
-template <int CG, int U>
+template <class T, int CG, int U>
 __global__ void __launch_bounds__(SP_BT)
-spmm_sell_kernel(const long* __restrict__ off, const int* __restrict__ len, const int* __restrict__ idx, const c128* __restrict__ val,
-                 int nrows, const c128* __restrict__ B, long ldb, c128* __restrict__ C, long ldc,
+spmm_sell_kernel(const long* __restrict__ off, const int* __restrict__ len, const int* __restrict__ idx, const T* __restrict__ val,
+                 int nrows, const T* __restrict__ B, long ldb, T* __restrict__ C, long ldc,
                  const int* __restrict__ a_rows, const int* __restrict__ c_rows, int count)
 {
     const int i = blockIdx.x * SP_BT + threadIdx.x;
     const int k0 = blockIdx.y * CG;
     if (i >= nrows) return;
     const int ng = min(CG, count - k0);
-    const c128* b[CG];
-    c128 acc[CG];
+    const T* b[CG];
+    T acc[CG];
 #pragma unroll
     for (int g = 0; g < CG; ++g) {
         b[g] = B + (long)a_rows[k0 + (g < ng ? g : 0)] * ldb;
-        acc[g] = cmake(0.0, 0.0);
+        acc[g] = czero<T>();
     }
     const long base = off[i / MAUS_WAVE] + (i % MAUS_WAVE);
     const int* __restrict__ ji = idx + base;
-    const c128* __restrict__ av = val + base;
+    const T* __restrict__ av = val + base;
     const int n = len[i];
     int p = 0;
-    for (; p + U <= n; p += U) sell_chunk<CG, U>(acc, b, ng, ji, av, p);
+    for (; p + U <= n; p += U) sell_chunk<T, CG, U>(acc, b, ng, ji, av, p);
     // the row's last n % U entries, in chunks of 4, 2, 1: still p ascending
-    if constexpr (U > 4) if (p + 4 <= n) { sell_chunk<CG, 4>(acc, b, ng, ji, av, p); p += 4; }
-    if constexpr (U > 2) if (p + 2 <= n) { sell_chunk<CG, 2>(acc, b, ng, ji, av, p); p += 2; }
-    if (p < n) sell_chunk<CG, 1>(acc, b, ng, ji, av, p);
+    if constexpr (U > 4) if (p + 4 <= n) { sell_chunk<T, CG, 4>(acc, b, ng, ji, av, p); p += 4; }
+    if constexpr (U > 2) if (p + 2 <= n) { sell_chunk<T, CG, 2>(acc, b, ng, ji, av, p); p += 2; }
+    if (p < n) sell_chunk<T, CG, 1>(acc, b, ng, ji, av, p);
 #pragma unroll
     for (int g = 0; g < CG; ++g)
         if (g < ng) C[(long)c_rows[k0 + g] * ldc + i] = acc[g];
@@ -147,10 +151,12 @@ sell_width_kernel(const int* __restrict__ ptr, int nrows, int nslices, int* __re
 }
 
 // step 3 (step 2, the exclusive scan of 64 w_s into off, runs on the host): a thread per row copies its entries in CSR order and
-// writes the rest of its lane of the slice as (index 0, value 0); one writer per slot, no atomics
+// writes the rest of its lane of the slice as (index 0, value 0); one writer per slot, no atomics.  sidx == nullptr: the values
+// alone (the real copy shares the indices of the complex one)
+template <class T>
 __global__ void __launch_bounds__(SP_BT)
-sell_fill_kernel(const int* __restrict__ ptr, const int* __restrict__ idx, const c128* __restrict__ val, int nrows, int nslices,
-                 const long* __restrict__ off, int* __restrict__ sidx, c128* __restrict__ sval)
+sell_fill_kernel(const int* __restrict__ ptr, const int* __restrict__ idx, const T* __restrict__ val, int nrows, int nslices,
+                 const long* __restrict__ off, int* __restrict__ sidx, T* __restrict__ sval)
 {
     const int r = blockIdx.x * SP_BT + threadIdx.x;
     const int s = r / MAUS_WAVE;
@@ -160,19 +166,23 @@ sell_fill_kernel(const int* __restrict__ ptr, const int* __restrict__ idx, const
     const int p0 = r < nrows ? ptr[r] : 0;
     const int n = r < nrows ? ptr[r + 1] - p0 : 0;
     for (int p = 0; p < n; ++p) {
-        sidx[base + (long)p * MAUS_WAVE] = idx[p0 + p];
+        if (sidx) sidx[base + (long)p * MAUS_WAVE] = idx[p0 + p];
         sval[base + (long)p * MAUS_WAVE] = val[p0 + p];
     }
     for (int p = n; p < w; ++p) {
-        sidx[base + (long)p * MAUS_WAVE] = 0;
-        sval[base + (long)p * MAUS_WAVE] = cmake(0.0, 0.0);
+        if (sidx) sidx[base + (long)p * MAUS_WAVE] = 0;
+        sval[base + (long)p * MAUS_WAVE] = czero<T>();
     }
 }
 
 // long rows: one wave per row, lanes over the row's nonzeros, the partial sums joined by a fixed tree
+__device__ __forceinline__ c128 sp_wave_sum(c128 v) { const double re = wave_sum_dpp(v.x), im = wave_sum_dpp(v.y); return cmake(re, im); }
+__device__ __forceinline__ double sp_wave_sum(double v) { return wave_sum_dpp(v); }
+
+template <class T>
 __global__ void __launch_bounds__(SP_BT)
-spmm_wave_kernel(const int* __restrict__ ptr, const int* __restrict__ idx, const c128* __restrict__ val, int nrows,
-                 const c128* __restrict__ B, long ldb, c128* __restrict__ C, long ldc,
+spmm_wave_kernel(const int* __restrict__ ptr, const int* __restrict__ idx, const T* __restrict__ val, int nrows,
+                 const T* __restrict__ B, long ldb, T* __restrict__ C, long ldc,
                  const int* __restrict__ a_rows, const int* __restrict__ c_rows, int count)
 {
     const int lane = threadIdx.x & (MAUS_WAVE - 1);
@@ -180,16 +190,16 @@ spmm_wave_kernel(const int* __restrict__ ptr, const int* __restrict__ idx, const
     const int k0 = blockIdx.y * SP_CG;
     if (i >= nrows) return;                       // whole waves leave together (i is uniform per wave)
     const int ng = min(SP_CG, count - k0);
-    const c128* b[SP_CG];
-    c128 acc[SP_CG];
+    const T* b[SP_CG];
+    T acc[SP_CG];
 #pragma unroll
     for (int g = 0; g < SP_CG; ++g) {
         b[g] = B + (long)a_rows[k0 + (g < ng ? g : 0)] * ldb;
-        acc[g] = cmake(0.0, 0.0);
+        acc[g] = czero<T>();
     }
     const int p1 = ptr[i + 1];
     for (int p = ptr[i] + lane; p < p1; p += MAUS_WAVE) {
-        const c128 a = val[p];
+        const T a = val[p];
         const int j = idx[p];
 #pragma unroll
         for (int g = 0; g < SP_CG; ++g)
@@ -198,54 +208,151 @@ spmm_wave_kernel(const int* __restrict__ ptr, const int* __restrict__ idx, const
 #pragma unroll
     for (int g = 0; g < SP_CG; ++g) {
         if (g >= ng) break;                       // ng is uniform per wave
-        const double re = wave_sum_dpp(acc[g].x), im = wave_sum_dpp(acc[g].y);
-        if (lane == 0) C[(long)c_rows[k0 + g] * ldc + i] = cmake(re, im);
+        const T sum = sp_wave_sum(acc[g]);
+        if (lane == 0) C[(long)c_rows[k0 + g] * ldc + i] = sum;
     }
 }
 
 // d[i] = A[i][i] (0 where the row stores no diagonal entry)
+template <class T>
 __global__ void __launch_bounds__(SP_BT)
-csr_diag_kernel(const int* __restrict__ ptr, const int* __restrict__ idx, const c128* __restrict__ val, int n, c128* __restrict__ d)
+csr_diag_kernel(const int* __restrict__ ptr, const int* __restrict__ idx, const T* __restrict__ val, int n, T* __restrict__ d)
 {
     const int i = blockIdx.x * SP_BT + threadIdx.x;
     if (i >= n) return;
-    c128 v = cmake(0.0, 0.0);
+    T v = czero<T>();
     for (int p = ptr[i]; p < ptr[i + 1]; ++p)
         if (idx[p] == i) { v = val[p]; break; }
     d[i] = v;
 }
 
+// r[i] = Re z[i]: the real copy of values whose imaginary parts are all +-0 (maus_real_sync_*)
+__global__ void __launch_bounds__(SP_BT)
+real_part_kernel(const c128* __restrict__ z, double* __restrict__ r, long n)
+{
+    const long i = (long)blockIdx.x * SP_BT + threadIdx.x;
+    if (i < n) r[i] = z[i].x;
+}
+
+// maus_real_spmm: R[k] = Re X[slots[k]] (and the row list 0 .. count - 1), and back, Y[slots[k]] = (Q[k], +0)
+__global__ void __launch_bounds__(SP_BT)
+real_rows_in_kernel(const c128* __restrict__ X, long ldx, const int* __restrict__ slots, int n, double* __restrict__ R, int* __restrict__ ident)
+{
+    const int i = blockIdx.x * SP_BT + threadIdx.x, k = blockIdx.y;
+    if (i < n) R[(long)k * n + i] = X[(long)slots[k] * ldx + i].x;
+    if (i == 0) ident[k] = k;
+}
+__global__ void __launch_bounds__(SP_BT)
+real_rows_out_kernel(const double* __restrict__ Q, int n, const int* __restrict__ slots, c128* __restrict__ Y, long ldy)
+{
+    const int i = blockIdx.x * SP_BT + threadIdx.x, k = blockIdx.y;
+    if (i < n) Y[(long)slots[k] * ldy + i] = cmake(Q[(long)k * n + i], 0.0);
+}
+
 }  // namespace
 
-void maus_spmm_launch(hipStream_t st, const MausCsr& m, int sched, const c128* B, long ldb, c128* C, long ldc,
-                      const int* a_rows, const int* c_rows, int count) {
+// One launch table for both scalar types: `val` / `sval` are the operand's values and those of its sliced-ELL copy in T
+template <class T>
+static void spmm_launch_t(hipStream_t st, const MausCsr& m, const T* val, const T* sval, int sched, const T* B, long ldb, T* C, long ldc,
+                          const int* a_rows, const int* c_rows, int count) {
     if (count <= 0 || m.rows <= 0) return;
     const int groups = (count + SP_CG - 1) / SP_CG;
     const MausSell& s = m.sell;
     const dim3 rows_grid((m.rows + SP_BT - 1) / SP_BT, groups);
-    if (SELL_G1 && s.val && count == 1)                 // the copy exists only under the lane-per-row schedule of the matrix (spmm_kind)
-        hipLaunchKernelGGL((spmm_sell_kernel<1, SELL_U1>), rows_grid, dim3(SP_BT), 0, st,
-                           s.off, s.len, s.idx, s.val, m.rows, B, ldb, C, ldc, a_rows, c_rows, count);
-    else if (s.val && s.wmax < SELL_U)
-        hipLaunchKernelGGL((spmm_sell_kernel<SP_CG, SELL_U_SHORT>), rows_grid, dim3(SP_BT), 0, st,
-                           s.off, s.len, s.idx, s.val, m.rows, B, ldb, C, ldc, a_rows, c_rows, count);
-    else if (s.val)
-        hipLaunchKernelGGL((spmm_sell_kernel<SP_CG, SELL_U>), rows_grid, dim3(SP_BT), 0, st,
-                           s.off, s.len, s.idx, s.val, m.rows, B, ldb, C, ldc, a_rows, c_rows, count);
+    if (SELL_G1 && sval && count == 1)                  // the copy exists only under the lane-per-row schedule of the matrix (spmm_kind)
+        hipLaunchKernelGGL((spmm_sell_kernel<T, 1, SELL_U1>), rows_grid, dim3(SP_BT), 0, st,
+                           s.off, s.len, s.idx, sval, m.rows, B, ldb, C, ldc, a_rows, c_rows, count);
+    else if (sval && s.wmax < SELL_U)
+        hipLaunchKernelGGL((spmm_sell_kernel<T, SP_CG, SELL_U_SHORT>), rows_grid, dim3(SP_BT), 0, st,
+                           s.off, s.len, s.idx, sval, m.rows, B, ldb, C, ldc, a_rows, c_rows, count);
+    else if (sval)
+        hipLaunchKernelGGL((spmm_sell_kernel<T, SP_CG, SELL_U>), rows_grid, dim3(SP_BT), 0, st,
+                           s.off, s.len, s.idx, sval, m.rows, B, ldb, C, ldc, a_rows, c_rows, count);
     else if (sched == MAUS_SPMM_WAVE)
-        hipLaunchKernelGGL(spmm_wave_kernel, dim3((m.rows + SP_BT / MAUS_WAVE - 1) / (SP_BT / MAUS_WAVE), groups), dim3(SP_BT), 0, st,
-                           m.ptr, m.idx, m.val, m.rows, B, ldb, C, ldc, a_rows, c_rows, count);
+        hipLaunchKernelGGL(spmm_wave_kernel<T>, dim3((m.rows + SP_BT / MAUS_WAVE - 1) / (SP_BT / MAUS_WAVE), groups), dim3(SP_BT), 0, st,
+                           m.ptr, m.idx, val, m.rows, B, ldb, C, ldc, a_rows, c_rows, count);
     else
-        hipLaunchKernelGGL(spmm_rows_kernel, dim3((m.rows + SP_BT - 1) / SP_BT, groups), dim3(SP_BT), 0, st,
-                           m.ptr, m.idx, m.val, m.rows, B, ldb, C, ldc, a_rows, c_rows, count);
+        hipLaunchKernelGGL(spmm_rows_kernel<T>, dim3((m.rows + SP_BT - 1) / SP_BT, groups), dim3(SP_BT), 0, st,
+                           m.ptr, m.idx, val, m.rows, B, ldb, C, ldc, a_rows, c_rows, count);
+}
+
+void maus_spmm_launch(hipStream_t st, const MausCsr& m, int sched, const c128* B, long ldb, c128* C, long ldc,
+                      const int* a_rows, const int* c_rows, int count) {
+    spmm_launch_t<c128>(st, m, m.val, m.sell.val, sched, B, ldb, C, ldc, a_rows, c_rows, count);
+}
+
+// the real path: the operand's real copy (m.rval; m.sell.rval where the complex operand runs the sliced-ELL kernel) times rows
+// of doubles -- the kernel, geometry and row lists that maus_spmm_launch picks for the same operand
+void maus_spmm_launch_real(hipStream_t st, const MausCsr& m, int sched, const double* B, long ldb, double* C, long ldc,
+                           const int* a_rows, const int* c_rows, int count) {
+    spmm_launch_t<double>(st, m, m.rval, m.sell.val ? m.sell.rval : nullptr, sched, B, ldb, C, ldc, a_rows, c_rows, count);
 }
 
 void maus_csr_diag_launch(hipStream_t st, const MausCsr& m, int n, c128* d) {
-    hipLaunchKernelGGL(csr_diag_kernel, dim3((n + SP_BT - 1) / SP_BT), dim3(SP_BT), 0, st, m.ptr, m.idx, m.val, n, d);
+    hipLaunchKernelGGL(csr_diag_kernel<c128>, dim3((n + SP_BT - 1) / SP_BT), dim3(SP_BT), 0, st, m.ptr, m.idx, m.val, n, d);
+}
+
+bool maus_real_flagged(const double* v, size_t count) {
+    for (size_t i = 0; i < count; ++i) {
+        uint64_t bits;
+        memcpy(&bits, &v[2 * i + 1], sizeof bits);
+        if (bits << 1) return false;            // anything but +0 / -0: a denormal, a NaN, a number
+    }
+    return true;
+}
+
+static int real_alloc(maus_ctx* c, double** p, size_t count) {
+    HIPCHK(c, hipMalloc((void**)p, sizeof(double) * std::max<size_t>(1, count)));
+    c->real_allocs += 1;
+    return 0;
+}
+static void real_release(double*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
+
+// The operand's real copies: the CSR values (indices shared with the complex CSR), their sliced-ELL copy where the complex
+// operand has one (the fill step of the build above on the real values; widths and offsets are the complex copy's), and the
+// diagonal.  They exist only while the rule can hold for the bound matrix: method 1, a square CSR matrix flagged real.
+int maus_real_sync_matrix(maus_ctx* c) {
+    MausCsr& m = c->Acsr;
+    if (!(c->real_method == 1 && c->csr && c->A_real && c->rows == c->cols)) {
+        real_release(m.rval); real_release(m.sell.rval); real_release(c->Adiag_r);
+        return 0;
+    }
+    const int n = c->rows;
+    if (!m.rval) {
+        if (real_alloc(c, &m.rval, (size_t)m.nnz)) return -1;
+        if (m.nnz > 0)
+            hipLaunchKernelGGL(real_part_kernel, dim3((unsigned)((m.nnz + SP_BT - 1) / SP_BT)), dim3(SP_BT), 0, c->st, m.val, m.rval, m.nnz);
+    }
+    if (!c->Adiag_r) {
+        if (real_alloc(c, &c->Adiag_r, (size_t)n)) return -1;
+        hipLaunchKernelGGL(csr_diag_kernel<double>, dim3((n + SP_BT - 1) / SP_BT), dim3(SP_BT), 0, c->st, m.ptr, m.idx, m.rval, n, c->Adiag_r);
+    }
+    if (!m.sell.val) real_release(m.sell.rval);
+    else if (!m.sell.rval) {
+        const MausSell& s = m.sell;
+        if (real_alloc(c, &m.sell.rval, (size_t)s.padded)) return -1;
+        hipLaunchKernelGGL(sell_fill_kernel<double>, dim3((s.slices * MAUS_WAVE + SP_BT - 1) / SP_BT), dim3(SP_BT), 0, c->st,
+                           m.ptr, m.idx, m.rval, m.rows, s.slices, s.off, (int*)nullptr, m.sell.rval);
+    }
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// The real copy of b, under method 1 for a b flagged real; refilled whenever b is set
+int maus_real_sync_rhs(maus_ctx* c) {
+    if (!(c->real_method == 1 && c->b && c->b_real)) { real_release(c->b_r); c->b_rn = 0; return 0; }
+    if (c->b_rn != c->bn) { real_release(c->b_r); c->b_rn = 0; }
+    if (!c->b_r) { if (real_alloc(c, &c->b_r, (size_t)c->bn)) return -1; c->b_rn = c->bn; }
+    hipLaunchKernelGGL(real_part_kernel, dim3((c->bn + SP_BT - 1) / SP_BT), dim3(SP_BT), 0, c->st, c->b, c->b_r, (long)c->bn);
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipGetLastError());
+    return 0;
 }
 
 static void sell_free(MausSell& s) {
     if (s.val) (void)hipFree(s.val);
+    if (s.rval) (void)hipFree(s.rval);
     if (s.idx) (void)hipFree(s.idx);
     if (s.len) (void)hipFree(s.len);
     if (s.off) (void)hipFree(s.off);
@@ -257,6 +364,7 @@ void maus_csr_free(MausCsr& m) {
     if (m.ptr) (void)hipFree(m.ptr);
     if (m.idx) (void)hipFree(m.idx);
     if (m.val) (void)hipFree(m.val);
+    if (m.rval) (void)hipFree(m.rval);
     m = MausCsr();
 }
 
@@ -296,7 +404,7 @@ static int sell_build_into(maus_ctx* c, const MausCsr& m, MausSell& s, int*& d_w
     HIPCHK(c, hipMalloc((void**)&s.idx, sizeof(int) * s.padded));
     HIPCHK(c, hipMalloc((void**)&s.val, sizeof(c128) * s.padded));
     if (maus_stage_h2d(c, s.off, off.data(), sizeof(long) * (ns + 1), c->st)) return -1;
-    hipLaunchKernelGGL(sell_fill_kernel, dim3(blocks), dim3(SP_BT), 0, c->st, m.ptr, m.idx, m.val, m.rows, ns, s.off, s.idx, s.val);
+    hipLaunchKernelGGL(sell_fill_kernel<c128>, dim3(blocks), dim3(SP_BT), 0, c->st, m.ptr, m.idx, m.val, m.rows, ns, s.off, s.idx, s.val);
     HIPCHK(c, hipStreamSynchronize(c->st));
     HIPCHK(c, hipGetLastError());
     return 0;
@@ -385,7 +493,8 @@ int maus_set_matrix_csr(maus_ctx* c, int rows, int cols, int64_t nnz,
     HIPCHK(c, hipStreamSynchronize(c->st));
     HIPCHK(c, hipGetLastError());
     if (sell_build(c, c->Acsr) || sell_build(c, c->AHcsr)) return -1;      // under maus_spmm_set_method(ctx, 1)
-    return 0;
+    c->A_real = maus_real_flagged(values_c128, (size_t)nnz);
+    return maus_real_sync_matrix(c);                                       // under maus_real_set_method(ctx, 1)
 }
 
 int maus_matrix_is_sparse(maus_ctx* c) {
@@ -410,12 +519,60 @@ int maus_spmm_set_method(maus_ctx* c, int method, int fill_cap_percent) {
         c->spmm_method = old_method; c->spmm_fill_cap = old_cap;
         if (sell_build(c, c->Acsr) || sell_build(c, c->AHcsr)) { sell_free(c->Acsr.sell); sell_free(c->AHcsr.sell); }
         c->err = why;
+        (void)maus_real_sync_matrix(c);
+        c->err = why;
+        return -1;
+    }
+    return maus_real_sync_matrix(c);            // the real sliced-ELL values follow the copy they mirror
+}
+
+int maus_spmm_get_method(maus_ctx* c) { return c ? c->spmm_method : -1; }
+
+int maus_real_set_method(maus_ctx* c, int method) {
+    if (!c) return -1;
+    if (method != 0 && method != 1) FAIL(c, "maus_real_set_method: method must be 0 (complex arithmetic) or 1 (real arithmetic where the rule holds)");
+    if (method == c->real_method) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    const int old = c->real_method;
+    c->real_method = method;
+    if (maus_real_sync_matrix(c) || maus_real_sync_rhs(c)) {
+        const std::string why = c->err;                        // device memory: back to the previous method, whose copies are smaller or none
+        c->real_method = old;
+        (void)maus_real_sync_matrix(c); (void)maus_real_sync_rhs(c);
+        c->err = why;
         return -1;
     }
     return 0;
 }
 
-int maus_spmm_get_method(maus_ctx* c) { return c ? c->spmm_method : -1; }
+int maus_real_get_method(maus_ctx* c) { return c ? c->real_method : -1; }
+
+int maus_real_values_flagged(const double* values_c128, int64_t count) {
+    if (count < 0 || (count > 0 && !values_c128)) return -1;
+    return maus_real_flagged(values_c128, (size_t)count) ? 1 : 0;
+}
+
+int maus_real_spmm(maus_ctx* c, const int* slots, int count) {
+    if (!c) return -1;
+    if (!c->csr || !c->Acsr.rval || !c->X) FAIL(c, "maus_real_spmm: needs method 1, a real square CSR matrix and a population");
+    if (count < 0 || (count > 0 && !slots)) FAIL(c, "maus_real_spmm: bad arguments");
+    if (count == 0) return 0;
+    maus_av_drop_all(c);
+    if (upload_slots(c, slots, count)) return -1;
+    const int n = c->rows;
+    const size_t rows = (sizeof(double) * (size_t)count * n + 255) / 256 * 256;
+    if (ensure_scratch(c, 2 * rows + sizeof(int) * count)) return -1;
+    double* R = (double*)c->scratch; double* Q = (double*)((char*)c->scratch + rows); int* ident = (int*)((char*)c->scratch + 2 * rows);
+    const dim3 grid((n + SP_BT - 1) / SP_BT, count);
+    hipLaunchKernelGGL(real_rows_in_kernel, grid, dim3(SP_BT), 0, c->st, c->X, c->ldp, c->d_slots, n, R, ident);
+    { ProfScope ps(c, KC_SPMM_REAL, 2.0 * count * c->Acsr.nnz, maus_spmm_operand_bytes_real(c->Acsr) * ((count + 7) / 8) + 16.0 * count * n);
+      maus_spmm_launch_real(c->st, c->Acsr, c->csr_sched, R, n, Q, n, ident, ident, count); }
+    hipLaunchKernelGGL(real_rows_out_kernel, grid, dim3(SP_BT), 0, c->st, Q, n, c->d_slots, c->Y, c->ldp);
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
 
 int maus_spmm_plan(int method, int fill_cap_percent, int rows, int64_t nnz, int64_t padded, int* kind_out) {
     if (!spmm_setting_ok(method, fill_cap_percent) || rows < 1 || nnz < 0 || padded < 0) return -1;

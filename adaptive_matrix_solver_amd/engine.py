@@ -304,6 +304,17 @@ def sparse_spmm_mode(mode):
     return mode
 
 
+REAL_ARITH_MODES = ("auto", "off", "on")
+
+
+def real_arith_mode(mode):
+    """The `real_arith` keyword: an explicit value, else MAUS_REAL_ARITH, else 'auto' (which means 'off')."""
+    mode = mode if mode is not None else os.environ.get("MAUS_REAL_ARITH", "auto")
+    if mode not in REAL_ARITH_MODES:
+        raise ValueError(f"real_arith must be one of {REAL_ARITH_MODES}, not {mode!r}")
+    return mode
+
+
 SPARSE_EIGSH_MODES = ("auto", "dense", "lanczos")
 
 
@@ -404,7 +415,8 @@ class DeviceEngine:
 
     def __init__(self, device: int = 0, pert_mode: str = "auto", gmres_compat: str = "rtol",
                  comm=None, ctx=None, eigh_mode: str = "auto", sparse_mode=None, sparse_direct=None, sparse_eigsh=None,
-                 sparse_gmres=None, few_rows=None, sparse_spmm=None, sparse_split=None, vector_draws=None):
+                 sparse_gmres=None, few_rows=None, sparse_spmm=None, sparse_split=None, vector_draws=None,
+                 real_arith=None):
         self.ctx = ctx if ctx is not None else _cabi.Context(device)
         cap_blas_threads()
         # Hermitian eigendecomposition (AMS:161), once per matrix: 'host' = scipy.linalg.eigh, the reference's call, (lambda, V)
@@ -451,6 +463,12 @@ class DeviceEngine:
         self.sparse_spmm = sparse_spmm_mode(sparse_spmm)
         if self.sparse_spmm == "sell":          # the only mode that touches the method: contexts without it keep working
             self.ctx.spmm_set_method(_cabi.SPMM_SELL)
+        # GMRES of a real sparse system (DESIGN §11 "GMRES in real arithmetic"): 'off' and 'auto' = complex arithmetic as ever;
+        # 'on' = a solve whose operand, b and shifts are all real runs on rows of doubles with a real copy of the operand
+        # (opt-in, 'auto' never picks it; the complex path's bits).  Everything else -- eigenvalue problems, a complex b, the
+        # direct fallback, the residual products -- runs as ever.  MAUS_REAL_ARITH sets the default.  Told to the context
+        # when a sparse matrix is bound, before the bind, which builds the real copies under it.
+        self.real_arith = real_arith_mode(real_arith)
         # sparse Hermitian shortcut (AMS:186-216): 'dense' = one scipy.linalg.eigh of A.toarray() per matrix, 'lanczos' =
         # thick-restart Lanczos on the CSR matrix on the device, 'auto' the first up to maus_lu_max_n() and the second above.
         # MAUS_SPARSE_EIGSH sets the default.
@@ -517,6 +535,8 @@ class DeviceEngine:
                 raise NotImplementedError("sparse problem matrices need sparse_mode='device' (or MAUS_SPARSE=device)")
             if comm is not None and comm.world > 1:
                 raise NotImplementedError("sharded runs (comm.world > 1) with a sparse matrix are not supported")
+            if self.real_arith == "on":         # the only mode that touches the method: contexts without it keep working
+                self.ctx.real_set_method(_cabi.REAL_ON)
             self.ctx.set_matrix_csr(A)
             if self.sparse_gmres == "wide":     # the only mode that touches the method: contexts without it keep working
                 self.ctx.gmres_set_method(1)

@@ -414,6 +414,40 @@ int maus_gmres_pert(maus_ctx* ctx, const int* slots, int count, const double* sh
 int maus_gmres_set_method(maus_ctx* ctx, int method);
 int maus_gmres_get_method(maus_ctx* ctx);
 int maus_gmres_kernel_for(maus_ctx* ctx, int n, int csr);
+/* Real arithmetic for maus_gmres on a real sparse system ("GMRES in real arithmetic").
+ *   maus_real_set_method   0 (the default): every solve runs in complex arithmetic, nothing else is allocated.
+ *                          1: a maus_gmres call runs on rows of n doubles, with a real copy of the operand values (8 bytes per
+ *                          nonzero; the indices are the complex operand's), of the diagonal and of b, when ALL of these hold:
+ *                          the matrix is CSR-bound and every stored value has an imaginary part of +0 or -0 (-0.0 counts as
+ *                          real; 5e-324 and NaN do not); rhs_mode is 1 and b is real in the same sense; every shift of the call
+ *                          has an imaginary part of +-0.  The flags are taken on the host when the arrays are bound.  Otherwise
+ *                          the call runs the complex path unchanged: maus_gmres_pert, dense matrices, population rows as
+ *                          right-hand sides, one complex shift among the call's.  Same algorithm, exits and status contract,
+ *                          both post schedules (maus_gmres_set_method) and both SpMM kernels (maus_spmm_set_method).  For finite
+ *                          data x, info, inner and status are those of the complex path bit for bit: every vector operation is
+ *                          the complex one without the terms that multiply an exact zero, in the same order, and the one-lane
+ *                          state machine is the complex one.  W[slot] receives x with imaginary part +0.0.  For non-finite data
+ *                          info and status are the same, and x may hold Inf where the complex path holds NaN (0 * Inf).  Kept
+ *                          across matrices; the real copies follow the bound matrix, b, and the SpMM method.
+ *   maus_real_get_method   the current method.
+ *   maus_real_plan         for the bound matrix and b: what a maus_gmres call with this rhs_mode and these `count` shifts does.
+ *                          out[0] 1 = the real path, 0 = the complex path; out[1] MAUS_REAL_OK or the first condition that
+ *                          fails; out[2] the post schedule as maus_gmres_kernel_for (-1: no square CSR matrix bound); out[3] the
+ *                          SpMM kernel as maus_spmm_kernel_for; out[4] how often a real copy was allocated on this context;
+ *                          out[5] the bytes of the real copies held now.  maus_gmres decides by the same function. */
+/* MAUS_REAL_NOT_CSR: no square CSR matrix is bound (a dense matrix, or none) */
+enum { MAUS_REAL_OK = 0, MAUS_REAL_METHOD_OFF = 1, MAUS_REAL_NOT_CSR = 2, MAUS_REAL_MATRIX_COMPLEX = 3, MAUS_REAL_RHS_ROWS = 4,
+       MAUS_REAL_RHS_COMPLEX = 5, MAUS_REAL_SHIFT_COMPLEX = 6 };
+int maus_real_set_method(maus_ctx* ctx, int method);
+int maus_real_get_method(maus_ctx* ctx);
+int maus_real_plan(maus_ctx* ctx, int rhs_mode, int count, const double* shift_c128, int64_t* out6);
+/* The flag of the rule on `count` complex values: 1 when every imaginary part has the bits of +0.0 or -0.0, else 0 (-1: bad
+ * arguments).  What maus_set_matrix_csr, maus_set_rhs and the shifts of a call are tested with; needs no context. */
+int maus_real_values_flagged(const double* values_c128, int64_t count);
+/* Y[slot] = A Re(X[slot]) by the SpMM kernels of the real path, the imaginary part +0.0: the product that a real solve runs on
+ * its Krylov vectors, on population rows (tests, tools/real_rates.py).  Needs the real copy of the operand (method 1, a square
+ * CSR matrix flagged real).  For rows with imaginary parts of +-0 the real part is that of the complex product, bit for bit. */
+int maus_real_spmm(maus_ctx* ctx, const int* slots, int count);
 /* Dense population products of at most 32 rows: A X of the Rayleigh quotient and the residuals (AMS:264-268, 295-301), the
  * score row conj(X) V of the Hermitian shortcut (AMS:165-175), the two products of the SVD power step (AMS:227-255) and the Gram
  * block of the converged candidates (AMS:432-451).  By default such a product runs ceil(N / 32) workgroups, each walking the whole
@@ -550,7 +584,10 @@ int maus_timer_stop(maus_ctx* ctx, float* ms_out);
  * 16 band solves by the wide method (bytes, an upper end: the band once per outer block of 64 columns over the full reach,
  *    LW once per column tile of the outer update, and the inner steps' bytes inside the block)
  * 17 the wide GMRES post step (maus_gmres_set_method; one bracket per tick around all its launches; flops 0, bytes 64 n per
- *    candidate and Gram-Schmidt column plus the form, tail, finish and new-cycle passes) */
+ *    candidate and Gram-Schmidt column plus the form, tail, finish and new-cycle passes)
+ * 19 the GMRES post step of the real path (maus_real_set_method), under either schedule: the brackets of class 6 / 17 with
+ *    half the bytes; 20 the CSR products of the real path (12 bytes per nonzero or padded slot, 16 n per row).  Classes 6, 11
+ *    and 17 count nothing of a call that runs real. */
 /* on = 1: event pairs around every launch of every class; on = 2: around the K>=256 zgemm launches only (class 0;
  * long kernels, so cheap enough for a timed region -- full bracketing costs 3-5 % of throughput; MAUS_PROF_STRIDE
  * can thin them out, each sample then stands for `stride` launches); 0: off */
