@@ -23,7 +23,7 @@ SYMBOLS = [
     "maus_svd_power_step", "maus_svd_power_propose", "maus_svd_commit", "maus_set_eigvecs", "maus_herm_match", "maus_herm_tridiag", "maus_herm_set_chunk", "maus_herm_chunk_plan", "maus_herm_release", "maus_herm_tridiag_eig", "maus_herm_tridiag_eigvals", "maus_herm_backtransform", "maus_get_eigvecs", "maus_gmres", "maus_gmres_pert", "maus_jacobi_check",
     "maus_profile_union_ms", "maus_gram", "maus_zgemm_host", "maus_lu_solve_host", "maus_timer_start", "maus_timer_stop",
     "maus_profile_enable", "maus_profile_read", "maus_sync", "maus_mt19937_jump",
-    "maus_lanczos_begin", "maus_lanczos_inject", "maus_lanczos_extend", "maus_lanczos_restart", "maus_lanczos_finish", "maus_herm_match_rows", "maus_get_ritz_rows",
+    "maus_lanczos_begin", "maus_lanczos_inject", "maus_lanczos_extend", "maus_lanczos_restart", "maus_lanczos_finish", "maus_herm_match_rows", "maus_get_ritz_rows", "maus_lanczos_get_basis",
     "maus_sparse_max_n", "maus_band_prepare", "maus_band_reserve", "maus_band_solve", "maus_band_lu_host", "maus_band_workspace_allocs",
     "maus_band_set_method", "maus_band_get_method", "maus_band_kernel_for", "maus_band_outer_nb", "maus_band_plan",
     "maus_band_set_split", "maus_band_get_split", "maus_band_split_plan",
@@ -150,6 +150,7 @@ def load_library():
         "maus_lanczos_finish": ([vp, vp, C.c_int, C.c_int], C.c_int),
         "maus_herm_match_rows": ([vp, vp, C.c_int, vp, vp], C.c_int),
         "maus_get_ritz_rows": ([vp, vp, C.c_int, C.c_int], C.c_int),
+        "maus_lanczos_get_basis": ([vp, C.c_int, C.c_int, vp], C.c_int),
         "maus_sparse_max_n": ([], C.c_int),
         "maus_band_prepare": ([vp, vp, C.c_int, ip, ip], C.c_int),
         "maus_band_reserve": ([vp, C.c_int, ip], C.c_int),
@@ -637,6 +638,12 @@ class Context:
         k = int(getattr(self, "_ritz_k", 0))
         out = np.empty((k, self.rows), dtype=np.complex128)
         self._ck(self.lib.maus_get_ritz_rows(self.h, _ptr(out), k, self.rows), "maus_get_ritz_rows")
+        return out
+
+    def lanczos_get_basis(self, j0, count):
+        """Rows j0 .. j0 + count - 1 of the live Lanczos basis, count x n (read-only; tests)."""
+        out = np.empty((max(int(count), 0), self.rows), dtype=np.complex128)
+        self._ck(self.lib.maus_lanczos_get_basis(self.h, int(j0), int(count), _ptr(out)), "maus_lanczos_get_basis")
         return out
 
     def gram(self, which, slots, length):

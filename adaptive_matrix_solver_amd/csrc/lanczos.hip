@@ -393,4 +393,13 @@ int maus_get_ritz_rows(maus_ctx* c, double* rows_c128_out, int k, int n) {
     return maus_stage_d2h(c, rows_c128_out, z.R, sizeof(c128) * (size_t)k * n, c->st);
 }
 
+int maus_lanczos_get_basis(maus_ctx* c, int j0, int count, double* rows_c128_out) {
+    if (!c) return -1;
+    LZ_NEED_BASIS(c, "maus_lanczos_get_basis");
+    MausLanczos& z = c->lz;
+    if (j0 < 0 || count < 1 || count > z.ncv + 1 - j0 || !rows_c128_out) FAIL(c, "maus_lanczos_get_basis: need 0 <= j0, 1 <= count, j0 + count <= ncv + 1");
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    return maus_stage_d2h(c, rows_c128_out, z.B + (long)j0 * z.n, sizeof(c128) * (size_t)count * z.n, c->st);
+}
+
 }  // extern "C"

@@ -349,7 +349,9 @@ int maus_herm_tridiag_eigvals(maus_ctx* ctx, const double* d, const double* e, i
  *                         not converge) frees the basis and keeps nothing.
  *   maus_herm_match_rows  AMS:197-202, maus_herm_match for the resident rows: scores vdot(X[slot], row j), the first largest
  *                         |score| as np.argmax, X[slot] <- row j / ||row j||.  idx_out[count], norm_out[count].
- *   maus_get_ritz_rows    the k resident rows on the host (rows_c128_out[k][n]; tests, reports). */
+ *   maus_get_ritz_rows    the k resident rows on the host (rows_c128_out[k][n]; tests, reports).
+ *   maus_lanczos_get_basis rows j0 .. j0 + count - 1 of the live basis on the host (rows_c128_out[count][n], 0 <= j0, 1 <= count,
+ *                         j0 + count <= ncv + 1; read-only, for tests); an error without a basis. */
 int maus_lanczos_begin(maus_ctx* ctx, const double* v0_c128, int ncv);
 int maus_lanczos_inject(maus_ctx* ctx, int j, const double* v_c128);
 int maus_lanczos_extend(maus_ctx* ctx, int j0, int j1, double tol_abs, double* alpha_out, double* beta_out);
@@ -357,6 +359,7 @@ int maus_lanczos_restart(maus_ctx* ctx, const double* s_real, int m, int keep);
 int maus_lanczos_finish(maus_ctx* ctx, const double* s_real, int m, int k);
 int maus_herm_match_rows(maus_ctx* ctx, const int* slots, int count, int32_t* idx_out, double* norm_out);
 int maus_get_ritz_rows(maus_ctx* ctx, double* rows_c128_out, int k, int n);
+int maus_lanczos_get_basis(maus_ctx* ctx, int j0, int count, double* rows_c128_out);
 
 /* Gram block of candidate vectors for the distinctness / redundancy tests      AMS:432-437, 443-451, 509-520:
  * out[i*count + j] = vdot(x_i, x_j) = sum_k conj(x_i[k]) x_j[k] over the first `len` entries of rows `slots`

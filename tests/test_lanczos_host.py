@@ -54,7 +54,8 @@ class FakeLanczosContext(FakeSparseContext):
         w = np.asarray(v, dtype=np.complex128).copy()
         for _h, w in self._orth(w, j):
             pass
-        self.B[j] = w / np.linalg.norm(w)
+        nrm = np.linalg.norm(w)
+        self.B[j] = w / nrm if nrm > 0.0 else 0.0                # the device leaves a zero row where the norm is not above 0
 
     def lanczos_extend(self, j0, j1, tol_abs):
         self.calls["extend"] += 1
@@ -84,8 +85,16 @@ class FakeLanczosContext(FakeSparseContext):
         m, k = S.shape
         self.R = None
         if k:
-            R = S.T @ self.B[:m]
-            self.R = R / np.linalg.norm(R, axis=1, keepdims=True)
+            # as the device: the recombination, then row by row classical Gram-Schmidt (twice) against the rows before it; a row
+            # of norm zero stays zero
+            self.B = S.T @ self.B[:m]
+            for q in range(k):
+                w = self.B[q]
+                for _h, w in self._orth(w, q):
+                    pass
+                nrm = np.linalg.norm(w)
+                self.B[q] = w / nrm if nrm > 0.0 else 0.0
+            self.R = self.B
         self.B = None
 
     def herm_match_rows(self, slots):
@@ -103,6 +112,10 @@ class FakeLanczosContext(FakeSparseContext):
 
     def get_ritz_rows(self):
         return self.R.copy()
+
+    def lanczos_get_basis(self, j0, count):
+        assert self.B is not None and 0 <= j0 and 1 <= count and j0 + count <= self.B.shape[0]
+        return self.B[j0:j0 + count].copy()
 
 
 def _engine(ctx=None, **kw):
