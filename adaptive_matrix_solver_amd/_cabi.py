@@ -27,6 +27,7 @@ SYMBOLS = [
     "maus_sparse_max_n", "maus_band_prepare", "maus_band_reserve", "maus_band_solve", "maus_band_lu_host", "maus_band_workspace_allocs",
     "maus_band_set_method", "maus_band_get_method", "maus_band_kernel_for", "maus_band_outer_nb", "maus_band_plan",
     "maus_band_set_split", "maus_band_get_split", "maus_band_split_plan",
+    "maus_band_set_real", "maus_band_get_real", "maus_band_real_plan", "maus_band_real_kinds",
     "maus_gmres_set_method", "maus_gmres_get_method", "maus_gmres_kernel_for",
     "maus_real_set_method", "maus_real_get_method", "maus_real_plan", "maus_real_spmm", "maus_real_values_flagged",
     "maus_few_rows_set_method", "maus_few_rows_get_method", "maus_few_rows_kernel_for", "maus_few_rows_plan", "maus_few_rows_workspace_allocs",
@@ -52,6 +53,11 @@ REAL_OFF, REAL_ON = 0, 1                             # maus_real_set_method
 # maus_real_plan: why a call runs complex (the first condition of the rule that fails), or REAL_OK
 REAL_OK, REAL_METHOD_OFF, REAL_NOT_CSR, REAL_MATRIX_COMPLEX, REAL_RHS_ROWS, REAL_RHS_COMPLEX, REAL_SHIFT_COMPLEX = range(7)
 KC_GMRES_REAL, KC_SPMM_REAL = 19, 20                 # the real path's post step and products: read as "gmres_real" / "spmm_real", behind the named classes
+BAND_REAL_OFF, BAND_REAL_ON = 0, 1                   # maus_band_set_real
+# maus_band_real_plan: why a band solve runs complex (the first condition of the rule that fails), or BAND_REAL_OK
+(BAND_REAL_OK, BAND_REAL_MODE_OFF, BAND_REAL_NOT_CSR, BAND_REAL_MATRIX_COMPLEX, BAND_REAL_RHS_ROWS, BAND_REAL_RHS_COMPLEX,
+ BAND_REAL_SHIFT_COMPLEX, BAND_REAL_NO_KERNELS) = range(8)
+KC_BAND_REAL = 21                                    # band solves of the real path: read as "band_real", behind the named classes
 FEW_ROWS_DEFAULT, FEW_ROWS_SPLITK = 0, 1             # maus_few_rows_set_method
 ZGEMM_ROWS, ZGEMM_LU = 0, 1                          # maus_zgemm_plan: the form ...
 LU_TILE_DEFAULT, LU_TILE_64X64, LU_TILE_128X64 = 0, 1, 2   # ... what MAUS_LU_TILE selects ...
@@ -187,6 +193,10 @@ def load_library():
         "maus_band_plan": ([C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p, i32p, C.POINTER(C.c_int64)], C.c_int),
         "maus_band_set_split": ([vp, C.c_int, C.c_int], C.c_int),
         "maus_band_get_split": ([vp, ip], C.c_int),
+        "maus_band_set_real": ([vp, C.c_int], C.c_int),
+        "maus_band_get_real": ([vp], C.c_int),
+        "maus_band_real_plan": ([vp, C.c_int, C.c_int, vp, vp], C.c_int),
+        "maus_band_real_kinds": ([C.c_int] * 6 + [vp], C.c_int),
         "maus_band_split_plan": ([C.c_int] * 5 + [i32p] * 6 + [C.POINTER(C.c_int64)], C.c_int),
         "maus_device_count": ([], C.c_int),
         "maus_comm_unique_id": ([C.c_char_p], C.c_int),
@@ -294,6 +304,7 @@ class Context:
         prof["band_split"] = self.profile_read_class(KC_BAND_SPLIT)
         prof["gmres_real"] = self.profile_read_class(KC_GMRES_REAL)
         prof["spmm_real"] = self.profile_read_class(KC_SPMM_REAL)
+        prof["band_real"] = self.profile_read_class(KC_BAND_REAL)
         return prof
 
     def lu_workspace_allocations(self) -> int:
@@ -745,6 +756,26 @@ class Context:
         self._ck(min(on, 0), "maus_band_get_split")
         return bool(on), int(m.value)
 
+    def band_set_real(self, mode):
+        """Real arithmetic for the band solves of a real sparse system (maus_band_set_real): BAND_REAL_OFF, or BAND_REAL_ON (a
+        band_solve() call whose CSR operand, b and shifts all have imaginary parts of +-0, with rhs_mode 1, under the column
+        kernel or the narrow method, with or without the split, runs on band storage of doubles; the complex path's x, ipiv
+        and status; csrc/band.hip).  Every other call runs complex as ever.  band_lu() follows it for arrays whose imaginary
+        parts are all +-0.  Independent of real_set_method(); kept across matrices."""
+        self._ck(self.lib.maus_band_set_real(self.h, int(mode)), "maus_band_set_real")
+
+    def band_real(self) -> int:
+        return int(self.lib.maus_band_get_real(self.h))
+
+    def band_real_plan(self, rhs_mode, shift) -> dict:
+        """What a band_solve() call with this rhs_mode and these shifts does on the bound matrix, ordering and b
+        (maus_band_real_plan, the function band_solve() itself decides by): 'real' (bool), 'why' (BAND_REAL_OK or the first
+        condition of the rule that fails), 'kind' (BAND_COLUMN ...; as band_kernel_for) and 'split' (bool)."""
+        sh = _c128(np.atleast_1d(np.asarray(shift, dtype=np.complex128)))
+        out = np.zeros(4, dtype=np.int32)
+        self._ck(self.lib.maus_band_real_plan(self.h, int(rhs_mode), int(sh.shape[0]), _ptr(sh), _ptr(out)), "maus_band_real_plan")
+        return {"real": bool(out[0]), "why": int(out[1]), "kind": int(out[2]), "split": bool(out[3])}
+
     def band_kernel_for(self, n, kl, ku):
         """(kernel, nb) that an (n, kl, ku) band runs under the current method: (BAND_COLUMN, 1), (BAND_BLOCKED, nb),
         (BAND_TILED, nb), (BAND_WIDE, nb of the inner steps) or (BAND_NARROW, 1)."""
@@ -956,6 +987,15 @@ def band_split_plan(method, n, kl, ku, part_len=0):
     if load_library().maus_band_split_plan(int(method), int(n), int(kl), int(ku), int(part_len), *[C.byref(x) for x in v], C.byref(per)) != 0:
         raise MausHipError(f"maus_band_split_plan: bad method, sizes or partition length ({method}, {n}, {kl}, {ku}, {part_len})")
     return (bool(v[0].value),) + tuple(int(x.value) for x in v[1:]) + (int(per.value),)
+
+
+def band_real_kinds(method, split, part_len, n, kl, ku):
+    """(real, kind, split takes) of an (n, kl, ku) band under `method`, the split switch and part_len (maus_band_real_kinds):
+    real says whether every kernel the solve would run has a real instantiation.  Needs neither a context nor a device."""
+    out = np.zeros(3, dtype=np.int32)
+    if load_library().maus_band_real_kinds(int(method), int(bool(split)), int(part_len), int(n), int(kl), int(ku), _ptr(out)) != 0:
+        raise MausHipError(f"maus_band_real_kinds: bad method, sizes or partition length ({method}, {split}, {part_len}, {n}, {kl}, {ku})")
+    return bool(out[0]), int(out[1]), bool(out[2])
 
 
 def few_rows_plan(method, slices, M, N, K, b_layout=1, conj_a=False, conj_b=False):

@@ -24,18 +24,31 @@
 // the tiled steps, then one rank-64 update on the MFMA pipe) for WID_MIN_KL <= kl <= WID_MAX_KL.
 // maus_band_set_method(ctx, 8) selects the narrow method (the column kernel's steps by one wave per matrix on an LDS ring of
 // column slots, the band streamed through it in chunks) for kl <= NAR_MAX_KL, kl + ku <= NAR_MAX_KV; the column kernel's bits.
+//
+// Real arithmetic (maus_band_set_real(ctx, 1), DESIGN §11 "Band solves in real arithmetic"): the build and scan kernels, the
+// column kernel, the narrow method and the split are one text over the scalar T, c128 or double.  A maus_band_solve call runs
+// on T = double when band_real_rule holds for it -- a real CSR matrix with an ordering, rhs_mode 1 with a real b, real shifts,
+// and a plan whose every kernel is one of those -- in the same workspace used as doubles; the T-dependent operations are the
+// overloads of common.h, each the complex operation without the terms that multiply an exact zero, so x, ipiv, info and status
+// are the complex path's values.  Population rows as right-hand sides (eigenvalue problems) and the blocked, tiled and wide
+// kernels have no real instantiation and run complex as ever.
 #include "ctx.h"
 #include <climits>
+#include <type_traits>
 #include <utility>
 
 namespace {
 
-struct BandArgs {
-    c128* ab; c128* x; int* ipiv; int* info; int* flags;
+// T: the scalar of the band storage and of the right-hand side, c128, or double on the real path (maus_band_set_real)
+template <class T>
+struct BandArgsT {
+    T* ab; T* x; int* ipiv; int* info; int* flags;
     int n, kl, ku, ldab;
 };
+using BandArgs = BandArgsT<c128>;
 
-__device__ __forceinline__ long bix(const BandArgs& a, int g) { return (long)g * a.ldab * a.n; }
+template <class T>
+__device__ __forceinline__ long bix(const BandArgsT<T>& a, int g) { return (long)g * a.ldab * a.n; }
 
 // ---- pieces that several kernels share: each rule is stated here, once ----------------------------------------------------
 // Pivot across the workgroup: from each thread's first maximum (best, bidx) the index of the first maximum of all, the lowest
@@ -97,9 +110,16 @@ __device__ __forceinline__ void solve_l11(c128* s_v, int ld, const c128* s_l11, 
 
 // H_k = A[perm][:, perm] - lam_k I + psi_k I into zeroed band storage, one thread per row of the permuted matrix; the
 // diagonal is (a - lam) + psi in NumPy's rounding order, with a = 0 where A stores none (as build_h_csr_kernel).  The permuted
-// right-hand side goes to x.  flags |= 1 on any non-finite value.
+// right-hand side goes to x.  flags |= 1 on any non-finite value.  T = double: the real parts of the same complex operands (the
+// rule of the real path has found every imaginary part +-0), the diagonal the real half of the complex one.
+__device__ __forceinline__ c128 band_diag(c128 v, c128 lam, double ps) {
+    return cmake(__dadd_rn(__dsub_rn(v.x, lam.x), ps), __dadd_rn(__dsub_rn(v.y, lam.y), 0.0));
+}
+__device__ __forceinline__ double band_diag(double v, double lam, double ps) { return __dadd_rn(__dsub_rn(v, lam), ps); }
+
+template <class T>
 __global__ void __launch_bounds__(256)
-band_build_csr_kernel(BandArgs a, const int* __restrict__ Ap, const int* __restrict__ Ai, const c128* __restrict__ Av,
+band_build_csr_kernel(BandArgsT<T> a, const int* __restrict__ Ap, const int* __restrict__ Ai, const c128* __restrict__ Av,
                       const int* __restrict__ perm, const int* __restrict__ iperm,
                       const c128* __restrict__ shift, const double* __restrict__ psi,
                       int rhs_mode, const c128* __restrict__ X, long ldx, const int* __restrict__ slots, const c128* __restrict__ bvec)
@@ -107,22 +127,22 @@ band_build_csr_kernel(BandArgs a, const int* __restrict__ Ap, const int* __restr
     const int i = blockIdx.x * 256 + threadIdx.x, g = blockIdx.y;
     bool bad = false;
     if (i < a.n) {
-        c128* ab = a.ab + bix(a, g);
+        T* ab = a.ab + bix(a, g);
         const int kv = a.kl + a.ku;
-        const c128 lam = shift[g];
+        const T lam = cnarrow<T>(shift[g]);
         const double ps = psi[g];
-        auto diag = [&](c128 v) { return cmake(__dadd_rn(__dsub_rn(v.x, lam.x), ps), __dadd_rn(__dsub_rn(v.y, lam.y), 0.0)); };
-        c128 h = diag(cmake(0.0, 0.0));
+        auto diag = [&](T v) { return band_diag(v, lam, ps); };
+        T h = diag(czero<T>());
         bad |= !cfinite(h);
         ab[kv + (long)i * a.ldab] = h;
         const int r = perm[i];
         for (int p = Ap[r]; p < Ap[r + 1]; ++p) {
             const int j = iperm[Ai[p]];
-            h = (j == i) ? diag(Av[p]) : Av[p];
+            h = (j == i) ? diag(cnarrow<T>(Av[p])) : cnarrow<T>(Av[p]);
             bad |= !cfinite(h);
             ab[kv + i - j + (long)j * a.ldab] = h;
         }
-        const c128 v = (rhs_mode == 0) ? X[(long)slots[g] * ldx + r] : bvec[r];
+        const T v = cnarrow<T>((rhs_mode == 0) ? X[(long)slots[g] * ldx + r] : bvec[r]);
         bad |= !cfinite(v);
         a.x[(long)g * a.n + i] = v;
     }
@@ -130,8 +150,9 @@ band_build_csr_kernel(BandArgs a, const int* __restrict__ Ap, const int* __restr
 }
 
 // band matrices and right-hand sides handed in by the caller (maus_band_lu_host): the non-finite scan only
+template <class T>
 __global__ void __launch_bounds__(256)
-band_scan_kernel(BandArgs a)
+band_scan_kernel(BandArgsT<T> a)
 {
     const int g = blockIdx.y;
     const long per = (long)a.ldab * a.n;
@@ -150,19 +171,19 @@ band_scan_kernel(BandArgs a)
 // zgbtf2 on matrix blockIdx.x with the forward half of zgbtrs folded in (see the file comment).  Column j of a step is not
 // written before every thread has read its pivot and its old top entry: the interchange inside column j is carried by the
 // multipliers' source (the row that receives the old top entry) and by one store of the pivot at the end of the step.
-template <int NT>
+template <class T, int NT>
 __global__ void __launch_bounds__(NT)
-band_factor_kernel(BandArgs a)
+band_factor_kernel(BandArgsT<T> a)
 {
     constexpr int NW = NT / 64;
     __shared__ double s_best[NW];
     __shared__ int s_idx[NW];
     const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = a.n, kl = a.kl, ku = a.ku, kv = kl + ku, ldab = a.ldab;
-    c128* ab = a.ab + bix(a, g);
-    c128* x = a.x + (long)g * n;
+    T* ab = a.ab + bix(a, g);
+    T* x = a.x + (long)g * n;
     int* ipiv = a.ipiv + (long)g * n;
-    auto at = [&](int r, int j) -> c128& { return ab[r + (long)j * ldab]; };
+    auto at = [&](int r, int j) -> T& { return ab[r + (long)j * ldab]; };
     // rows handled together in the update (a power of two from 64 to NT, so that it divides NT) and the column groups that
     // share them
     int RW = 64;
@@ -171,21 +192,21 @@ band_factor_kernel(BandArgs a)
     const int pr = tid % RW, cg = tid / RW;
     // the fill-in rows of columns ku + 1 .. min(kv, n) - 1 start at zero (zgbtf2)
     for (int j = ku + 1; j < min(kv, n); ++j)
-        for (int r = kv - j + tid; r < kl; r += NT) at(r, j) = cmake(0.0, 0.0);
+        for (int r = kv - j + tid; r < kl; r += NT) at(r, j) = czero<T>();
     int ju = 0, info = 0;
     for (int j = 0; j < n; ++j) {
-        if (j + kv < n) for (int r = tid; r < kl; r += NT) at(r, j + kv) = cmake(0.0, 0.0);
+        if (j + kv < n) for (int r = tid; r < kl; r += NT) at(r, j + kv) = czero<T>();
         const int km = min(kl, n - 1 - j);
         double best = -1.0; int bidx = INT_MAX;
         for (int p = tid; p <= km; p += NT) {
             const double v = cabs1(at(kv + p, j));
-            if (v > best) { best = v; bidx = p; }                        // NaN never wins (izamax)
+            if (v > best) { best = v; bidx = p; }                                                  // NaN never wins (izamax)
         }
         int jp = block_argmax<NW, false>(best, bidx, s_best, s_idx, lane, wave);
         if (jp == INT_MAX) jp = 0;
-        const c128 piv = at(kv + jp, j), top = at(kv, j);
-        if (tid == 0) ipiv[j] = j + jp + 1;                              // LAPACK's 1-based row
-        if (piv.x == 0.0 && piv.y == 0.0) {
+        const T piv = at(kv + jp, j), top = at(kv, j);
+        if (tid == 0) ipiv[j] = j + jp + 1;                             // LAPACK's 1-based row
+        if (ciszero(piv)) {
             if (info == 0) info = j + 1;
             __syncthreads();                                             // s_best / s_idx are written again by the next column
             continue;
@@ -193,26 +214,26 @@ band_factor_kernel(BandArgs a)
         ju = max(ju, min(j + ku + jp, n - 1));
         if (jp != 0) {
             for (int c = j + 1 + tid; c <= ju; c += NT) {
-                const c128 t = at(kv + jp + j - c, c);
+                const T t = at(kv + jp + j - c, c);
                 at(kv + jp + j - c, c) = at(kv + j - c, c);
                 at(kv + j - c, c) = t;
             }
-            if (tid == 0) { const c128 t = x[j + jp]; x[j + jp] = x[j]; x[j] = t; }
+            if (tid == 0) { const T t = x[j + jp]; x[j + jp] = x[j]; x[j] = t; }
         }
         __syncthreads();
         if (km > 0) {
-            const c128 r = crecip(piv);
-            const c128 xj = x[j];
+            const T r = crecip(piv);
+            const T xj = x[j];
             if (cg == 0)
                 for (int p = pr; p < km; p += RW) {
-                    const c128 l = cmul(p + 1 == jp ? top : at(kv + 1 + p, j), r);
+                    const T l = cmul(p + 1 == jp ? top : at(kv + 1 + p, j), r);
                     at(kv + 1 + p, j) = l;
                     cfms(x[j + 1 + p], l, xj);
                 }
             __syncthreads();
             const int ncol = ju - j;
             for (int p = pr; p < km; p += RW) {
-                const c128 l = at(kv + 1 + p, j);
+                const T l = at(kv + 1 + p, j);
                 for (int c = 1 + cg; c <= ncol; c += CG) cfms(at(kv + 1 + p - c, j + c), l, at(kv - c, j + c));
             }
         }
@@ -225,23 +246,23 @@ band_factor_kernel(BandArgs a)
 // U x = y (ztbsv, upper, non-unit, k = kl + ku) on matrix blockIdx.x; x[j] goes to out[perm[j]] (out[j] without perm) once it
 // is final.  Every thread forms x[j] itself (the same division of the same operands), so one barrier per column suffices.
 // flags |= 2 on a non-finite result.
-template <int NT>
+template <class T, int NT>
 __global__ void __launch_bounds__(NT)
-band_back_kernel(BandArgs a, c128* __restrict__ out, long ldo, const int* __restrict__ slots, const int* __restrict__ perm)
+band_back_kernel(BandArgsT<T> a, c128* __restrict__ out, long ldo, const int* __restrict__ slots, const int* __restrict__ perm)
 {
     const int g = blockIdx.x, tid = threadIdx.x;
     const int n = a.n, kv = a.kl + a.ku, ldab = a.ldab;
-    const c128* ab = a.ab + bix(a, g);
-    c128* x = a.x + (long)g * n;
+    const T* ab = a.ab + bix(a, g);
+    T* x = a.x + (long)g * n;
     c128* o = out + (slots ? (long)slots[g] : (long)g) * ldo;
     bool bad = false;
     for (int j = n - 1; j >= 0; --j) {
-        c128 xj = x[j];
-        if (xj.x != 0.0 || xj.y != 0.0) {
+        T xj = x[j];
+        if (!ciszero(xj)) {
             xj = cdiv(xj, ab[kv + (long)j * ldab]);
             for (int i = max(0, j - kv) + tid; i < j; i += NT) cfms(x[i], xj, ab[kv + i - j + (long)j * ldab]);
         }
-        if (tid == 0) { o[perm ? perm[j] : j] = xj; bad |= !cfinite(xj); }
+        if (tid == 0) { o[perm ? perm[j] : j] = cwiden(xj); bad |= !cfinite(xj); }
         __syncthreads();
     }
     if (tid == 0 && bad) atomicOr(&a.flags[g], 2);
@@ -327,7 +348,7 @@ band_panel_kernel(BandArgs a, BlkArgs w, int j0)
                 const int r = tid + m * NT;
                 if (r >= jj && r <= jj + km) {
                     const double v = cabs1(row[m][jj]);
-                    if (v > best) { best = v; bidx = r; }               // NaN never wins (izamax)
+                    if (v > best) { best = v; bidx = r; }                                          // NaN never wins (izamax)
                 }
             });
             int pr = block_argmax<NW, true>(best, bidx, s_best, s_idx, lane, wave);
@@ -987,38 +1008,38 @@ __device__ __forceinline__ void nar_chunk_map(int (&loff)[NAR_EL], int lane, int
     }
 }
 
-template <int RW>
+template <class T, int RW>
 __global__ void __launch_bounds__(64)
-band_narrow_factor_kernel(BandArgs a)
+band_narrow_factor_kernel(BandArgsT<T> a)
 {
     constexpr int CG = 64 / RW;
-    __shared__ c128 s_ab[NAR_SLOTS * NAR_LD];
-    __shared__ c128 s_x[NAR_SLOTS];
+    __shared__ T s_ab[NAR_SLOTS * NAR_LD];
+    __shared__ T s_x[NAR_SLOTS];
     const int g = blockIdx.x, lane = threadIdx.x;
     const int n = a.n, kl = a.kl, ku = a.ku, kv = kl + ku, ldab = a.ldab;
-    c128* ab = a.ab + bix(a, g);
-    c128* x = a.x + (long)g * n;
+    T* ab = a.ab + bix(a, g);
+    T* x = a.x + (long)g * n;
     int* ipiv = a.ipiv + (long)g * n;
     const long end = (long)ldab * n;
     int loff[NAR_EL];
     nar_chunk_map(loff, lane, ldab);
-    auto S = [&](int r, int c) -> c128& { return s_ab[(c & (NAR_SLOTS - 1)) * NAR_LD + r]; };
+    auto S = [&](int r, int c) -> T& { return s_ab[(c & (NAR_SLOTS - 1)) * NAR_LD + r]; };
     // columns c0 .. c0 + 15 and their x (c0 a multiple of 16; nothing is read at or past column n)
-    auto load = [&](int c0, c128 (&v)[NAR_EL], c128& vx) {
+    auto load = [&](int c0, T (&v)[NAR_EL], T& vx) {
         const long e0 = (long)c0 * ldab + lane;
 #pragma unroll
-        for (int k = 0; k < NAR_EL; ++k) v[k] = (loff[k] >= 0 && e0 + 64 * k < end) ? ab[e0 + 64 * k] : cmake(0.0, 0.0);
-        vx = (lane < NAR_CH && c0 + lane < n) ? x[c0 + lane] : cmake(0.0, 0.0);
+        for (int k = 0; k < NAR_EL; ++k) v[k] = (loff[k] >= 0 && e0 + 64 * k < end) ? ab[e0 + 64 * k] : czero<T>();
+        vx = (lane < NAR_CH && c0 + lane < n) ? x[c0 + lane] : czero<T>();
     };
     // the fill-in rows of column c, kv - c <= r < kl, start at zero (zgbtf2: columns ku + 1 .. kv - 1 before the first step,
     // column j + kv at step j -- in both cases before a pivot row reaches the column)
-    auto enter = [&](int c0, const c128 (&v)[NAR_EL], const c128& vx) {
+    auto enter = [&](int c0, const T (&v)[NAR_EL], const T& vx) {
         const int s0 = (c0 & (NAR_SLOTS - 1)) * NAR_LD;
 #pragma unroll
         for (int k = 0; k < NAR_EL; ++k)
             if (loff[k] >= 0) {
                 const int r = loff[k] % NAR_LD, c = c0 + loff[k] / NAR_LD;
-                s_ab[s0 + loff[k]] = (r < kl && r + c >= kv) ? cmake(0.0, 0.0) : v[k];
+                s_ab[s0 + loff[k]] = (r < kl && r + c >= kv) ? czero<T>() : v[k];
             }
         if (lane < NAR_CH) s_x[(c0 & (NAR_SLOTS - 1)) + lane] = vx;
     };
@@ -1030,7 +1051,7 @@ band_narrow_factor_kernel(BandArgs a)
             if (loff[k] >= 0 && e0 + 64 * k < end) ab[e0 + 64 * k] = s_ab[s0 + loff[k]];
         if (lane < NAR_CH && c0 + lane < n) { x[c0 + lane] = s_x[(c0 & (NAR_SLOTS - 1)) + lane]; ipiv[c0 + lane] = pv; }
     };
-    c128 pre[NAR_EL], prex;
+    T pre[NAR_EL], prex;
     load(0, pre, prex); enter(0, pre, prex);
     load(NAR_CH, pre, prex); enter(NAR_CH, pre, prex);
     load(2 * NAR_CH, pre, prex);
@@ -1043,18 +1064,18 @@ band_narrow_factor_kernel(BandArgs a)
         const int je = min(j0 + NAR_CH, n);
         for (int j = j0; j < je; ++j) {
             const int km = min(kl, n - 1 - j);
-            const c128 cand = lane <= km ? S(kv + lane, j) : cmake(0.0, 0.0);
+            const T cand = lane <= km ? S(kv + lane, j) : czero<T>();
             double best = -1.0; int bidx = INT_MAX;
             if (lane <= km) {
                 const double v = cabs1(cand);
-                if (v > best) { best = v; bidx = lane; }                 // NaN never wins (izamax)
+                if (v > best) { best = v; bidx = lane; }                                           // NaN never wins (izamax)
             }
             wave_argmax(best, bidx);
             int jp = __builtin_amdgcn_readfirstlane(bidx);
             if (jp == INT_MAX) jp = 0;
-            const c128 piv = lane_bcast(cand, jp), top = lane_bcast(cand, 0);
+            const T piv = lane_bcast(cand, jp), top = lane_bcast(cand, 0);
             if (lane == (j & (NAR_CH - 1))) pv = j + jp + 1;            // LAPACK's 1-based row
-            if (piv.x == 0.0 && piv.y == 0.0) {
+            if (ciszero(piv)) {
                 if (info == 0) info = j + 1;
                 continue;
             }
@@ -1062,24 +1083,24 @@ band_narrow_factor_kernel(BandArgs a)
             if (jp != 0) {
                 const int c = j + 1 + lane;
                 if (c <= ju) {
-                    const c128 t = S(kv + jp + j - c, c);
+                    const T t = S(kv + jp + j - c, c);
                     S(kv + jp + j - c, c) = S(kv + j - c, c);
                     S(kv + j - c, c) = t;
                 }
                 if (lane == 0) {
-                    c128& xa = s_x[(j + jp) & (NAR_SLOTS - 1)];
-                    c128& xb = s_x[j & (NAR_SLOTS - 1)];
-                    const c128 t = xa; xa = xb; xb = t;
+                    T& xa = s_x[(j + jp) & (NAR_SLOTS - 1)];
+                    T& xb = s_x[j & (NAR_SLOTS - 1)];
+                    const T t = xa; xa = xb; xb = t;
                 }
                 lds_barrier();
             }
             if (km > 0) {
-                const c128 r = crecip(piv);
-                const c128 xj = s_x[j & (NAR_SLOTS - 1)];
+                const T r = crecip(piv);
+                const T xj = s_x[j & (NAR_SLOTS - 1)];
                 const int p = lane % RW, cg = lane / RW;
                 if (p < km) {
-                    const c128 own = S(kv + 1 + p, j);
-                    const c128 l = cmul(p + 1 == jp ? top : own, r);
+                    const T own = S(kv + 1 + p, j);
+                    const T l = cmul(p + 1 == jp ? top : own, r);
                     if (cg == 0) {
                         S(kv + 1 + p, j) = l;
                         cfms(s_x[(j + 1 + p) & (NAR_SLOTS - 1)], l, xj);
@@ -1100,28 +1121,29 @@ band_narrow_factor_kernel(BandArgs a)
 // columns of the chunk at hand sit in LDS, the chunk below it is in flight in registers; x lives in a ring of NAR_SLOTS
 // entries (a step reaches kv entries up, so the chunk at hand and the two below it are resident, the third below in flight).
 // x[j] goes to out[perm[j]] a chunk at a time; flags |= 2 on a non-finite result.
+template <class T>
 __global__ void __launch_bounds__(64)
-band_narrow_back_kernel(BandArgs a, c128* __restrict__ out, long ldo, const int* __restrict__ slots, const int* __restrict__ perm)
+band_narrow_back_kernel(BandArgsT<T> a, c128* __restrict__ out, long ldo, const int* __restrict__ slots, const int* __restrict__ perm)
 {
-    __shared__ c128 s_u[NAR_CH * NAR_LD];
-    __shared__ c128 s_x[NAR_SLOTS];
+    __shared__ T s_u[NAR_CH * NAR_LD];
+    __shared__ T s_x[NAR_SLOTS];
     const int g = blockIdx.x, lane = threadIdx.x;
     const int n = a.n, kv = a.kl + a.ku, ldab = a.ldab;
-    const c128* ab = a.ab + bix(a, g);
-    const c128* x = a.x + (long)g * n;
+    const T* ab = a.ab + bix(a, g);
+    const T* x = a.x + (long)g * n;
     c128* o = out + (slots ? (long)slots[g] : (long)g) * ldo;
     const long end = (long)ldab * n;
     int loff[NAR_EL];
     nar_chunk_map(loff, lane, ldab);
     // chunk k of the band (columns 16 k ..) and chunk k - 2 of x; nothing is read below index 0 or at or past n
-    auto load = [&](int k, c128 (&v)[NAR_EL], c128& vx) {
+    auto load = [&](int k, T (&v)[NAR_EL], T& vx) {
         const long e0 = (long)k * NAR_CH * ldab + lane;
 #pragma unroll
-        for (int q = 0; q < NAR_EL; ++q) v[q] = (k >= 0 && loff[q] >= 0 && e0 + 64 * q < end) ? ab[e0 + 64 * q] : cmake(0.0, 0.0);
+        for (int q = 0; q < NAR_EL; ++q) v[q] = (k >= 0 && loff[q] >= 0 && e0 + 64 * q < end) ? ab[e0 + 64 * q] : czero<T>();
         const int i = (k - 2) * NAR_CH + lane;
-        vx = (lane < NAR_CH && i >= 0 && i < n) ? x[i] : cmake(0.0, 0.0);
+        vx = (lane < NAR_CH && i >= 0 && i < n) ? x[i] : czero<T>();
     };
-    auto enter = [&](int k, const c128 (&v)[NAR_EL], const c128& vx) {
+    auto enter = [&](int k, const T (&v)[NAR_EL], const T& vx) {
 #pragma unroll
         for (int q = 0; q < NAR_EL; ++q) if (loff[q] >= 0) s_u[loff[q]] = v[q];
         if (lane < NAR_CH && k >= 2) s_x[((k - 2) * NAR_CH + lane) & (NAR_SLOTS - 1)] = vx;
@@ -1131,7 +1153,7 @@ band_narrow_back_kernel(BandArgs a, c128* __restrict__ out, long ldo, const int*
         const int i = (K - 1) * NAR_CH + lane;                          // x of the last two chunks
         if (lane < 2 * NAR_CH && i >= 0 && i < n) s_x[i & (NAR_SLOTS - 1)] = x[i];
     }
-    c128 pre[NAR_EL], prex;
+    T pre[NAR_EL], prex;
     load(K, pre, prex);
     bool bad = false;
     for (int k = K; k >= 0; --k) {
@@ -1139,12 +1161,12 @@ band_narrow_back_kernel(BandArgs a, c128* __restrict__ out, long ldo, const int*
         load(k - 1, pre, prex);
         const int jo = k * NAR_CH + lane;                               // the entry of x this lane writes out
         const int po = (lane < NAR_CH && jo < n) ? (perm ? perm[jo] : jo) : 0;
-        c128 xo = cmake(0.0, 0.0);
+        T xo = czero<T>();
         lds_barrier();
         for (int j = min(k * NAR_CH + NAR_CH, n) - 1; j >= k * NAR_CH; --j) {
-            const c128* u = s_u + (j & (NAR_CH - 1)) * NAR_LD + kv;     // the diagonal entry of column j
-            c128 xj = s_x[j & (NAR_SLOTS - 1)];
-            if (xj.x != 0.0 || xj.y != 0.0) {
+            const T* u = s_u + (j & (NAR_CH - 1)) * NAR_LD + kv;        // the diagonal entry of column j
+            T xj = s_x[j & (NAR_SLOTS - 1)];
+            if (!ciszero(xj)) {
                 xj = cdiv(xj, u[0]);
                 const int i = j - 1 - lane;
                 if (lane < kv && i >= 0) cfms(s_x[i & (NAR_SLOTS - 1)], xj, u[i - j]);
@@ -1152,18 +1174,19 @@ band_narrow_back_kernel(BandArgs a, c128* __restrict__ out, long ldo, const int*
             if (lane == (j & (NAR_CH - 1))) xo = xj;
             lds_barrier();
         }
-        if (lane < NAR_CH && jo < n) { o[po] = xo; bad |= !cfinite(xo); }
+        if (lane < NAR_CH && jo < n) { o[po] = cwiden(xo); bad |= !cfinite(xo); }
     }
     if (__any(bad) && lane == 0) atomicOr(&a.flags[g], 2);
 }
 
-void launch_narrow(const BandArgs& a, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
-    if (a.kl <= 1) hipLaunchKernelGGL((band_narrow_factor_kernel<1>), dim3(G), dim3(64), 0, st, a);
-    else if (a.kl <= 2) hipLaunchKernelGGL((band_narrow_factor_kernel<2>), dim3(G), dim3(64), 0, st, a);
-    else if (a.kl <= 4) hipLaunchKernelGGL((band_narrow_factor_kernel<4>), dim3(G), dim3(64), 0, st, a);
-    else if (a.kl <= 8) hipLaunchKernelGGL((band_narrow_factor_kernel<8>), dim3(G), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((band_narrow_factor_kernel<16>), dim3(G), dim3(64), 0, st, a);
-    hipLaunchKernelGGL(band_narrow_back_kernel, dim3(G), dim3(64), 0, st, a, out, ldo, slots, perm);
+template <class T>
+void launch_narrow(const BandArgsT<T>& a, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
+    if (a.kl <= 1) hipLaunchKernelGGL((band_narrow_factor_kernel<T, 1>), dim3(G), dim3(64), 0, st, a);
+    else if (a.kl <= 2) hipLaunchKernelGGL((band_narrow_factor_kernel<T, 2>), dim3(G), dim3(64), 0, st, a);
+    else if (a.kl <= 4) hipLaunchKernelGGL((band_narrow_factor_kernel<T, 4>), dim3(G), dim3(64), 0, st, a);
+    else if (a.kl <= 8) hipLaunchKernelGGL((band_narrow_factor_kernel<T, 8>), dim3(G), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL((band_narrow_factor_kernel<T, 16>), dim3(G), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(band_narrow_back_kernel<T>, dim3(G), dim3(64), 0, st, a, out, ldo, slots, perm);
 }
 
 // ---- the split method (maus_band_set_split(ctx, 1, part_len), DESIGN §11 "The split method") -----------------------------
@@ -1188,7 +1211,8 @@ void launch_narrow(const BandArgs& a, int G, hipStream_t st, c128* out, long ldo
 //            (one fixed order), and the x of the band columns move up one lane per step.
 // Every choice is a function of (n, kl, ku, part_len) alone, and a group works on its own partition only: a system's bits do
 // not depend on the batch or the chunking.
-hipError_t launch_solve(const BandPlan& plan, const BandArgs& a, const BlkArgs& w, int G, hipStream_t st, c128* out, long ldo,
+template <class T>
+hipError_t launch_solve(const BandPlan& plan, const BandArgsT<T>& a, const BlkArgs& w, int G, hipStream_t st, c128* out, long ldo,
                         const int* slots, const int* perm);
 size_t band_per_solve(const BandPlan& plan, int n, int kl, int ku);
 double band_flops(int n, int kl, int ku, int G);
@@ -1237,16 +1261,18 @@ bool split_plan(int method, int mode, int part_len, int n, int kl, int ku, Split
 
 // the split's arrays for G solves: pr[G][n][2 w + 2], the reduced system r (its x: the right-hand side), its solution
 // xs[G][n_red], the local phase's info linfo[G] and the reduced plan's panel
-struct SplitWs { c128* pr; BandArgs r; c128* xs; int* linfo; BlkArgs rw; };
+template <class T>
+struct SplitWsT { T* pr; BandArgsT<T> r; c128* xs; int* linfo; BlkArgs rw; };
 
-size_t split_carve(const SplitPlan& sp, int n, int G, char* base, SplitWs* ws) {
+template <class T>
+size_t split_carve(const SplitPlan& sp, int n, int G, char* base, SplitWsT<T>* ws) {
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return base + o; };
-    SplitWs s;
+    SplitWsT<T> s;
     s.r.n = sp.n_red; s.r.kl = sp.kl_red; s.r.ku = sp.ku_red; s.r.ldab = 2 * sp.kl_red + sp.ku_red + 1;
-    s.pr = (c128*)take(sizeof(c128) * (size_t)n * (2 * sp.w + 2) * G);
-    s.r.ab = (c128*)take(sizeof(c128) * (size_t)s.r.ldab * sp.n_red * G);
-    s.r.x = (c128*)take(sizeof(c128) * (size_t)sp.n_red * G);
+    s.pr = (T*)take(sizeof(T) * (size_t)n * (2 * sp.w + 2) * G);
+    s.r.ab = (T*)take(sizeof(T) * (size_t)s.r.ldab * sp.n_red * G);
+    s.r.x = (T*)take(sizeof(T) * (size_t)sp.n_red * G);
     s.xs = (c128*)take(sizeof(c128) * (size_t)sp.n_red * G);
     s.r.ipiv = (int*)take(sizeof(int) * (size_t)sp.n_red * G);
     s.r.info = (int*)take(sizeof(int) * G);
@@ -1259,7 +1285,16 @@ size_t split_carve(const SplitPlan& sp, int n, int G, char* base, SplitWs* ws) {
     return off;
 }
 
-struct SplitArgs { c128* pr; int* linfo; int w, m, p; };
+template <class T>
+struct SplitArgsT { T* pr; int* linfo; int w, m, p; };
+
+// the lane traffic of the split's back substitution, per component
+__device__ __forceinline__ void lane_xor_add(c128& t, int off) { t.x += __shfl_xor(t.x, off, 64); t.y += __shfl_xor(t.y, off, 64); }
+__device__ __forceinline__ void lane_xor_add(double& t, int off) { t += __shfl_xor(t, off, 64); }
+__device__ __forceinline__ c128 lane_shfl(c128 v, int l) { return cmake(__shfl(v.x, l, 64), __shfl(v.y, l, 64)); }
+__device__ __forceinline__ double lane_shfl(double v, int l) { return __shfl(v, l, 64); }
+__device__ __forceinline__ c128 lane_shfl_up1(c128 v) { return cmake(__shfl_up(v.x, 1, 64), __shfl_up(v.y, 1, 64)); }
+__device__ __forceinline__ double lane_shfl_up1(double v) { return __shfl_up(v, 1, 64); }
 
 // interior columns of partition i, and the longest interior among the NG partitions of a wave (the wave's trip count)
 __device__ __forceinline__ int split_ni(int p, int m, int w, int n, int i) { return i < p - 1 ? m - w : n - (p - 1) * m; }
@@ -1270,39 +1305,39 @@ __device__ __forceinline__ int split_trips(int p, int m, int w, int n, int i0) {
     return T;
 }
 
-template <int GS>
+template <class T, int GS>
 __global__ void __launch_bounds__(64)
-band_split_local_kernel(BandArgs a, BandArgs r, SplitArgs s)
+band_split_local_kernel(BandArgsT<T> a, BandArgsT<T> r, SplitArgsT<T> s)
 {
     constexpr int NG = 64 / GS, RS = GS / 2;
-    __shared__ c128 s_win[NG * RS * GS];
-    __shared__ c128 s_l[NG * RS];
+    __shared__ T s_win[NG * RS * GS];
+    __shared__ T s_l[NG * RS];
     __shared__ int s_row[NG * RS];
     __shared__ int s_pv[NG];
     const int g = blockIdx.y, grp = threadIdx.x / GS, l = threadIdx.x % GS;
     const int i = blockIdx.x * NG + grp;
     const bool act = i < s.p;
     const int n = a.n, kl = a.kl, ku = a.ku, w = s.w, ldab = a.ldab, m = s.m;
-    const c128* ab = a.ab + bix(a, g);
-    const c128* x = a.x + (long)g * n;
+    const T* ab = a.ab + bix(a, g);
+    const T* x = a.x + (long)g * n;
     int* ipiv = a.ipiv + (long)g * n;
-    c128* pr = s.pr + (long)g * n * (2 * w + 2);
+    T* pr = s.pr + (long)g * n * (2 * w + 2);
     const bool hasL = act && i > 0, hasR = act && i < s.p - 1;
     const int a0 = act ? i * m : 0, ni = act ? split_ni(s.p, m, w, n, i) : 0;
     const int rs0 = max(a0 - ku, 0), rend = hasR ? a0 + m - ku : n;     // R_i = [rs0, rend)
-    const int T = split_trips<NG>(s.p, m, w, n, blockIdx.x * NG);
+    const int trips = split_trips<NG>(s.p, m, w, n, blockIdx.x * NG);
     const bool bandl = l >= w && l <= 2 * w;
-    c128* S = s_win + (long)grp * RS * GS + l;                          // this lane's column: row slot q at S[q * GS]
-    c128* sl = s_l + grp * RS;
+    T* S = s_win + (long)grp * RS * GS + l;                             // this lane's column: row slot q at S[q * GS]
+    T* sl = s_l + grp * RS;
     int* srow = s_row + grp * RS;
-    auto elem = [&](int rr, int cc) -> c128 {
-        return (cc >= 0 && cc < n && rr - cc <= kl && cc - rr <= ku) ? ab[w + rr - cc + (long)cc * ldab] : cmake(0.0, 0.0);
+    auto elem = [&](int rr, int cc) -> T {
+        return (cc >= 0 && cc < n && rr - cc <= kl && cc - rr <= ku) ? ab[w + rr - cc + (long)cc * ldab] : czero<T>();
     };
     // this lane's element of row rr while it owns band column mc
-    auto rowval = [&](int rr, int mc) -> c128 {
-        if (l < w) return hasL ? elem(rr, a0 - w + l) : cmake(0.0, 0.0);
+    auto rowval = [&](int rr, int mc) -> T {
+        if (l < w) return hasL ? elem(rr, a0 - w + l) : czero<T>();
         if (l <= 2 * w) return elem(rr, mc);
-        return l == 2 * w + 1 ? x[rr] : cmake(0.0, 0.0);
+        return l == 2 * w + 1 ? x[rr] : czero<T>();
     };
     int mycol = 0;
     if (bandl) { const int sg = l - w, am = a0 % (w + 1); mycol = a0 + (sg - am + w + 1) % (w + 1); }
@@ -1311,19 +1346,19 @@ band_split_local_kernel(BandArgs a, BandArgs r, SplitArgs s)
     unsigned live = 0;
     int fs = ninit;                                                     // the free slot the next row enters
     for (int q = 0; q <= w; ++q) {
-        S[q * GS] = q < ninit ? rowval(rs0 + q, mycol) : cmake(0.0, 0.0);
+        S[q * GS] = q < ninit ? rowval(rs0 + q, mycol) : czero<T>();
         if (l == 0) srow[q] = q < ninit ? rs0 + q : INT_MAX;
         if (q < ninit) live |= 1u << q;
     }
-    c128 inc = (ni > 0 && a0 + kl < rend) ? rowval(a0 + kl, mycol) : cmake(0.0, 0.0);   // the row that enters at the first step
-    for (int j = 0; j < T; ++j) {
+    T inc = (ni > 0 && a0 + kl < rend) ? rowval(a0 + kl, mycol) : czero<T>();           // the row that enters at the first step
+    for (int j = 0; j < trips; ++j) {
         const bool on = j < ni;
         const int c = a0 + j;
         const bool pl = on && bandl && mycol == c;                      // the lane of the pivot column
         if (on) {
             const int re = c + kl;
             if (re < rend) { S[fs * GS] = inc; if (l == 0) srow[fs] = re; live |= 1u << fs; }
-            inc = (j + 1 < ni && re + 1 < rend) ? rowval(re + 1, pl ? c + w + 1 : mycol) : cmake(0.0, 0.0);
+            inc = (j + 1 < ni && re + 1 < rend) ? rowval(re + 1, pl ? c + w + 1 : mycol) : czero<T>();
         }
         lds_barrier();
         if (pl) {
@@ -1344,28 +1379,28 @@ band_split_local_kernel(BandArgs a, BandArgs r, SplitArgs s)
                         if (d < fd || (d == fd && row < brow)) { fd = d; bs = q; brow = row; }
                     }
             }
-            const c128 piv = S[bs * GS];
-            const bool zp = piv.x == 0.0 && piv.y == 0.0;
+            const T piv = S[bs * GS];
+            const bool zp = ciszero(piv);
             if (zp) atomicMin(&s.linfo[g], c + 1);
-            const c128 rc = zp ? cmake(0.0, 0.0) : crecip(piv);
+            const T rc = zp ? czero<T>() : crecip(piv);
             for (int q = 0; q <= w; ++q) {
                 const bool upd = (live >> q & 1) && q != bs;
-                sl[q] = (upd && !zp) ? cmul(S[q * GS], rc) : cmake(0.0, 0.0);
-                if (q != bs) S[q * GS] = cmake(0.0, 0.0);                          // column c is eliminated: the slot becomes column c + w + 1
+                sl[q] = (upd && !zp) ? cmul(S[q * GS], rc) : czero<T>();
+                if (q != bs) S[q * GS] = czero<T>();                               // column c is eliminated: the slot becomes column c + w + 1
             }
             s_pv[grp] = bs;
         }
         lds_barrier();
         if (on) {
             const int bs = s_pv[grp];
-            const c128 u = S[bs * GS];
+            const T u = S[bs * GS];
             if (l <= 2 * w + 1) pr[(long)c * (2 * w + 2) + (bandl ? w + mycol - c : l)] = u;
             if (l == 0) ipiv[c] = srow[bs] + 1;                         // 1-based row of H, as LAPACK counts
             live &= ~(1u << bs);
             if (!pl)
                 for (int q = 0; q <= w; ++q)
-                    if (live >> q & 1) { c128 v = S[q * GS]; cfms(v, sl[q], u); S[q * GS] = v; }
-            S[bs * GS] = cmake(0.0, 0.0);
+                    if (live >> q & 1) { T v = S[q * GS]; cfms(v, sl[q], u); S[q * GS] = v; }
+            S[bs * GS] = czero<T>();
             fs = bs;
             if (pl) mycol += w + 1;
         }
@@ -1374,7 +1409,7 @@ band_split_local_kernel(BandArgs a, BandArgs r, SplitArgs s)
     if (!act) return;
     // the rows left over, in row order, into the reduced system: columns of S_{i-1} at (i - 1) w .., of S_i at i w ..
     const int rho0 = i == 0 ? 0 : kl + (i - 1) * w, kvr = r.kl + r.ku;
-    c128* rab = r.ab + bix(r, g);
+    T* rab = r.ab + bix(r, g);
     int q_red = -1;
     if (l < w) { if (hasL) q_red = (i - 1) * w + l; }
     else if (bandl) { if (hasR && mycol < a0 + m) q_red = i * w + mycol - (a0 + m - w); }
@@ -1388,9 +1423,9 @@ band_split_local_kernel(BandArgs a, BandArgs r, SplitArgs s)
     }
 }
 
-template <int GS>
+template <class T, int GS>
 __global__ void __launch_bounds__(64)
-band_split_back_kernel(BandArgs a, SplitArgs s, const c128* __restrict__ xs, int n_red, c128* __restrict__ out, long ldo,
+band_split_back_kernel(BandArgsT<T> a, SplitArgsT<T> s, const c128* __restrict__ xs, int n_red, c128* __restrict__ out, long ldo,
                        const int* __restrict__ slots, const int* __restrict__ perm)
 {
     constexpr int NG = 64 / GS;
@@ -1398,37 +1433,37 @@ band_split_back_kernel(BandArgs a, SplitArgs s, const c128* __restrict__ xs, int
     const int i = blockIdx.x * NG + grp;
     const bool act = i < s.p;
     const int n = a.n, w = s.w, m = s.m;
-    const c128* pr = s.pr + (long)g * n * (2 * w + 2);
+    const T* pr = s.pr + (long)g * n * (2 * w + 2);
     const c128* xg = xs + (long)g * n_red;
     c128* o = out + (slots ? (long)slots[g] : (long)g) * ldo;
     const bool hasL = act && i > 0, hasR = act && i < s.p - 1;
     const int a0 = act ? i * m : 0, ni = act ? split_ni(s.p, m, w, n, i) : 0, b0 = a0 + ni - 1;
-    const int T = split_trips<NG>(s.p, m, w, n, blockIdx.x * NG);
+    const int trips = split_trips<NG>(s.p, m, w, n, blockIdx.x * NG);
     const bool mult = l < 2 * w + 1 && l != w;                          // a coefficient that multiplies an x
     bool bad = false;
     // lane k < w: x of column k of S_{i-1}; lane w + d, 1 <= d <= w: x of column c + d, at the start the columns of S_i
-    c128 xv = cmake(0.0, 0.0);
-    if (l < w) { if (hasL) xv = xg[(i - 1) * w + l]; }
-    else if (l > w && l <= 2 * w) { if (hasR) xv = xg[i * w + l - w - 1]; }
+    T xv = czero<T>();
+    if (l < w) { if (hasL) xv = cnarrow<T>(xg[(i - 1) * w + l]); }
+    else if (l > w && l <= 2 * w) { if (hasR) xv = cnarrow<T>(xg[i * w + l - w - 1]); }
     if (hasR && l < w) {                                                // the separator's own x
         const c128 v = xg[i * w + l];
         const int c = a0 + m - w + l;
         o[perm ? perm[c] : c] = v; bad |= !cfinite(v);
     }
-    c128 cur = (ni > 0 && l <= 2 * w + 1) ? pr[(long)b0 * (2 * w + 2) + l] : cmake(0.0, 0.0);
-    for (int j = 0; j < T; ++j) {
+    T cur = (ni > 0 && l <= 2 * w + 1) ? pr[(long)b0 * (2 * w + 2) + l] : czero<T>();
+    for (int j = 0; j < trips; ++j) {
         const bool on = j < ni;
         const int c = b0 - j;
-        const c128 nxt = (j + 1 < ni && l <= 2 * w + 1) ? pr[(long)(c - 1) * (2 * w + 2) + l] : cmake(0.0, 0.0);
-        c128 t = l == 2 * w + 1 ? cur : cmake(0.0, 0.0);
+        const T nxt = (j + 1 < ni && l <= 2 * w + 1) ? pr[(long)(c - 1) * (2 * w + 2) + l] : czero<T>();
+        T t = l == 2 * w + 1 ? cur : czero<T>();
         if (mult) cfms(t, cur, xv);
 #pragma unroll
-        for (int off = GS / 2; off > 0; off >>= 1) { t.x += __shfl_xor(t.x, off, 64); t.y += __shfl_xor(t.y, off, 64); }
-        const c128 piv = cmake(__shfl(cur.x, grp * GS + w, 64), __shfl(cur.y, grp * GS + w, 64));
-        const c128 xc = cdiv(t, piv);
-        const c128 up = cmake(__shfl_up(xv.x, 1, 64), __shfl_up(xv.y, 1, 64));
+        for (int off = GS / 2; off > 0; off >>= 1) lane_xor_add(t, off);
+        const T piv = lane_shfl(cur, grp * GS + w);
+        const T xc = cdiv(t, piv);
+        const T up = lane_shfl_up1(xv);
         if (on) {
-            if (l == 0) { o[perm ? perm[c] : c] = xc; bad |= !cfinite(xc); }
+            if (l == 0) { o[perm ? perm[c] : c] = cwiden(xc); bad |= !cfinite(xc); }
             if (l == w + 1) xv = xc; else if (l > w + 1 && l <= 2 * w) xv = up;
         }
         cur = nxt;
@@ -1438,11 +1473,12 @@ band_split_back_kernel(BandArgs a, SplitArgs s, const c128* __restrict__ xs, int
 
 // The split solve of G matrices on `st`: the reduced system is zeroed, filled by the local phase, solved by its own plan
 // (no slots, no permutation: its x goes to xs), then the back substitution writes everything out.
-hipError_t launch_split(const SplitPlan& sp, const BandArgs& a, const SplitWs& ws, int G, hipStream_t st, c128* out, long ldo,
+template <class T>
+hipError_t launch_split(const SplitPlan& sp, const BandArgsT<T>& a, const SplitWsT<T>& ws, int G, hipStream_t st, c128* out, long ldo,
                         const int* slots, const int* perm) {
-    const SplitArgs s{ws.pr, ws.linfo, sp.w, sp.m, sp.p};
-    const BandArgs& r = ws.r;
-    hipError_t err = hipMemsetAsync(r.ab, 0, sizeof(c128) * (size_t)r.ldab * r.n * G, st);
+    const SplitArgsT<T> s{ws.pr, ws.linfo, sp.w, sp.m, sp.p};
+    const BandArgsT<T>& r = ws.r;
+    hipError_t err = hipMemsetAsync(r.ab, 0, sizeof(T) * (size_t)r.ldab * r.n * G, st);
     if (err == hipSuccess) err = hipMemsetAsync(r.info, 0, sizeof(int) * G, st);
     if (err == hipSuccess) err = hipMemsetAsync(r.flags, 0, sizeof(int) * G, st);
     if (err == hipSuccess) err = hipMemsetAsync(ws.linfo, 0x7f, sizeof(int) * G, st);
@@ -1450,18 +1486,18 @@ hipError_t launch_split(const SplitPlan& sp, const BandArgs& a, const SplitWs& w
     const int ng = 64 / sp.gs;
     const dim3 grid((sp.p + ng - 1) / ng, G);
     switch (sp.gs) {
-    case 8: hipLaunchKernelGGL((band_split_local_kernel<8>), grid, dim3(64), 0, st, a, r, s); break;
-    case 16: hipLaunchKernelGGL((band_split_local_kernel<16>), grid, dim3(64), 0, st, a, r, s); break;
-    case 32: hipLaunchKernelGGL((band_split_local_kernel<32>), grid, dim3(64), 0, st, a, r, s); break;
-    default: hipLaunchKernelGGL((band_split_local_kernel<64>), grid, dim3(64), 0, st, a, r, s); break;
+    case 8: hipLaunchKernelGGL((band_split_local_kernel<T, 8>), grid, dim3(64), 0, st, a, r, s); break;
+    case 16: hipLaunchKernelGGL((band_split_local_kernel<T, 16>), grid, dim3(64), 0, st, a, r, s); break;
+    case 32: hipLaunchKernelGGL((band_split_local_kernel<T, 32>), grid, dim3(64), 0, st, a, r, s); break;
+    default: hipLaunchKernelGGL((band_split_local_kernel<T, 64>), grid, dim3(64), 0, st, a, r, s); break;
     }
     if ((err = hipGetLastError()) != hipSuccess) return err;
     if ((err = launch_solve(sp.rplan, r, ws.rw, G, st, ws.xs, r.n, nullptr, nullptr)) != hipSuccess) return err;
     switch (sp.gs) {
-    case 8: hipLaunchKernelGGL((band_split_back_kernel<8>), grid, dim3(64), 0, st, a, s, ws.xs, r.n, out, ldo, slots, perm); break;
-    case 16: hipLaunchKernelGGL((band_split_back_kernel<16>), grid, dim3(64), 0, st, a, s, ws.xs, r.n, out, ldo, slots, perm); break;
-    case 32: hipLaunchKernelGGL((band_split_back_kernel<32>), grid, dim3(64), 0, st, a, s, ws.xs, r.n, out, ldo, slots, perm); break;
-    default: hipLaunchKernelGGL((band_split_back_kernel<64>), grid, dim3(64), 0, st, a, s, ws.xs, r.n, out, ldo, slots, perm); break;
+    case 8: hipLaunchKernelGGL((band_split_back_kernel<T, 8>), grid, dim3(64), 0, st, a, s, ws.xs, r.n, out, ldo, slots, perm); break;
+    case 16: hipLaunchKernelGGL((band_split_back_kernel<T, 16>), grid, dim3(64), 0, st, a, s, ws.xs, r.n, out, ldo, slots, perm); break;
+    case 32: hipLaunchKernelGGL((band_split_back_kernel<T, 32>), grid, dim3(64), 0, st, a, s, ws.xs, r.n, out, ldo, slots, perm); break;
+    default: hipLaunchKernelGGL((band_split_back_kernel<T, 64>), grid, dim3(64), 0, st, a, s, ws.xs, r.n, out, ldo, slots, perm); break;
     }
     return hipGetLastError();
 }
@@ -1492,25 +1528,28 @@ int band_threads(int kl, int ku) {
     return w <= 512 ? 64 : (w <= 32768 ? 256 : 1024);
 }
 
-void launch_factor(const BandArgs& a, int G, hipStream_t st) {
+template <class T>
+void launch_factor(const BandArgsT<T>& a, int G, hipStream_t st) {
     switch (band_threads(a.kl, a.ku)) {
-    case 64: hipLaunchKernelGGL((band_factor_kernel<64>), dim3(G), dim3(64), 0, st, a); break;
-    case 256: hipLaunchKernelGGL((band_factor_kernel<256>), dim3(G), dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL((band_factor_kernel<1024>), dim3(G), dim3(1024), 0, st, a); break;
+    case 64: hipLaunchKernelGGL((band_factor_kernel<T, 64>), dim3(G), dim3(64), 0, st, a); break;
+    case 256: hipLaunchKernelGGL((band_factor_kernel<T, 256>), dim3(G), dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL((band_factor_kernel<T, 1024>), dim3(G), dim3(1024), 0, st, a); break;
     }
 }
 
-void launch_back(const BandArgs& a, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
+template <class T>
+void launch_back(const BandArgsT<T>& a, int G, hipStream_t st, c128* out, long ldo, const int* slots, const int* perm) {
     switch (band_threads(a.kl, a.ku)) {
-    case 64: hipLaunchKernelGGL((band_back_kernel<64>), dim3(G), dim3(64), 0, st, a, out, ldo, slots, perm); break;
-    case 256: hipLaunchKernelGGL((band_back_kernel<256>), dim3(G), dim3(256), 0, st, a, out, ldo, slots, perm); break;
-    default: hipLaunchKernelGGL((band_back_kernel<1024>), dim3(G), dim3(1024), 0, st, a, out, ldo, slots, perm); break;
+    case 64: hipLaunchKernelGGL((band_back_kernel<T, 64>), dim3(G), dim3(64), 0, st, a, out, ldo, slots, perm); break;
+    case 256: hipLaunchKernelGGL((band_back_kernel<T, 256>), dim3(G), dim3(256), 0, st, a, out, ldo, slots, perm); break;
+    default: hipLaunchKernelGGL((band_back_kernel<T, 1024>), dim3(G), dim3(1024), 0, st, a, out, ldo, slots, perm); break;
     }
 }
 
 // The solve of G matrices on `st` by the schedule of the plan.  w is read where plan.panel; the LW of the wide method lies
 // behind the G panels of lw.  The one-launch-per-phase schedules (column, narrow) report their errors at the caller's next check.
-hipError_t launch_solve(const BandPlan& plan, const BandArgs& a, const BlkArgs& w, int G, hipStream_t st, c128* out, long ldo,
+template <class T>
+hipError_t launch_solve(const BandPlan& plan, const BandArgsT<T>& a, const BlkArgs& w, int G, hipStream_t st, c128* out, long ldo,
                         const int* slots, const int* perm) {
     switch (plan.kind) {
     case BK_COLUMN:
@@ -1520,6 +1559,12 @@ hipError_t launch_solve(const BandPlan& plan, const BandArgs& a, const BlkArgs& 
     case BK_NARROW:
         launch_narrow(a, G, st, out, ldo, slots, perm);
         return hipSuccess;
+    default:
+        break;
+    }
+    // the panel methods have no real instantiation: band_real_kinds keeps a real call away from them
+    if constexpr (!std::is_same_v<T, c128>) return hipErrorInvalidValue;
+    else switch (plan.kind) {
     case BK_BLOCKED:
         return plan.nb == BNB ? launch_blocked_nb<BNB>(a, w, G, st, out, ldo, slots, perm)
                               : launch_blocked_nb<BNB_TALL>(a, w, G, st, out, ldo, slots, perm);
@@ -1622,16 +1667,18 @@ int ensure_band_ws(maus_ctx* c, int want) {
         HIPCHK(c, hipMalloc((void**)&c->band_lw, sizeof(c128) * plan.lw * G));
         HIPCHK(c, hipMalloc((void**)&c->band_ju, sizeof(int) * G));
     }
-    if (sp.on) HIPCHK(c, hipMalloc((void**)&c->band_sws, split_carve(sp, n, G, nullptr, nullptr)));
+    if (sp.on) HIPCHK(c, hipMalloc((void**)&c->band_sws, split_carve<c128>(sp, n, G, nullptr, nullptr)));
     c->band_ws_m = sp.m;
     c->band_g = G; c->band_ws_key = key; c->band_allocs++;
     c->band_at_limit = same || G < G_asked || G >= std::min(cap, gmax);
     return 0;
 }
 
-BandArgs band_args(maus_ctx* c) {
-    BandArgs a;
-    a.ab = c->band_ab; a.x = c->band_x; a.ipiv = c->band_ipiv; a.info = c->band_info; a.flags = c->band_flags;
+// the workspace of the context as T: the real path uses the same allocation as doubles
+template <class T>
+BandArgsT<T> band_args(maus_ctx* c) {
+    BandArgsT<T> a;
+    a.ab = (T*)c->band_ab; a.x = (T*)c->band_x; a.ipiv = c->band_ipiv; a.info = c->band_info; a.flags = c->band_flags;
     a.n = c->band_n; a.kl = c->band_kl; a.ku = c->band_ku; a.ldab = 2 * a.kl + a.ku + 1;
     return a;
 }
@@ -1652,9 +1699,146 @@ void band_status(int G, const int* info, const int* flags, int32_t* status) {
 }
 
 // the solve of G matrices by the split where its plan takes the band, else by the method's plan
-hipError_t launch_any(const SplitPlan& sp, const SplitWs& ws, const BandPlan& plan, const BandArgs& a, const BlkArgs& w, int G, hipStream_t st,
+template <class T>
+hipError_t launch_any(const SplitPlan& sp, const SplitWsT<T>& ws, const BandPlan& plan, const BandArgsT<T>& a, const BlkArgs& w, int G, hipStream_t st,
                       c128* out, long ldo, const int* slots, const int* perm) {
     return sp.on ? launch_split(sp, a, ws, G, st, out, ldo, slots, perm) : launch_solve(plan, a, w, G, st, out, ldo, slots, perm);
+}
+
+// profile class and the scale of the complex flop (1 / 4) and byte (1 / 2) formulas on T
+template <class T> int prof_class(const SplitPlan& sp, const BandPlan& plan) {
+    return std::is_same_v<T, c128> ? (sp.on ? (int)KC_BAND_SPLIT : plan.cls) : (int)KC_BAND_REAL;
+}
+template <class T> double prof_scale(int by) { return std::is_same_v<T, c128> ? 1.0 : 1.0 / by; }
+
+// Whether every kernel that a solve of an (n, kl, ku) band runs under (method, split) has a real instantiation: the column
+// kernel and the narrow method have, for the band itself or for the split's reduced system.  False for a bad partition length.
+bool band_real_kinds(int method, int split_mode, int part_len, int n, int kl, int ku, bool* real, int* kind, bool* split) {
+    SplitPlan sp;
+    if (!split_plan(method, split_mode, part_len, n, kl, ku, &sp)) return false;
+    const BandPlan plan = band_plan(method, kl, ku);
+    const BandKind k = sp.on ? sp.rplan.kind : plan.kind;
+    *real = k == BK_COLUMN || k == BK_NARROW; *kind = plan.kind; *split = sp.on;
+    return true;
+}
+
+// The rule of the real path, stated once: maus_band_solve decides by it and maus_band_real_plan reports it.  All or nothing
+// per call.  MAUS_BAND_REAL_OK or the first condition that fails.
+int band_real_rule(const maus_ctx* c, int rhs_mode, int count, const double* shift) {
+    if (c->band_real != 1) return MAUS_BAND_REAL_OFF;
+    if (!c->csr || c->rows != c->cols || !c->band_perm || c->band_n != c->rows) return MAUS_BAND_REAL_NOT_CSR;
+    if (!c->A_real) return MAUS_BAND_REAL_MATRIX_COMPLEX;
+    if (rhs_mode != 1) return MAUS_BAND_REAL_RHS_ROWS;
+    if (!c->b || !c->b_real) return MAUS_BAND_REAL_RHS_COMPLEX;
+    if (count > 0 && (!shift || !maus_real_flagged(shift, (size_t)count))) return MAUS_BAND_REAL_SHIFT_COMPLEX;
+    bool real = false, split = false; int kind = 0;
+    if (!band_real_kinds(c->band_method, c->band_split, c->band_split_len, c->band_n, c->band_kl, c->band_ku, &real, &kind, &split) || !real)
+        return MAUS_BAND_REAL_NO_KERNELS;
+    return MAUS_BAND_REAL_OK;
+}
+
+// maus_band_lu_host on T: ab and b are the caller's arrays as T (the real path: their real parts)
+template <class T>
+int band_lu_host_t(maus_ctx* c, int count, int n, int kl, int ku, const T* ab, const T* b, double* x_out,
+                   int32_t* ipiv_out, int32_t* info_out) {
+    BandArgsT<T> a;
+    a.n = n; a.kl = kl; a.ku = ku; a.ldab = 2 * kl + ku + 1;
+    const size_t abb = sizeof(T) * (size_t)a.ldab * n, xb = sizeof(T) * (size_t)n, ob = sizeof(c128) * (size_t)n, ib = sizeof(int) * (size_t)n;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    const size_t o_ab = take(abb * count), o_x = take(xb * count), o_o = take(ob * count), o_p = take(ib * count),
+                 o_i = take(sizeof(int) * count), o_f = take(sizeof(int) * count);
+    const BandPlan plan = band_plan(c->band_method, kl, ku);
+    const size_t o_l = take(sizeof(c128) * plan.lw * count), o_j = take(plan.panel ? sizeof(int) * count : 0);
+    SplitPlan sp;
+    if (!split_plan(c->band_method, c->band_split, c->band_split_len, n, kl, ku, &sp))
+        FAIL(c, "maus_band_lu_host: the partition length of maus_band_set_split is below 2 (kl + ku) + 2 for this band");
+    const size_t o_s = take(sp.on ? split_carve<T>(sp, n, count, nullptr, nullptr) : 0);
+    if (ensure_scratch(c, off)) return -1;
+    char* base = (char*)c->scratch;
+    a.ab = (T*)(base + o_ab); a.x = (T*)(base + o_x); a.ipiv = (int*)(base + o_p); a.info = (int*)(base + o_i); a.flags = (int*)(base + o_f);
+    c128* out = (c128*)(base + o_o);
+    const BlkArgs w = blk_args(plan, kl, plan.panel ? (c128*)(base + o_l) : nullptr, plan.panel ? (int*)(base + o_j) : nullptr);
+    SplitWsT<T> ws{};
+    if (sp.on) split_carve(sp, n, count, base + o_s, &ws);
+    if (maus_stage_h2d(c, a.ab, ab, abb * count, c->st)) return -1;
+    if (maus_stage_h2d(c, a.x, b, xb * count, c->st)) return -1;
+    HIPCHK(c, hipMemsetAsync(a.info, 0, sizeof(int) * count, c->st));
+    HIPCHK(c, hipMemsetAsync(a.flags, 0, sizeof(int) * count, c->st));
+    {
+        ProfScope ps(c, prof_class<T>(sp, plan), prof_scale<T>(4) * (sp.on ? split_flops(sp, n, count) : band_flops(n, kl, ku, count)),
+                     prof_scale<T>(2) * (sp.on ? split_bytes_moved(sp, n, kl, ku, count) : band_bytes(plan, n, kl, ku, count)));
+        hipLaunchKernelGGL(band_scan_kernel<T>, dim3(64, count), dim3(256), 0, c->st, a);
+        if constexpr (std::is_same_v<T, c128>)
+            if (plan.panel && !sp.on) hipLaunchKernelGGL(band_zero_fill_kernel, dim3(64, count), dim3(256), 0, c->st, a);
+        HIPCHK(c, launch_any(sp, ws, plan, a, w, count, c->st, out, n, nullptr, nullptr));
+    }
+    std::vector<int> h_info(count), h_flags(count), h_rinfo(sp.on ? count : 0), h_ripiv(sp.on && ipiv_out ? (size_t)sp.n_red * count : 0);
+    if (maus_stage_d2h(c, x_out, out, ob * count, c->st)) return -1;
+    if (ipiv_out && maus_stage_d2h(c, ipiv_out, a.ipiv, ib * count, c->st)) return -1;
+    if (!h_ripiv.empty() && maus_stage_d2h(c, h_ripiv.data(), ws.r.ipiv, sizeof(int) * h_ripiv.size(), c->st)) return -1;
+    if (maus_d2h(c, h_info.data(), sp.on ? ws.linfo : a.info, sizeof(int) * count, c->st)) return -1;
+    if (sp.on && maus_d2h(c, h_rinfo.data(), ws.r.info, sizeof(int) * count, c->st)) return -1;
+    if (maus_d2h(c, h_flags.data(), a.flags, sizeof(int) * count, c->st)) return -1;
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipGetLastError());
+    if (sp.on) {
+        for (int g = 0; g < count; ++g) h_info[g] = split_info(sp, h_info[g], h_rinfo[g]);
+        // a separator column carries the pivot of its unknown of the reduced system (LAPACK's 1-based row of that system)
+        if (ipiv_out)
+            for (int g = 0; g < count; ++g)
+                for (int q = 0; q < sp.n_red; ++q) ipiv_out[(size_t)g * n + split_sep_col(sp, q)] = h_ripiv[(size_t)g * sp.n_red + q];
+    }
+    band_status(count, h_info.data(), h_flags.data(), info_out);
+    return 0;
+}
+
+// maus_band_solve on T (the caller has decided by band_real_rule): what the rule relies on is what the build kernel reads
+template <class T>
+int band_solve_t(maus_ctx* c, const int* slots, int count, const double* shift, const double* psi, int rhs_mode, int32_t* status) {
+    if (!c->csr || !c->X) FAIL(c, "maus_band_solve: sparse matrix/population missing");
+    if (!c->band_perm || c->band_n != c->rows) FAIL(c, "maus_band_solve: no ordering for the bound matrix (maus_band_prepare)");
+    if (rhs_mode != 0 && rhs_mode != 1) FAIL(c, "maus_band_solve: rhs_mode must be 0 (X[slot]) or 1 (b)");
+    if (rhs_mode == 1 && (!c->b || c->bn != c->rows)) FAIL(c, "maus_band_solve: rhs b not set");
+    if (count == 0) return 0;
+    if (check_slots(c, slots, count)) return -1;
+    if (ensure_scalars(c, count)) return -1;
+    if (ensure_band_ws(c, count)) return -1;
+    const int nchunks = (count + c->band_g - 1) / c->band_g;            // balanced chunks, as maus_shifted_lu_solve
+    const int Gmax = (count + nchunks - 1) / nchunks;
+    std::vector<int> h_info(Gmax), h_flags(Gmax);
+    const BandArgsT<T> a = band_args<T>(c);
+    const BandPlan plan = band_plan(c->band_method, a.kl, a.ku);
+    const BlkArgs w = blk_args(plan, a.kl, c->band_lw, c->band_ju);
+    SplitPlan sp;
+    SplitWsT<T> ws{};
+    (void)split_plan(c->band_method, c->band_split, c->band_split_len, a.n, a.kl, a.ku, &sp);   // checked by ensure_band_ws
+    if (sp.on) split_carve(sp, a.n, c->band_g, c->band_sws, &ws);
+    std::vector<int> h_rinfo(sp.on ? Gmax : 0);
+    for (int off = 0; off < count; off += Gmax) {
+        const int G = std::min(Gmax, count - off);
+        if (maus_h2d(c, c->d_slots, slots + off, sizeof(int) * G, c->st)) return -1;
+        if (maus_h2d(c, c->d_c1, shift + 2 * (size_t)off, sizeof(c128) * G, c->st)) return -1;
+        if (maus_h2d(c, c->d_r1, psi + off, sizeof(double) * G, c->st)) return -1;
+        {
+            ProfScope ps(c, prof_class<T>(sp, plan), prof_scale<T>(4) * (sp.on ? split_flops(sp, a.n, G) : band_flops(a.n, a.kl, a.ku, G)),
+                         prof_scale<T>(2) * (sp.on ? split_bytes_moved(sp, a.n, a.kl, a.ku, G) : band_bytes(plan, a.n, a.kl, a.ku, G)));
+            HIPCHK(c, hipMemsetAsync(a.info, 0, sizeof(int) * G, c->st));
+            HIPCHK(c, hipMemsetAsync(a.flags, 0, sizeof(int) * G, c->st));
+            HIPCHK(c, hipMemsetAsync(a.ab, 0, sizeof(T) * (size_t)a.ldab * a.n * G, c->st));
+            hipLaunchKernelGGL(band_build_csr_kernel<T>, dim3((a.n + 255) / 256, G), dim3(256), 0, c->st, a, c->Acsr.ptr, c->Acsr.idx,
+                               c->Acsr.val, c->band_perm, c->band_iperm, c->d_c1, c->d_r1, rhs_mode, c->X, c->ldp, c->d_slots, c->b);
+            HIPCHK(c, launch_any(sp, ws, plan, a, w, G, c->st, c->W, c->ldp, c->d_slots, c->band_perm));
+        }
+        if (maus_d2h(c, h_info.data(), sp.on ? ws.linfo : a.info, sizeof(int) * G, c->st)) return -1;
+        if (sp.on && maus_d2h(c, h_rinfo.data(), ws.r.info, sizeof(int) * G, c->st)) return -1;
+        if (maus_d2h(c, h_flags.data(), a.flags, sizeof(int) * G, c->st)) return -1;
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        HIPCHK(c, hipGetLastError());
+        if (sp.on) for (int g = 0; g < G; ++g) h_info[g] = split_info(sp, h_info[g], h_rinfo[g]);
+        band_status(G, h_info.data(), h_flags.data(), status + off);
+    }
+    return 0;
 }
 
 }  // namespace
@@ -1719,49 +1903,9 @@ int maus_band_reserve(maus_ctx* c, int count, int* capacity_out) {
 int maus_band_solve(maus_ctx* c, const int* slots, int count, const double* shift, const double* psi, int rhs_mode, int32_t* status) {
     if (!c) return -1;
     maus_av_drop_all(c);
-    if (!c->csr || !c->X) FAIL(c, "maus_band_solve: sparse matrix/population missing");
-    if (!c->band_perm || c->band_n != c->rows) FAIL(c, "maus_band_solve: no ordering for the bound matrix (maus_band_prepare)");
-    if (rhs_mode != 0 && rhs_mode != 1) FAIL(c, "maus_band_solve: rhs_mode must be 0 (X[slot]) or 1 (b)");
-    if (rhs_mode == 1 && (!c->b || c->bn != c->rows)) FAIL(c, "maus_band_solve: rhs b not set");
-    if (count == 0) return 0;
-    if (check_slots(c, slots, count)) return -1;
-    if (ensure_scalars(c, count)) return -1;
-    if (ensure_band_ws(c, count)) return -1;
-    const int nchunks = (count + c->band_g - 1) / c->band_g;            // balanced chunks, as maus_shifted_lu_solve
-    const int Gmax = (count + nchunks - 1) / nchunks;
-    std::vector<int> h_info(Gmax), h_flags(Gmax);
-    const BandArgs a = band_args(c);
-    const BandPlan plan = band_plan(c->band_method, a.kl, a.ku);
-    const BlkArgs w = blk_args(plan, a.kl, c->band_lw, c->band_ju);
-    SplitPlan sp;
-    SplitWs ws{};
-    (void)split_plan(c->band_method, c->band_split, c->band_split_len, a.n, a.kl, a.ku, &sp);   // checked by ensure_band_ws
-    if (sp.on) split_carve(sp, a.n, c->band_g, c->band_sws, &ws);
-    std::vector<int> h_rinfo(sp.on ? Gmax : 0);
-    for (int off = 0; off < count; off += Gmax) {
-        const int G = std::min(Gmax, count - off);
-        if (maus_h2d(c, c->d_slots, slots + off, sizeof(int) * G, c->st)) return -1;
-        if (maus_h2d(c, c->d_c1, shift + 2 * (size_t)off, sizeof(c128) * G, c->st)) return -1;
-        if (maus_h2d(c, c->d_r1, psi + off, sizeof(double) * G, c->st)) return -1;
-        {
-            ProfScope ps(c, sp.on ? KC_BAND_SPLIT : plan.cls, sp.on ? split_flops(sp, a.n, G) : band_flops(a.n, a.kl, a.ku, G),
-                         sp.on ? split_bytes_moved(sp, a.n, a.kl, a.ku, G) : band_bytes(plan, a.n, a.kl, a.ku, G));
-            HIPCHK(c, hipMemsetAsync(a.info, 0, sizeof(int) * G, c->st));
-            HIPCHK(c, hipMemsetAsync(a.flags, 0, sizeof(int) * G, c->st));
-            HIPCHK(c, hipMemsetAsync(a.ab, 0, sizeof(c128) * (size_t)a.ldab * a.n * G, c->st));
-            hipLaunchKernelGGL(band_build_csr_kernel, dim3((a.n + 255) / 256, G), dim3(256), 0, c->st, a, c->Acsr.ptr, c->Acsr.idx,
-                               c->Acsr.val, c->band_perm, c->band_iperm, c->d_c1, c->d_r1, rhs_mode, c->X, c->ldp, c->d_slots, c->b);
-            HIPCHK(c, launch_any(sp, ws, plan, a, w, G, c->st, c->W, c->ldp, c->d_slots, c->band_perm));
-        }
-        if (maus_d2h(c, h_info.data(), sp.on ? ws.linfo : a.info, sizeof(int) * G, c->st)) return -1;
-        if (sp.on && maus_d2h(c, h_rinfo.data(), ws.r.info, sizeof(int) * G, c->st)) return -1;
-        if (maus_d2h(c, h_flags.data(), a.flags, sizeof(int) * G, c->st)) return -1;
-        HIPCHK(c, hipStreamSynchronize(c->st));
-        HIPCHK(c, hipGetLastError());
-        if (sp.on) for (int g = 0; g < G; ++g) h_info[g] = split_info(sp, h_info[g], h_rinfo[g]);
-        band_status(G, h_info.data(), h_flags.data(), status + off);
-    }
-    return 0;
+    // real or complex: one decision for the whole call (band_real_rule), also where the call then runs in chunks
+    return band_real_rule(c, rhs_mode, count, shift) == MAUS_BAND_REAL_OK ? band_solve_t<double>(c, slots, count, shift, psi, rhs_mode, status)
+                                                                          : band_solve_t<c128>(c, slots, count, shift, psi, rhs_mode, status);
 }
 
 int maus_band_workspace_allocs(maus_ctx* c) { return c ? c->band_allocs : -1; }
@@ -1834,54 +1978,44 @@ int maus_band_lu_host(maus_ctx* c, int count, int n, int kl, int ku, const doubl
     if (!c) return -1;
     if (count <= 0 || n <= 0 || kl < 0 || ku < 0 || n > maus_sparse_max_n()) FAIL(c, "maus_band_lu_host: bad sizes");
     if (!ab || !b || !x_out || !info_out) FAIL(c, "maus_band_lu_host: null array");
-    BandArgs a;
-    a.n = n; a.kl = kl; a.ku = ku; a.ldab = 2 * kl + ku + 1;
-    const size_t abb = sizeof(c128) * (size_t)a.ldab * n, xb = sizeof(c128) * (size_t)n, ib = sizeof(int) * (size_t)n;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    const size_t o_ab = take(abb * count), o_x = take(xb * count), o_o = take(xb * count), o_p = take(ib * count),
-                 o_i = take(sizeof(int) * count), o_f = take(sizeof(int) * count);
-    const BandPlan plan = band_plan(c->band_method, kl, ku);
-    const size_t o_l = take(sizeof(c128) * plan.lw * count), o_j = take(plan.panel ? sizeof(int) * count : 0);
-    SplitPlan sp;
-    if (!split_plan(c->band_method, c->band_split, c->band_split_len, n, kl, ku, &sp))
-        FAIL(c, "maus_band_lu_host: the partition length of maus_band_set_split is below 2 (kl + ku) + 2 for this band");
-    const size_t o_s = take(sp.on ? split_carve(sp, n, count, nullptr, nullptr) : 0);
-    if (ensure_scratch(c, off)) return -1;
-    char* base = (char*)c->scratch;
-    a.ab = (c128*)(base + o_ab); a.x = (c128*)(base + o_x); a.ipiv = (int*)(base + o_p); a.info = (int*)(base + o_i); a.flags = (int*)(base + o_f);
-    c128* out = (c128*)(base + o_o);
-    const BlkArgs w = blk_args(plan, kl, plan.panel ? (c128*)(base + o_l) : nullptr, plan.panel ? (int*)(base + o_j) : nullptr);
-    SplitWs ws{};
-    if (sp.on) split_carve(sp, n, count, base + o_s, &ws);
-    if (maus_stage_h2d(c, a.ab, ab, abb * count, c->st)) return -1;
-    if (maus_stage_h2d(c, a.x, b, xb * count, c->st)) return -1;
-    HIPCHK(c, hipMemsetAsync(a.info, 0, sizeof(int) * count, c->st));
-    HIPCHK(c, hipMemsetAsync(a.flags, 0, sizeof(int) * count, c->st));
-    {
-        ProfScope ps(c, sp.on ? KC_BAND_SPLIT : plan.cls, sp.on ? split_flops(sp, n, count) : band_flops(n, kl, ku, count),
-                     sp.on ? split_bytes_moved(sp, n, kl, ku, count) : band_bytes(plan, n, kl, ku, count));
-        hipLaunchKernelGGL(band_scan_kernel, dim3(64, count), dim3(256), 0, c->st, a);
-        if (plan.panel && !sp.on) hipLaunchKernelGGL(band_zero_fill_kernel, dim3(64, count), dim3(256), 0, c->st, a);
-        HIPCHK(c, launch_any(sp, ws, plan, a, w, count, c->st, out, n, nullptr, nullptr));
+    // the real path (maus_band_set_real): the plan has real kernels and every element handed in is flagged real
+    bool real = false, split = false; int kind = 0;
+    const size_t nab = (size_t)(2 * kl + ku + 1) * n * count, nb = (size_t)n * count;
+    if (c->band_real == 1 && band_real_kinds(c->band_method, c->band_split, c->band_split_len, n, kl, ku, &real, &kind, &split) && real
+        && maus_real_flagged(ab, nab) && maus_real_flagged(b, nb)) {
+        std::vector<double> abr(nab), br(nb);
+        for (size_t i = 0; i < nab; ++i) abr[i] = ab[2 * i];
+        for (size_t i = 0; i < nb; ++i) br[i] = b[2 * i];
+        return band_lu_host_t<double>(c, count, n, kl, ku, abr.data(), br.data(), x_out, ipiv_out, info_out);
     }
-    std::vector<int> h_info(count), h_flags(count), h_rinfo(sp.on ? count : 0), h_ripiv(sp.on && ipiv_out ? (size_t)sp.n_red * count : 0);
-    if (maus_stage_d2h(c, x_out, out, xb * count, c->st)) return -1;
-    if (ipiv_out && maus_stage_d2h(c, ipiv_out, a.ipiv, ib * count, c->st)) return -1;
-    if (!h_ripiv.empty() && maus_stage_d2h(c, h_ripiv.data(), ws.r.ipiv, sizeof(int) * h_ripiv.size(), c->st)) return -1;
-    if (maus_d2h(c, h_info.data(), sp.on ? ws.linfo : a.info, sizeof(int) * count, c->st)) return -1;
-    if (sp.on && maus_d2h(c, h_rinfo.data(), ws.r.info, sizeof(int) * count, c->st)) return -1;
-    if (maus_d2h(c, h_flags.data(), a.flags, sizeof(int) * count, c->st)) return -1;
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    HIPCHK(c, hipGetLastError());
-    if (sp.on) {
-        for (int g = 0; g < count; ++g) h_info[g] = split_info(sp, h_info[g], h_rinfo[g]);
-        // a separator column carries the pivot of its unknown of the reduced system (LAPACK's 1-based row of that system)
-        if (ipiv_out)
-            for (int g = 0; g < count; ++g)
-                for (int q = 0; q < sp.n_red; ++q) ipiv_out[(size_t)g * n + split_sep_col(sp, q)] = h_ripiv[(size_t)g * sp.n_red + q];
-    }
-    band_status(count, h_info.data(), h_flags.data(), info_out);
+    return band_lu_host_t<c128>(c, count, n, kl, ku, (const c128*)ab, (const c128*)b, x_out, ipiv_out, info_out);
+}
+
+int maus_band_set_real(maus_ctx* c, int mode) {
+    if (!c) return -1;
+    if (mode != 0 && mode != 1) FAIL(c, "maus_band_set_real: mode must be 0 (complex arithmetic) or 1 (real arithmetic where the rule holds)");
+    c->band_real = mode;
+    return 0;
+}
+
+int maus_band_get_real(maus_ctx* c) { return c ? c->band_real : -1; }
+
+int maus_band_real_plan(maus_ctx* c, int rhs_mode, int count, const double* shift, int32_t* out) {
+    if (!c) return -1;
+    if (count < 0 || (count > 0 && !shift) || !out) FAIL(c, "maus_band_real_plan: bad arguments");
+    const int why = band_real_rule(c, rhs_mode, count, shift);
+    bool real = false, split = false; int kind = 0;
+    if (c->band_perm)
+        (void)band_real_kinds(c->band_method, c->band_split, c->band_split_len, c->band_n, c->band_kl, c->band_ku, &real, &kind, &split);
+    out[0] = why == MAUS_BAND_REAL_OK; out[1] = why; out[2] = kind; out[3] = split;
+    return 0;
+}
+
+int maus_band_real_kinds(int method, int split_mode, int part_len, int n, int kl, int ku, int32_t* out) {
+    if (!band_method_ok(method) || (split_mode != 0 && split_mode != 1) || part_len < 0 || n < 0 || kl < 0 || ku < 0 || !out) return -1;
+    bool real = false, split = false; int kind = 0;
+    if (!band_real_kinds(method, split_mode, part_len, n, kl, ku, &real, &kind, &split)) return -1;
+    out[0] = real; out[1] = kind; out[2] = split;
     return 0;
 }
 

@@ -59,6 +59,21 @@ __device__ __forceinline__ c128 cdiv(c128 a, c128 b) {
     }
 }
 __device__ __forceinline__ bool cfinite(c128 a) { return isfinite(a.x) && isfinite(a.y); }
+__device__ __forceinline__ bool ciszero(c128 a) { return a.x == 0.0 && a.y == 0.0; }
+// The same on real operands: what the complex ones evaluate when every imaginary part is an exact zero (the real path of
+// band.hip) -- the product rounds once, Smith's reciprocal and quotient come down to one division (t = +-0, d = z.x)
+__device__ __forceinline__ double cmul(double a, double b) { return __dmul_rn(a, b); }
+__device__ __forceinline__ double cabs1(double a) { return fabs(a); }
+__device__ __forceinline__ double crecip(double z) { return 1.0 / z; }
+__device__ __forceinline__ double cdiv(double a, double b) { return a / b; }
+__device__ __forceinline__ bool cfinite(double a) { return isfinite(a); }
+__device__ __forceinline__ bool ciszero(double a) { return a == 0.0; }
+// T as a c128 with imaginary part +0.0 (the store into W[slot] or out), and the T of a c128 (its real part)
+__device__ __forceinline__ c128 cwiden(c128 a) { return a; }
+__device__ __forceinline__ c128 cwiden(double a) { return cmake(a, 0.0); }
+template <class T> __device__ __forceinline__ T cnarrow(c128 a);
+template <> __device__ __forceinline__ c128 cnarrow<c128>(c128 a) { return a; }
+template <> __device__ __forceinline__ double cnarrow<double>(c128 a) { return a.x; }
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -117,4 +132,4 @@ static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 // kernel classes for the profiling counters (maus_profile_read)
 enum { KC_GEMM = 0, KC_PANEL = 1, KC_TRSM = 2, KC_LASWP = 3, KC_BUILD = 4, KC_BACKSOLVE = 5, KC_VEC = 6,
-       KC_GEMM_K128 = 7, KC_GEMM_K64 = 8, KC_GEMM_K32 = 9, KC_GEMM_K16 = 10, KC_SPMM = 11, KC_BAND = 12, KC_LANCZOS = 13, KC_BAND_BLOCKED = 14, KC_BAND_TILED = 15, KC_BAND_WIDE = 16, KC_GMRES_WIDE = 17, KC_BAND_SPLIT = 18, KC_GMRES_REAL = 19, KC_SPMM_REAL = 20, KC_COUNT = 21 };   // 7..10: LU recursion GEMMs by K (<256); 11: CSR products (spmm.hip); 12: band solves (band.hip); 13: Lanczos reorthogonalisation, restart and match (lanczos.hip); 14: band solves by the blocked method (band.hip); 15: band solves by the tiled method (band.hip); 16: band solves by the wide method (band.hip); 17: the wide GMRES post step (gmres.hip); 18: band solves by the split method (band.hip); 19: the GMRES post step of the real path, any schedule (gmres.hip); 20: CSR products of the real path (spmm.hip)
+       KC_GEMM_K128 = 7, KC_GEMM_K64 = 8, KC_GEMM_K32 = 9, KC_GEMM_K16 = 10, KC_SPMM = 11, KC_BAND = 12, KC_LANCZOS = 13, KC_BAND_BLOCKED = 14, KC_BAND_TILED = 15, KC_BAND_WIDE = 16, KC_GMRES_WIDE = 17, KC_BAND_SPLIT = 18, KC_GMRES_REAL = 19, KC_SPMM_REAL = 20, KC_BAND_REAL = 21, KC_COUNT = 22 };   // 7..10: LU recursion GEMMs by K (<256); 11: CSR products (spmm.hip); 12: band solves (band.hip); 13: Lanczos reorthogonalisation, restart and match (lanczos.hip); 14: band solves by the blocked method (band.hip); 15: band solves by the tiled method (band.hip); 16: band solves by the wide method (band.hip); 17: the wide GMRES post step (gmres.hip); 18: band solves by the split method (band.hip); 19: the GMRES post step of the real path, any schedule (gmres.hip); 20: CSR products of the real path (spmm.hip); 21: band solves of the real path, any method and the split (band.hip)

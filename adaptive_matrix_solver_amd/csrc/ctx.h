@@ -95,7 +95,8 @@ struct maus_ctx {
     int band_g = 0, band_allocs = 0; bool band_at_limit = false; unsigned long long band_ws_key = 0;
     int band_method = 0;                                // 0: column kernel, 1: blocked, 2: tiled, 4: wide (maus_band_set_method); kept across matrices
     int band_split = 0, band_split_len = 0;             // maus_band_set_split: 0 off / 1 on, the forced partition length (0: the rule); kept across matrices
-    char* band_sws = nullptr; int band_ws_m = 0;        // the split method's arrays of the workspace (SplitWs) and the partition length they were sized for
+    int band_real = 0;                                  // maus_band_set_real: 0 complex arithmetic, 1 real arithmetic where the rule of band.hip holds; kept across matrices
+    char* band_sws = nullptr; int band_ws_m = 0;       // the split method's arrays of the workspace (SplitWs) and the partition length they were sized for
     c128* band_lw = nullptr; int* band_ju = nullptr;    // the blocked / tiled / wide method's panel of L (wide: LW behind it) and reach, per solve of the workspace
     MausLanczos lz;
     int gmres_method = 0;                               // 0: one workgroup per candidate, 1: the wide step for CSR matrices (maus_gmres_set_method); kept across matrices

@@ -315,6 +315,17 @@ def real_arith_mode(mode):
     return mode
 
 
+REAL_DIRECT_MODES = ("auto", "off", "on")
+
+
+def real_direct_mode(mode):
+    """The `real_direct` keyword: an explicit value, else MAUS_REAL_DIRECT, else 'auto' (which means 'off')."""
+    mode = mode if mode is not None else os.environ.get("MAUS_REAL_DIRECT", "auto")
+    if mode not in REAL_DIRECT_MODES:
+        raise ValueError(f"real_direct must be one of {REAL_DIRECT_MODES}, not {mode!r}")
+    return mode
+
+
 SPARSE_EIGSH_MODES = ("auto", "dense", "lanczos")
 
 
@@ -416,7 +427,7 @@ class DeviceEngine:
     def __init__(self, device: int = 0, pert_mode: str = "auto", gmres_compat: str = "rtol",
                  comm=None, ctx=None, eigh_mode: str = "auto", sparse_mode=None, sparse_direct=None, sparse_eigsh=None,
                  sparse_gmres=None, few_rows=None, sparse_spmm=None, sparse_split=None, vector_draws=None,
-                 real_arith=None):
+                 real_arith=None, real_direct=None):
         self.ctx = ctx if ctx is not None else _cabi.Context(device)
         cap_blas_threads()
         # Hermitian eigendecomposition (AMS:161), once per matrix: 'host' = scipy.linalg.eigh, the reference's call, (lambda, V)
@@ -469,6 +480,12 @@ class DeviceEngine:
         # direct fallback, the residual products -- runs as ever.  MAUS_REAL_ARITH sets the default.  Told to the context
         # when a sparse matrix is bound, before the bind, which builds the real copies under it.
         self.real_arith = real_arith_mode(real_arith)
+        # band solves of a real sparse system (DESIGN §11 "Band solves in real arithmetic"): 'off' and 'auto' = complex
+        # arithmetic as ever; 'on' = a direct solve of a linear system whose operand, b and shifts are all real runs on band
+        # storage of doubles under the column kernel or 'narrow', with or without the split (opt-in, 'auto' never picks it; the
+        # complex path's x and status).  Eigenvalue problems and the blocked, tiled and wide kernels run as ever.  Independent
+        # of real_arith.  MAUS_REAL_DIRECT sets the default.  Told to the context with the ordering (prepare_band).
+        self.real_direct = real_direct_mode(real_direct)
         # sparse Hermitian shortcut (AMS:186-216): 'dense' = one scipy.linalg.eigh of A.toarray() per matrix, 'lanczos' =
         # thick-restart Lanczos on the CSR matrix on the device, 'auto' the first up to maus_lu_max_n() and the second above.
         # MAUS_SPARSE_EIGSH sets the default.
@@ -595,6 +612,8 @@ class DeviceEngine:
                 self.ctx.band_set_method(DIRECT_METHOD[self.sparse_direct])
             if self.sparse_split == "on":               # 'off' does not touch the switch: contexts without it keep working
                 self.ctx.band_set_split(True, 0)
+            if self.real_direct == "on":                # 'off' does not touch the switch: contexts without it keep working
+                self.ctx.band_set_real(_cabi.BAND_REAL_ON)
             self.ctx.band_prepare(perm)
             self._band_ready = True
 

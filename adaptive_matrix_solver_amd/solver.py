@@ -32,7 +32,7 @@ from . import _cabi
 from ._cabi import POP_U, POP_X
 from .band import DIRECT_METHOD, band_bytes_per_solve, band_order, split_bytes_per_solve
 from .candstore import C_NP as _C_NP, C_PY as _C_PY, EXACT as _EXACT, F_NP as _F_NP, F_PY as _F_PY, HREF as _HREF, MISSING as _MISSING
-from .engine import DIRECT, GMRES, DeviceEngine, _advance_numpy_stream, few_rows_mode, vector_draws_mode, sparse_direct_mode, sparse_eigsh_mode, sparse_gmres_mode, sparse_split_mode, sparse_spmm_mode, real_arith_mode
+from .engine import DIRECT, GMRES, DeviceEngine, _advance_numpy_stream, few_rows_mode, vector_draws_mode, sparse_direct_mode, sparse_eigsh_mode, sparse_gmres_mode, sparse_split_mode, sparse_spmm_mode, real_arith_mode, real_direct_mode
 
 
 class ProblemType(Enum):                     # AMS:10-13
@@ -162,7 +162,7 @@ class InverseIterateSolver:
 
     def __init__(self, N, base_psi_epsilon, max_attempts, preferred_method="direct_solve", is_sparse=False,
                  gmres_compat="rtol", pert_mode="uniform", sparse_mode=None, sparse_direct=None, sparse_gmres=None,
-                 few_rows=None, sparse_spmm=None, sparse_split=None, real_arith=None):
+                 few_rows=None, sparse_spmm=None, sparse_split=None, real_arith=None, real_direct=None):
         self.N = N
         self.base_psi_epsilon = base_psi_epsilon
         self.max_attempts = max_attempts
@@ -178,6 +178,7 @@ class InverseIterateSolver:
         self.few_rows = few_rows_mode(few_rows)
         self.sparse_spmm = sparse_spmm_mode(sparse_spmm)
         self.real_arith = real_arith_mode(real_arith)
+        self.real_direct = real_direct_mode(real_direct)
         self.last_trace = []
 
     @classmethod
@@ -234,6 +235,11 @@ class InverseIterateSolver:
                     ctx.band_set_split(True, 0)
                 elif getattr(ctx, "band_split", None) is not None and ctx.band_split()[0]:
                     ctx.band_set_split(False, 0)
+                # ... and real arithmetic for the band solves ('on' is opt-in)
+                if self.real_direct == "on":
+                    ctx.band_set_real(_cabi.BAND_REAL_ON)
+                elif getattr(ctx, "band_real", None) is not None and ctx.band_real() != _cabi.BAND_REAL_OFF:
+                    ctx.band_set_real(_cabi.BAND_REAL_OFF)
                 ctx.band_prepare(band_order(A_sp)[0])
         else:
             band = False
@@ -822,9 +828,10 @@ class MAUS_Solver:
                  record_history=None, comm=None, quiet=False, engine=None, gram_min=8, cond_exact_max=1024,
                  diag_info=None, eigh_mode="auto", sparse_mode=None, sparse_direct=None, sparse_eigsh=None,
                  sparse_hermitian_check=None, sparse_gmres=None, few_rows=None, sparse_spmm=None, sparse_split=None,
-                 vector_draws=None, real_arith=None):
+                 vector_draws=None, real_arith=None, real_direct=None):
         few_rows = few_rows_mode(few_rows)
         real_arith = real_arith_mode(real_arith)
+        real_direct = real_direct_mode(real_direct)
         vector_draws = vector_draws_mode(vector_draws)
         sparse_split = sparse_split_mode(sparse_split)
         sparse_spmm = sparse_spmm_mode(sparse_spmm)
@@ -858,7 +865,7 @@ class MAUS_Solver:
                                                                      sparse_eigsh=sparse_eigsh, sparse_gmres=sparse_gmres,
                                                                      few_rows=few_rows, sparse_spmm=sparse_spmm,
                                                                      sparse_split=sparse_split, vector_draws=vector_draws,
-                                                                     real_arith=real_arith)
+                                                                     real_arith=real_arith, real_direct=real_direct)
         # `diag_info`: start-up diagnostics of the same matrix taken from an earlier solver (bench side runs)
         if diag_info is not None:
             self.diag_info = dict(diag_info)

@@ -156,7 +156,42 @@ int maus_matrix_is_sparse(maus_ctx* ctx);
  *   device: takes (0 / 1), the partition length, the number of partitions, the reduced system's order and half-bandwidths,
  *   and the bytes of the split's arrays per solve (what the workspace adds to maus_band_plan's).  Where takes = 0 the rest
  *   are 0.  Every out pointer may be NULL.  Returns 0, or -1 for a bad method, a negative size, or a part_len below
- *   2 (kl + ku) + 2 on a band in the split's range. */
+ *   2 (kl + ku) + 2 on a band in the split's range.
+ * maus_band_set_real: band solves in real arithmetic (DESIGN §11 "Band solves in real arithmetic"), a switch of its own beside
+ *   maus_real_set_method and independent of it.  mode 0 (the default): complex arithmetic, today's path bit for bit.  mode 1:
+ *   a maus_band_solve call runs on band storage, right-hand sides and ring slots of doubles when all of these hold -- a
+ *   square CSR matrix with an ordering is bound and every stored value has an imaginary part of +-0; rhs_mode is 1 and b is
+ *   real in the same sense; every shift of the call has an imaginary part of +-0 (maus_real_values_flagged); and the plan of
+ *   the context's method for (kl, ku) is the column kernel or the narrow method, or the split takes the band and its reduced
+ *   system's plan is one of those two.  All or nothing per call, also where the call runs in chunks.  Otherwise the call
+ *   runs complex as ever: population rows as right-hand sides (eigenvalue problems) and the blocked, tiled and wide kernels
+ *   have no real instantiation.  The real kernels are the complex text over T = double: geometry, ownership, pivot rule,
+ *   chunks, ring slots, partition lengths and plans are the complex path's, and every operation is the complex one without
+ *   the terms that multiply an exact zero.  For finite data x, ipiv, info and status are the complex path's under
+ *   array_equal (zeros may differ in sign); a solution of a singular or non-finite system may hold Inf where the complex
+ *   path holds NaN, with the same status.  W[slot] receives x with imaginary part +0.0.  No real copy of the operand is
+ *   kept (the build kernel reads the real parts of the complex CSR values and of b) and nothing is allocated: the band
+ *   workspace is used as doubles.  Counted in the profile class 21 ("band_real") and in no other band class.  Kept across
+ *   matrices.  A mode other than 0 / 1 is refused and changes nothing.
+ *   maus_band_lu_host follows the switch: under mode 1 it runs real when the plan qualifies and every element of ab and b
+ *   handed in has an imaginary part of +-0 -- taken over the whole arrays on the host, fill rows and corners included, so a
+ *   caller who leaves complex or NaN-imaginary workspace there gets the complex path.
+ * maus_band_get_real: the mode.
+ * maus_band_real_plan: what a maus_band_solve call with this rhs_mode and these `count` shifts does on the bound matrix,
+ *   ordering and b: out[0] 1 = real, 0 = complex; out[1] MAUS_BAND_REAL_OK or the first condition of the rule that fails;
+ *   out[2] the kernel kind as maus_band_kernel_for (0 without an ordering); out[3] 1 where the split takes the band.
+ *   maus_band_solve decides by the same function.
+ * maus_band_real_kinds: without a context or a device: out[0] 1 when every kernel that an (n, kl, ku) band runs under
+ *   (method, split_mode, part_len) has a real instantiation, out[1] the kind as maus_band_plan, out[2] whether the split
+ *   takes the band.  Returns 0, or -1 for bad arguments (as maus_band_split_plan). */
+/* MAUS_BAND_REAL_NOT_CSR: no square CSR matrix with an ordering is bound; MAUS_BAND_REAL_NO_KERNELS: the method's plan for the
+ * band (or for the split's reduced system) is the blocked, tiled or wide method */
+enum { MAUS_BAND_REAL_OK = 0, MAUS_BAND_REAL_OFF = 1, MAUS_BAND_REAL_NOT_CSR = 2, MAUS_BAND_REAL_MATRIX_COMPLEX = 3,
+       MAUS_BAND_REAL_RHS_ROWS = 4, MAUS_BAND_REAL_RHS_COMPLEX = 5, MAUS_BAND_REAL_SHIFT_COMPLEX = 6, MAUS_BAND_REAL_NO_KERNELS = 7 };
+int maus_band_set_real(maus_ctx* ctx, int mode);
+int maus_band_get_real(maus_ctx* ctx);
+int maus_band_real_plan(maus_ctx* ctx, int rhs_mode, int count, const double* shift_c128, int32_t* out4);
+int maus_band_real_kinds(int method, int split_mode, int part_len, int n, int kl, int ku, int32_t* out3);
 int maus_sparse_max_n(void);
 int maus_band_prepare(maus_ctx* ctx, const int32_t* perm, int n, int* kl_out, int* ku_out);
 int maus_band_reserve(maus_ctx* ctx, int count, int* capacity_out);

@@ -39,6 +39,17 @@ the 1.25x bar of an opt-in schedule.  Then MAUS_Solver linear loop bodies on a t
 the direct path with sparse_direct 'band' and 'narrow'.
 
     python tools/band_rates.py --table narrow [--out profiles/band_narrow_rates.txt]
+
+With --table real: band solves in real arithmetic (maus_band_set_real(ctx, 1)) against the complex path of the same build, the
+two alternating in one process on the same real systems -> profiles/band_real_rates.txt.  Tridiagonal, pentadiagonal and
+kl = ku = 15 operators (real normal values on every diagonal, identity ordering, real shifts, b as the right-hand side) at
+n = 65536, 262144 and 2^20, each alone and in a batch of 64, under the column kernel, under the narrow method and under narrow
+with the split; one more row for the 5-point operator at n = 16384 (kl = 128) under the column kernel.  Per row the ms per solve
+of both paths (the better of two timed calls after one warm-up call) and complex ms / real ms against the 1.25x bar of an
+opt-in.  Then MAUS_Solver linear loop bodies on a real tridiagonal operator at n = 262144, P = 64 on the direct path under
+narrow + split with real_direct 'off' and 'on'.
+
+    python tools/band_rates.py --table real [--out profiles/band_real_rates.txt]
 """
 import argparse
 import os
@@ -420,13 +431,152 @@ def main_split(args):
     flush()
 
 
+def real_diagonals(n, k, seed=0):
+    """diagonals() with real normal values, stored as complex128 with imaginary parts +0.0."""
+    rng = np.random.default_rng(seed)
+    offs = list(range(-k, k + 1))
+    return sp.diags([rng.standard_normal(n - abs(o)) + 0j for o in offs], offs, format="csr")
+
+
+def timed_band_real(ctx, count, real, klass):
+    """timed_band on the linear-system form (rhs_mode 1, real shifts) with the real path on or off: the better of two timed
+    calls after one warm-up call, of the profile class the path counts in."""
+    rng = np.random.default_rng(2)
+    shift = rng.standard_normal(count) + 0j
+    psi = np.full(count, 1e-3)
+    slots = np.arange(count)
+    ctx.band_set_real(1 if real else 0)
+    assert ctx.band_real_plan(1, shift)["real"] == real
+    ctx.band_reserve(count)
+    ctx.band_solve(slots, shift, psi, 1)                       # warm-up
+    best = None
+    for _ in range(2):
+        ctx.profile_enable(False)
+        ctx.profile_enable(True)
+        st = ctx.band_solve(slots, shift, psi, 1)
+        pr = ctx.profile_read()["band_real" if real else klass]
+        assert (st == 0).all(), st
+        if best is None or pr["ms"] < best["ms"]:
+            best = pr
+    ctx.profile_enable(False)
+    return best
+
+
+def loop_rate_real(real_direct, n=262144, P=64, bodies=3):
+    """loop_rate_narrow on a real tridiagonal operator (diagonal near 4, off-diagonals of modulus <= 1) under narrow + split."""
+    import random
+    from adaptive_matrix_solver_amd.solver import MAUS_Solver, ProblemType, SolutionCandidate
+    rng = np.random.default_rng(8)
+    off = [rng.uniform(0.2, 1.0, n - 1) * rng.choice([-1.0, 1.0], n - 1) + 0j for _ in range(2)]
+    A = sp.diags([off[0], 4.0 + 0.1 * rng.standard_normal(n) + 0j, off[1]], [-1, 0, 1], format="csr")
+    b = rng.standard_normal(n) + 0j
+    np.random.seed(3); random.seed(3); SolutionCandidate._candidate_id_counter = 0
+    diag = {"is_sparse_init": True, "condition_number": 1e7, "is_singular": False, "is_hermitian": False,
+            "is_complex_symmetric": False}
+    s = MAUS_Solver(A, ProblemType.SOLVE_LINEAR_SYSTEM, b_vector=b, initial_num_candidates=P, quiet=True, sparse_mode="device",
+                    gmres_compat="scipy-legacy", sparse_direct="narrow", sparse_split="on", real_direct=real_direct, diag_info=diag)
+    s.loop_body(1)
+    ctx = s.engine.ctx
+    ctx.profile_enable(False)
+    ctx.profile_enable(True)
+    steps, t0 = 0, time.perf_counter()
+    for it in range(bodies):
+        steps += len(s.candidates)
+        s.loop_body(it + 2)
+    ctx.sync()
+    wall = time.perf_counter() - t0
+    pr = ctx.profile_read()
+    ctx.profile_enable(False)
+    ctx.close()
+    return steps / wall, (pr["band"]["ms"] + pr["band_split"]["ms"] + pr["band_real"]["ms"]) / bodies, pr["band_real"]["launches"]
+
+
+def main_real(args):
+    """The real path against the complex path, alternating in one process on the same real systems."""
+    ctx = _cabi.Context(0)
+    info = ctx.device_info()
+    head = (f"{'n':>8} {'kl':>3} {'ku':>3} {'batch':>5} {'schedule':>12} {'complex ms':>10} {'real ms':>10} {'complex/real':>12} "
+            f"{'real TB/s':>9} {'1.25x bar':>9}")
+    lines = [f"# band solves in real arithmetic (maus_band_set_real), csrc/band.hip, against the complex path of the same build, the two",
+             f"# alternating in one process on the same real systems -- {info['name']}, {info['cus']} CUs",
+             "# ms per solve from the 'band_real' / 'band' / 'band_split' profile class (HIP events around build + factor + solve of one",
+             "# batch), the better of two timed calls after one warm-up call; real normal values on every diagonal, identity ordering,",
+             "# real shifts, b as the right-hand side; real TB/s = the real path's byte count (the complex formulas at 8 B per value)",
+             "# over its time; bar: the 1.25x of an opt-in, complex ms / real ms, per row",
+             head]
+    missed = []
+
+    def flush():
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+    def row(n, kl, ku, P, name, method, split):
+        ctx.band_set_method(method)
+        ctx.band_set_split(split, 0)
+        klass = "band_split" if ctx.band_real_plan(1, np.zeros(1))["split"] else "band"
+        ms = {}
+        for real in (False, True):
+            pr = timed_band_real(ctx, P, real, klass)
+            ms[real] = pr["ms"] / P
+            if real:
+                tb = pr["bytes"] / (pr["ms"] / 1e3) / 1e12
+        up = ms[False] / ms[True]
+        if up < 1.25:
+            missed.append(f"{n}/{kl}/{P}/{name} {up:.2f}x")
+        lines.append(f"{n:>8} {kl:>3} {ku:>3} {P:>5} {name:>12} {ms[False]:>10.3f} {ms[True]:>10.3f} {up:>11.2f}x {tb:>9.3f} "
+                     f"{'met' if up >= 1.25 else 'MISSED':>9}")
+        print(lines[-1], flush=True)
+        flush()
+
+    def bind_real(A, P):
+        kl, ku = bind(ctx, A, P, identity=True)
+        ctx.set_rhs(np.random.default_rng(4).standard_normal(A.shape[0]) + 0j)
+        return kl, ku
+
+    only = args.only.split(",") if args.only else None
+    for k, n in [(k, n) for k in (1, 2, 15) for n in (65536, 262144, 1 << 20)]:
+        if only and f"{k}:{n}" not in only:
+            continue
+        kl, ku = bind_real(real_diagonals(n, k, k + n), 64)
+        assert (kl, ku) == (k, k)
+        for P in (1, 64):
+            for name, method, split in (("column", _cabi.BAND_COLUMN, False), ("narrow", _cabi.BAND_NARROW, False),
+                                        ("narrow+split", _cabi.BAND_NARROW, True)):
+                row(n, kl, ku, P, name, method, split)
+    if not only or "5pt" in only:
+        A = five_point(128, 7)
+        A.data = A.data.real + 0j
+        ctx.set_matrix_csr(A)
+        perm, kl, ku = band_order(A)
+        ctx.band_prepare(perm)
+        ctx.pop_reserve(64)
+        ctx.set_rhs(np.random.default_rng(4).standard_normal(16384) + 0j)
+        for P in (1, 64):
+            row(16384, kl, ku, P, "column", _cabi.BAND_COLUMN, False)
+    ctx.close()                                                # its workspaces would crowd out the solver's own context
+    if not only or "loop" in only:
+        lines += ["", "# MAUS_Solver linear loop bodies on a real tridiagonal operator at n = 262144, P = 64, direct path (gmres_compat=",
+                  "# 'scipy-legacy': every solve a band solve), sparse_direct='narrow', sparse_split='on': 1 untimed + 3 timed bodies;",
+                  "# candidate-steps = candidates at the start of each timed body"]
+        rates = {}
+        for rd in ("off", "on"):
+            rates[rd], band_ms, nreal = loop_rate_real(rd)
+            lines.append(f"real_direct={rd:<4} {rates[rd]:9.1f} candidate-steps/s   (band classes {band_ms:9.1f} ms per body, {nreal} real band calls)")
+            print(lines[-1], flush=True)
+        up = rates["on"] / rates["off"]
+        lines.append(f"on / off: {up:.2f}x candidate-steps/s ({'meets' if up >= 1.25 else 'MISSES'} the 1.25x bar)")
+        print(lines[-1], flush=True)
+    lines += ["", "# rows below the 1.25x bar (n/kl/batch/schedule): " + ("none" if not missed else ", ".join(missed))]
+    flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--table", choices=("blocked", "tiled", "wide", "narrow", "split"), default="blocked")
+    ap.add_argument("--table", choices=("blocked", "tiled", "wide", "narrow", "split", "real"), default="blocked")
     ap.add_argument("--out", default=None)
     ap.add_argument("--sizes", default="128:1,128:64,256:1,256:64,512:1,512:8")
     ap.add_argument("--only", default=None, help="--table tiled / wide: the wide-band rows whose label contains one of these, nothing else; "
-                         "--table narrow: the rows k:n (half-bandwidth:size) and 'loop' listed here, nothing else")
+                         "--table narrow / split / real: the rows k:n (half-bandwidth:size) and 'loop' (real: also '5pt') listed here, nothing else")
     ap.add_argument("--no-column", action="store_true", help="--table tiled: leave the column kernel's minutes out")
     ap.add_argument("--split", action="store_true", help="the split beside the narrow method (same as --table split); --only as for narrow")
     args = ap.parse_args()
@@ -441,6 +591,8 @@ def main():
         return main_wide(args)
     if args.table == "narrow":
         return main_narrow(args)
+    if args.table == "real":
+        return main_real(args)
     ctx = _cabi.Context(0)
     info = ctx.device_info()
     lines = [f"# band solves, csrc/band.hip, column kernel and blocked method in one process -- {info['name']}, {info['cus']} CUs",
